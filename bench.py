@@ -7,7 +7,15 @@ all-reduce of the LoRA gradients (N>1) -> global-norm clip + AdamW.  Inputs are 
 timed region starts.  Random-init weights of the real architecture (no network for checkpoints).
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_outputs
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --dump-outputs DIR writes what the last timed
+step computed (loss, adapter weights, AdamW moments; float32 .npy, fixed seeded samples of the large buffers) before the line is
+printed.  --full adds everything else the benchmark measures or checks: the per-launch roofline / bandwidth-kernel replay, the
+data-parallel exchange report and replica check (N > 1), the secondary lines (drop-in, sustained, host-fed, per-GPU batch 2,
+MX-FP8 trunk), the CPU baseline and the live PMC traffic passes (the --no-* switches below skip single ones of them).
 
 Prints ONE JSON line on rank 0 (see README/DESIGN for the field meanings).
 """
@@ -26,7 +34,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "qwen-image-finetune_amd"))
 
 BF = torch.bfloat16
-PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak of the MI355X
+DUMP_SAMPLE = 2 << 20      # --dump-outputs: elements kept of each flat fp32 buffer larger than this (3 x 8 MB)
 
 
 def algorithmic_flops(L, D, S_i, T, Jd, Cin, Cout, r, n_tgt):
@@ -259,6 +268,24 @@ def live_pmc_traffic(kernel="gemm256_kernel", budget_s=200):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(out_dir, step, loss):
+    """What a caller of the timed path holds after its last step: the step's loss, the updated adapter weights (flat fp32 buffer in
+    named_parameters() order) and the AdamW moments, as out_dir/<name>.npy in float32.  Buffers above DUMP_SAMPLE elements are
+    reduced to a fixed sample: the same seeded, sorted index set on every run of the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    st = step.dit.lora_store
+    n = st.pflat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(st.pflat.device)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    for name, buf in (("lora_params", st.pflat), ("adamw_exp_avg", step._m), ("adamw_exp_avg_sq", step._v)):
+        arrays[name] = buf.detach().float() if idx is None else buf.detach().float()[idx]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def self_spawn(n):
     """`python bench.py --gpus N` without a launcher: start N ranks through torch.distributed.run (one process per GPU, RCCL) and
     relay rank 0's JSON line."""
@@ -283,6 +310,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1, help="per-GPU micro batch")
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--rank", type=int, default=16, help="LoRA rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks (roofline replay, hbm_kernels, dp_exchange, drop-in, sustained, "
+                         "host-fed, batch 2, MX-FP8, CPU baseline, live PMC traffic); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; seeded samples of the large buffers)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batch2", action="store_true", help="skip the secondary per-GPU-batch-2 measurement")
     ap.add_argument("--no-fp8", action="store_true", help="skip the secondary MX-FP8 trunk measurement")
@@ -291,6 +323,8 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the committed PMC summary instead of two rocprofv3 passes of this run")
     ap.add_argument("--sustained-steps", type=int, default=150, help="steps of the secondary sustained-throughput line (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(args.gpus))
 
@@ -357,32 +391,34 @@ def main():
     dt = tmax.item()
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
-
-    # ---- dominant kernel (gemm_kernel): per-launch HIP-event timing on the launch stream, one extra replayed step
-    plan = list(dit._plans.values())[0]
-    dit.refresh_lora_operands()
-    gemm_fns = (L.lib.qfx_gemm_bf16, L.lib.qfx_gemm_grouped)
-    hbm = {}
-    ev = run_profiled(plan.fwd, gemm_fns, hbm)
-    ev += run_profiled(plan.bwd, gemm_fns, hbm)
-    torch.cuda.synchronize()
-    gemm_ms = sum(a.elapsed_time(b) for a, b in ev)
-    gf_f, n_f = gemm_flops_of(plan.fwd)
-    gf_b, n_b = gemm_flops_of(plan.bwd)
-    n_launch = n_f + n_b
-    achieved = (gf_f + gf_b) / (gemm_ms * 1e-3) / 1e12
-    step.zero_grad()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, loss)
 
     cfgd = dit.config
     fwd_fl, bwd_fl = algorithmic_flops(cfgd.num_layers, dit.inner_dim, 2 * S_t, T, Jd, cfgd.in_channels, dit.proj_out.out_features,
                                        args.rank, 4)
     traffic, traffic_src = (None, None)
-    if B == 1 and args.layers == 60 and args.res == 512 and args.rank == 16:
-        traffic, traffic_src = pmc_traffic()
+    if args.full:
+        # ---- dominant kernel (gemm_kernel): per-launch HIP-event timing on the launch stream, one extra replayed step
+        plan = list(dit._plans.values())[0]
+        dit.refresh_lora_operands()
+        gemm_fns = (L.lib.qfx_gemm_bf16, L.lib.qfx_gemm_grouped)
+        hbm = {}
+        ev = run_profiled(plan.fwd, gemm_fns, hbm)
+        ev += run_profiled(plan.bwd, gemm_fns, hbm)
+        torch.cuda.synchronize()
+        gemm_ms = sum(a.elapsed_time(b) for a, b in ev)
+        gf_f, n_f = gemm_flops_of(plan.fwd)
+        gf_b, n_b = gemm_flops_of(plan.bwd)
+        n_launch = n_f + n_b
+        achieved = (gf_f + gf_b) / (gemm_ms * 1e-3) / 1e12
+        step.zero_grad()
+        if B == 1 and args.layers == 60 and args.res == 512 and args.rank == 16:
+            traffic, traffic_src = pmc_traffic()
 
     # ---- data-parallel exchange: what the bucketed all-reduce costs on top of the step, and how much of it the backward hides
     dp = None
-    if world > 1:
+    if args.full and world > 1:
         try:      # adapter weights + optimizer state identical on every rank after the timed steps (every rank reaches the same verdict)
             replicas_ok = bool(step.check_replicas())
         except RuntimeError as e:
@@ -428,25 +464,27 @@ def main():
                    "step_tflop_algorithmic": round((fwd_fl + bwd_fl) * B / 1e12, 2),
                    "whole_step_tflops_per_gpu": round((fwd_fl + bwd_fl) * B / (ms_per_step * 1e-3) / 1e12, 1),
                    "loss": float(loss.item())},
-        "roofline": {"bound": "mfma", "kernel": "gemm256_kernel / gemm_kernel (qfx_gemm_grouped + qfx_gemm_bf16, all epilogue variants)",
-                     "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                     "traffic": traffic, "traffic_unit": "bytes per launch, L2 fabric side incl. Infinity-Cache hits (committed PMC pass)",
-                     "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": int(gemm_bytes_of(plan.fwd, plan.bwd) / n_launch),
-                     "launches_per_step": n_launch, "avg_launch_us": round(gemm_ms * 1e3 / n_launch, 2),
-                     "gemm_share_of_step": round(gemm_ms / ms_per_step, 3),
-                     # rounds 4-5: what actually limits these launches (ablations, not this run)
-                     "measured_limiter": "operand stream on the L2 -> CU vector-memory path (~32 B/clk/CU): 92 % of a launch remains with the matrix pipe idle, 94.5 % with the same requests as plain loads that never touch the LDS (profiles/r04_gemm_operand_stream.json, r05_gemm_stream_path.json); priced against the MFMA peak as the contract asks"},
+    }
+    if args.full:
+        out["roofline"] = {
+            "bound": "mfma", "kernel": "gemm256_kernel / gemm_kernel (qfx_gemm_grouped + qfx_gemm_bf16, all epilogue variants)",
+            "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+            "traffic": traffic, "traffic_unit": "bytes per launch, L2 fabric side incl. Infinity-Cache hits (committed PMC pass)",
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": int(gemm_bytes_of(plan.fwd, plan.bwd) / n_launch),
+            "launches_per_step": n_launch, "avg_launch_us": round(gemm_ms * 1e3 / n_launch, 2),
+            "gemm_share_of_step": round(gemm_ms / ms_per_step, 3),
+            # rounds 4-5: what actually limits these launches (ablations, not this run)
+            "measured_limiter": "operand stream on the L2 -> CU vector-memory path (~32 B/clk/CU): 92 % of a launch remains with the matrix pipe idle, 94.5 % with the same requests as plain loads that never touch the LDS (profiles/r04_gemm_operand_stream.json, r05_gemm_stream_path.json); priced against the MFMA peak as the contract asks"}
         # the bandwidth-bound kernels of the same replayed step (serial replay: the weight-gradient launches are timed alone here,
         # in the step they overlap the main stream): algorithmic bytes / summed launch time against the 8 TB/s HBM3E peak
-        "hbm_kernels": {k: {"GBps": round(v[1] / (sum(a.elapsed_time(b) for a, b in v[0]) * 1e-3) / 1e9, 1),
-                            "frac_of_8TBps": round(v[1] / (sum(a.elapsed_time(b) for a, b in v[0]) * 1e-3) / 8e12, 3),
-                            "ms_per_step": round(sum(a.elapsed_time(b) for a, b in v[0]), 3), "launches": v[2]}
-                        for k, v in sorted(hbm.items())},
-    }
+        out["hbm_kernels"] = {k: {"GBps": round(v[1] / (sum(a.elapsed_time(b) for a, b in v[0]) * 1e-3) / 1e9, 1),
+                                  "frac_of_8TBps": round(v[1] / (sum(a.elapsed_time(b) for a, b in v[0]) * 1e-3) / 8e12, 3),
+                                  "ms_per_step": round(sum(a.elapsed_time(b) for a, b in v[0]), 3), "launches": v[2]}
+                              for k, v in sorted(hbm.items())}
     if dp is not None:
         out["dp_exchange"] = dp
-    if world == 1 and B == 1 and not args.no_dropin:
+    if args.full and world == 1 and B == 1 and not args.no_dropin:
         # secondary line: the DROP-IN path a reference user gets after the two-line swap of INTEGRATION.md -- the reference's own
         # loop body (base_trainer.py:508-561): loss = criterion(dit(...)[0]); loss.backward(); clip_grad_norm_(trainable, 1.0);
         # torch.optim.AdamW.step(); zero_grad() -- autograd node around the same launch programs, torch's optimizer over the per-tensor
@@ -475,7 +513,7 @@ def main():
                                           "the reference's loop body (base_trainer.py:508-561) on the drop-in module; `value` above is the fused step"}
         del opt
         step.zero_grad()
-    if world == 1 and B == 1 and args.sustained_steps > 0:
+    if args.full and world == 1 and B == 1 and args.sustained_steps > 0:
         # secondary line: SUSTAINED throughput (`value` is a 20-40 step burst).  >= 150 back-to-back steps with no host
         # synchronisation inside the loop; per-step GPU time from one HIP event per step on the launch stream (durations between
         # consecutive events), wall clock around the whole run, package power / shader clock sampled by rocm-smi meanwhile.
@@ -525,7 +563,7 @@ def main():
                             "samples": len(smp),
                             "note": "same resident batch as `value`, no host sync in the loop; per-step times = gaps between per-step HIP events"}
         step.zero_grad()
-    if world == 1 and B == 1 and not args.no_hostfed:
+    if args.full and world == 1 and B == 1 and not args.no_hostfed:
         # secondary line: the step fed the way a training job feeds it -- the reference's on-disk embedding cache (fp16 .pt files,
         # SURVEY 8f1) -> PrefetchLoader (worker thread, pinned staging, upload on a side stream) -> train_step.  `value` above is
         # measured with the batch already resident in HBM; this is the disk + PCIe inclusive rate of the same step.
@@ -562,7 +600,7 @@ def main():
         finally:
             shutil.rmtree(root, ignore_errors=True)
         step.zero_grad()
-    if world == 1 and B == 1 and not args.no_batch2:
+    if args.full and world == 1 and B == 1 and not args.no_batch2:
         # secondary line: the reference's own default micro-batch for this config is 2 (configs/face_seg_config.yaml:31, and its
         # README numbers are quoted at bs 2).  At B=2 every GEMM runs >= 2 rounds per CU, so the per-launch fixed cost (pipeline
         # fill + exposed epilogue, ~12 us of a 45-170 us launch at B=1: profiles/r02_gemm_fixed_cost.json) is amortised.
@@ -588,7 +626,7 @@ def main():
         out["per_gpu_batch_2"] = {"value": round(2 * n2 / dt2, 4), "unit": "images/s", "ms_per_step": round(dt2 / n2 * 1e3, 3), "steps": n2,
                                   "gemm_frac_of_peak": round(gf2 / (gemm_ms2 * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
                                   "note": "same workload at the reference's default micro-batch (batch_size: 2); `value` above stays B=1"}
-    if world == 1 and B == 1 and not args.no_fp8:
+    if args.full and world == 1 and B == 1 and not args.no_fp8:
         # secondary line: the low-precision trunk (the reference's `model.quantize: true` analogue): forward + dX GEMMs of the block
         # linears in MX-FP8 on the block-scaled MFMA; NOT the headline precision (`dtype` above stays bf16)
         dit.quantize_trunk("mxfp8-fb")
@@ -605,12 +643,12 @@ def main():
         out["mxfp8_trunk"] = {"value": round(n8 / dt8, 4), "unit": "images/s", "ms_per_step": round(dt8 / n8 * 1e3, 3), "steps": n8,
                               "mode": "quantize_trunk('mxfp8-fb'): MX-FP8 forward + dX GEMMs, bf16 everywhere else",
                               "note": "reduced-precision option, reported beside the bf16 headline, never as `value`"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline((cfgd.attention_head_dim, cfgd.num_attention_heads, Jd, S_t, T))
         except Exception as e:  # the baseline is a reported side number; never let it kill the bench line
             out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e!r}"}
-    if rank == 0 and world == 1 and traffic is not None and not args.no_live_traffic:
+    if args.full and rank == 0 and world == 1 and traffic is not None and not args.no_live_traffic:
         lt, lsrc = live_pmc_traffic()
         if lt is not None:
             out["roofline"]["traffic_committed_summary"] = {"bytes_per_launch": traffic, **(traffic_src or {})}

@@ -106,12 +106,12 @@ def test_bench_two_ranks_share_one_gpu():
 
 def test_bench_self_spawns_its_ranks():
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE: bench.py starts its own ranks (torch.distributed.run) and
-    still prints exactly one JSON line carrying the data-parallel exchange report."""
+    still prints exactly one JSON line carrying the data-parallel exchange report (a --full line)."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(QFX_DIST_BACKEND="gloo", QFX_SHARE_GPU="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--layers", "2", "--res", "256"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--layers", "2", "--res", "256", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-2000:], out.stderr[-2000:])

@@ -4,7 +4,7 @@
 VAR=$1; A=$2; B=$3; R=${4:-2}; shift 4 2>/dev/null
 for i in $(seq 1 $R); do
   for v in $A $B; do
-    env $VAR=$v python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-batch2 --no-fp8 --no-dropin --no-hostfed "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-batch2 --no-fp8 --no-dropin --no-hostfed "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()
