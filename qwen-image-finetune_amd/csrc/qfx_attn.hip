@@ -32,9 +32,6 @@ namespace {
 // NW = waves per block (32 queries each).  8 waves / 256 queries, one block per CU, is used when it quantises better onto the
 // 256 CUs (S = 2432: 10 x 24 = 240 blocks, 94 % of the CUs, against 456 blocks on 512 half-CU slots = 89 %) and halves the K/V
 // LDS-DMA traffic per query; 4 waves / 128 queries, two blocks per CU, otherwise.
-#ifndef ATTN_DEFER_MAX
-#define ATTN_DEFER_MAX 8.0f     // log2 units; -DATTN_DEFER_MAX=0.0f = the eager running maximum of rounds 1-3
-#endif
 template <int DH, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(const qfx_attn_args a) {
   constexpr int KC = DH / 32, DF = DH / 16;
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(cons
     // against that row's reference, one wave vote); the cross-lane row maximum is only formed when the reference has to move.  On
     // typical data the reference settles within the first tiles and both the reduction and the 64-register rescale of O leave the
     // loop.  (-inf - -inf = NaN compares false: the first tile and fully masked rows take the update path.)
-    if (!__all(mx[0] * cs - mrow[0] <= ATTN_DEFER_MAX && mx[1] * cs - mrow[1] <= ATTN_DEFER_MAX)) {
+    if (!__all(mx[0] * cs - mrow[0] <= DEFER_MAX && mx[1] * cs - mrow[1] <= DEFER_MAX)) {
       float alpha[2];
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
@@ -323,14 +320,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(c
     dsm[f] = part;
     if (g == 0 && q0 + f * 16 + li < S) a.dsum[((int64_t)b * a.H + h) * a.S_pad + q] = part;
   }
-#if !defined(QFX_ATTN_NO_CLAIM)
 #pragma unroll
   for (int f = 0; f < 2; ++f) {      // round 6: claim the prologue's loads before the tile loop (see attn_bwd_dkv_kernel)
 #pragma unroll
     for (int kk = 0; kk < KC; ++kk) { asm volatile("" : "+v"(qf[f][kk])); asm volatile("" : "+v"(dof[f][kk])); }
     asm volatile("" : "+v"(lse[f]), "+v"(dsm[f]));
   }
-#endif
   f32x4 dq[DF][2];
 #pragma unroll
   for (int d = 0; d < DF; ++d) { dq[d][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; dq[d][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
@@ -531,14 +526,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv_kernel(const qfx_attn_arg
   // Round 6: claim the prologue's register loads BEFORE the tile loop.  hipcc does not see the hand-placed s_waitcnt vmcnt(0) at the top
   // of the loop; left pending in its model, the K fragment loads got counted waits (vmcnt(10) ... vmcnt(3)) at their first use INSIDE
   // the loop, every iteration, right behind the 4-5 LDS-DMA pieces of the next tile -- vmcnt(3) then waits for the oldest of those.
-#if !defined(QFX_ATTN_NO_CLAIM)
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
 #pragma unroll
     for (int kk = 0; kk < KC; ++kk) asm volatile("" : "+v"(kf[f][kk]));
     asm volatile("" : "+v"(mk[f]));
   }
-#endif
   f32x4 dk[DF][2], dv[DF][2];
 #pragma unroll
   for (int d = 0; d < DF; ++d)

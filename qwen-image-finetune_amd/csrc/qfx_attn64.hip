@@ -26,17 +26,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-// ablation lever (wrong results): -DQFX_A64_NOEXP replaces the exponentials of the pipelined forward by moves -- what do they cost a lone wave?
-#if defined(QFX_A64_NOEXP)
-#define A64_EXP "v_mov_b32"
-#else
-#define A64_EXP "v_exp_f32"
-#endif
-
-#ifndef ATTN_DEFER_MAX
-#define ATTN_DEFER_MAX 8.0f
-#endif
-
 // every statement that writes the hand-allocated half names all of it: the compiler then holds nothing there across our statements
 #define A64_CLOB \
   "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", \
@@ -169,8 +158,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(const qfx_attn_args 
     const int rr = lane >> 4, c = lane & 15, ii = i & 3;
     const int row = 16 * w + 4 * ii + rr;
     int s = jt * 64 + row; s = s < S ? s : S - 1;
-    if (i < 4) glds16a(Kb + (row_off(s, a.ldk) + (unsigned)((c ^ swz_row<DH>(row)) * 8)), dK + (16 * w + 4 * ii) * 256);
-    else glds16a(Vb + (row_off(s, a.ldv) + (unsigned)((c ^ (rr << 2)) * 8)), dK + TB + (16 * w + 4 * ii) * 256);
+    if (i < 4) glds16(Kb + (row_off(s, a.ldk) + (unsigned)((c ^ swz_row<DH>(row)) * 8)), dK + (16 * w + 4 * ii) * 256);
+    else glds16(Vb + (row_off(s, a.ldv) + (unsigned)((c ^ (rr << 2)) * 8)), dK + TB + (16 * w + 4 * ii) * 256);
   };
   auto stage = [&](int jt, int buf) {
 #pragma unroll
@@ -325,7 +314,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64_kernel(const qfx_attn_args 
       if constexpr (i == 2) {
         float mx = fmaxf(mxa, mxb);
         // lazy reference maximum (qfx_attn.hip): the reference of a row moves only when a score of this tile exceeds it by > 2^8
-        if (__builtin_expect(!__all(mx * cs - mrow[qb] <= ATTN_DEFER_MAX), 0)) {
+        if (__builtin_expect(!__all(mx * cs - mrow[qb] <= DEFER_MAX), 0)) {
           const uint32_t u1 = __float_as_uint(mx);
           const auto r1 = __builtin_amdgcn_permlane32_swap(u1, u1, false, false);
           mx = fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
@@ -493,8 +482,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64p_kernel(const qfx_attn_args
     const int row = 16 * w + 4 * ii + rr;
     int s = jt * 64 + row; s = s < S ? s : S - 1;
     const unsigned sc = (unsigned)((c ^ swz64(row)) * 8);
-    if (i < 4) glds16a(Kb + (row_off(s, a.ldk) + sc), dK + (16 * w + 4 * ii) * 256);
-    else glds16a(Vb + (row_off(s, a.ldv) + sc), dK + TB + (16 * w + 4 * ii) * 256);
+    if (i < 4) glds16(Kb + (row_off(s, a.ldk) + sc), dK + (16 * w + 4 * ii) * 256);
+    else glds16(Vb + (row_off(s, a.ldv) + sc), dK + TB + (16 * w + 4 * ii) * 256);
   };
   auto stage = [&](int jt, int buf) {
 #pragma unroll
@@ -633,7 +622,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64p_kernel(const qfx_attn_args
       auto vote = [&](auto QB) {
         constexpr int qb = QB.value;
         float mx = mxs[qb];
-        if (__builtin_expect(!__all(mx * cs - mrow[qb] <= ATTN_DEFER_MAX), 0)) {
+        if (__builtin_expect(!__all(mx * cs - mrow[qb] <= DEFER_MAX), 0)) {
           const uint32_t u1 = __float_as_uint(mx);
           const auto r1 = __builtin_amdgcn_permlane32_swap(u1, u1, false, false);
           mx = fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
@@ -660,7 +649,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd64p_kernel(const qfx_attn_args
         uint32_t pw;
         asm volatile(
             "v_fma_f32 %5, %7, %9, %10\n\tv_fma_f32 %6, %8, %9, %10\n\tv_add_f32 %1, %1, %3\n\tv_add_f32 %2, %2, %4\n\t"
-            "v_cvt_pk_bf16_f32 %0, %3, %4\n\t" A64_EXP " %3, %5\n\t" A64_EXP " %4, %6"
+            "v_cvt_pk_bf16_f32 %0, %3, %4\n\tv_exp_f32 %3, %5\n\tv_exp_f32 %4, %6"
             : "=&v"(pw), "+v"(l0), "+v"(l1), "+v"(e0), "+v"(e1), "=&v"(t0), "=&v"(t1)
             : "v"(Sc[qb][k]), "v"(Sc[qb][k + 1]), "v"(cs), "v"(negm[qb]));
         ls0[qb] = l0; ls1[qb] = l1; pe0[qb] = e0; pe1[qb] = e1;
@@ -817,8 +806,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(const qfx_attn_ar
     const int row = 16 * w + 4 * ii + rr;
     int s = jt * 64 + row; s = s < S ? s : S - 1;
     const unsigned sc = (unsigned)((c ^ swz64(row)) * 8);
-    if (i < 4) glds16a(Kb + (row_off(s, a.ldk) + sc), dK + (16 * w + 4 * ii) * 256);
-    else glds16a(Vb + (row_off(s, a.ldv) + sc), dK + TB + (16 * w + 4 * ii) * 256);
+    if (i < 4) glds16(Kb + (row_off(s, a.ldk) + sc), dK + (16 * w + 4 * ii) * 256);
+    else glds16(Vb + (row_off(s, a.ldv) + sc), dK + TB + (16 * w + 4 * ii) * 256);
   };
   auto stage = [&](int jt, int buf) {
 #pragma unroll

@@ -32,15 +32,8 @@ constexpr int DH = 128, KC = DH / 32, DF = DH / 16, NW = 8;
 constexpr int TB = 64 * DH * 2;                 // bytes of a 64-row tile
 constexpr int DSROW = 128;                      // bytes of a dS row: 64 queries x bf16
 constexpr int ACC_TILE = 64 * DH;               // floats of one dQ tile in the workspace
-// Ablation switches of the timing builds (tools/build_variants.py x=-DBWD1_ABL=<mask>; wrong results): 1 = no turn wait / accumulated-tile
-// load / add, 2 = no workspace stores, 4 = no dQ MFMA loop, 8 = no dS tile writes, 16 = no mid-tile barrier, 32 = no
-// rotation (every key block starts at tile 0), 64 = no zeroing of dS for keys past S, 128 = statistics are constants (no DPP).  0 in the product.
-#ifndef BWD1_ABL
-#define BWD1_ABL 0
-#endif
-#ifndef BWD1_STORE_AUX
-#define BWD1_STORE_AUX 16      // cache policy of the workspace stores: 16 = sc1 (agent scope: what the protocol needs); 0 / 1 / 2 = plain / sc0 / nt timing experiments
-#endif
+// Where the time of this kernel goes, from ablation builds: profiles/r06_attn_onepass.json.
+constexpr int STORE_SC1 = 16;            // cache policy of the workspace stores: sc1, agent scope (what the hand-off protocol needs)
 constexpr int SPIN_LIMIT = 1 << 20;      // ~1 s of polling: a turn that never comes is a trap, not a hang
 
 template <class F, int... I> __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) {
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
     int* turnb = a.dq_turn + ((int64_t)b * H + h) * ntiles;
     const int64_t accbytes = (int64_t)ntiles * ACC_TILE * 4;
     const __amdgpu_buffer_rsrc_t accr = __builtin_amdgcn_make_buffer_rsrc((void*)accb, 0, accbytes > 0x7fffffff ? 0x7fffffff : (int)accbytes, 0x27000);
-    const int st = (BWD1_ABL & 32) ? 0 : (kbi * ntiles) / nkb;          // first query tile of this key block
+    const int st = (kbi * ntiles) / nkb;          // first query tile of this key block
     const bool ktail = kb0 + 256 > S;             // block-uniform: some keys of this block lie past S
 
     auto stage = [&](int ti, int buf) {
@@ -188,7 +181,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
       // for them here would expose a full store round trip in every iteration.  They are known complete at the NEXT top (they are older
       // than that iteration's stores), so a tile's turn is handed on two tops after it was accumulated.
       if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if constexpr (BWD1_ABL & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       __syncthreads();                                    // ... everyone's; everyone is done with the dS tile and the stage of it-1
       if (it > 1 && tid == 0) __hip_atomic_store(turnb + rel_ti, rel_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -233,8 +225,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
           __builtin_amdgcn_sched_barrier(0);
           // per-query statistics of this fragment's four rows: -dsum[q] is where the dP chains START (the MFMA takes it as its C operand:
           // the subtraction dP - dsum costs nothing), lse2[q] rides in the FMA that feeds the exponential
-          const f32x4 l4 = (BWD1_ABL & 128) ? (f32x4){lse_c, lse_c, lse_c, lse_c} : stat4<qfi>(lse_c);
-          const f32x4 s4n = (BWD1_ABL & 128) ? (f32x4){dsn_c, dsn_c, dsn_c, dsn_c} : stat4<qfi>(dsn_c);
+          const f32x4 l4 = stat4<qfi>(lse_c);
+          const f32x4 s4n = stat4<qfi>(dsn_c);
           f32x4 sa[2], da[2];
           sa[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; sa[1] = sa[0]; da[0] = s4n; da[1] = s4n;
 #pragma unroll
@@ -284,8 +276,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
             dsu[f][2 * q2] = pack2bf(da[f][0], da[f][1]); dsu[f][2 * q2 + 1] = pack2bf(da[f][2], da[f][3]);
             u32x2 dsw = {dsu[f][2 * q2], dsu[f][2 * q2 + 1]};
             // keys past S ride along on row S - 1: their dS must not reach dQ (only the LDS copy: their dK / dV rows are never stored)
-            if (ktail && !(BWD1_ABL & 64) && key0 + f * 16 + li >= S) dsw = (u32x2){0u, 0u};
-            if constexpr (!(BWD1_ABL & 8)) *(QFX_AS3 u32x2*)((dwb ^ (qfi << 5)) + f * (16 * DSROW)) = dsw;
+            if (ktail && key0 + f * 16 + li >= S) dsw = (u32x2){0u, 0u};
+            *(QFX_AS3 u32x2*)((dwb ^ (qfi << 5)) + f * (16 * DSROW)) = dsw;
           }
         });
         const bf16x8 pb0 = __builtin_bit_cast(bf16x8, pbu[0]), pb1 = __builtin_bit_cast(bf16x8, pbu[1]);
@@ -301,7 +293,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
           dk[d][1] = MFMA(qt, ds1, dk[d][1]);
         }
       });
-      if constexpr (!(BWD1_ABL & 16)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the dS tile is complete (the next tile's DMA stays in flight)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the dS tile is complete (the next tile's DMA stays in flight)
       if (it + 1 < ntiles) {      // next tile's statistics: requested HERE (their registers are free from the last softmax on) so that they
         // have the whole dQ phase to arrive -- requested at the end of the iteration, the top-of-loop wait exposed their full latency
         // in every iteration (PMC: +50 M parked wave cycles per launch against the two-pass dK/dV kernel)
@@ -315,8 +307,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
       // every scratch access waits vmcnt(0)).
       const int aoff = ti * (ACC_TILE * 4) + w * 4096;
       char* sOld = sStage + buf * 2 * TB + w * 4096;
-      if constexpr (BWD1_ABL & 1) asm volatile("" :: "v"(tv));      // (ablation builds: keep the flag load's register claimed as the product does)
-      if (rank != 0 && !(BWD1_ABL & 1)) {
+      if (rank != 0) {
         int spins = 0;
         while (__builtin_amdgcn_readfirstlane(tv) != rank) {
           __builtin_amdgcn_s_sleep(2);
@@ -335,7 +326,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
         const uint32_t tk0 = tkb ^ ((2 * dq_) << 5), tk1 = tkb ^ ((2 * dq_ + 1) << 5);
         const uint32_t dr0 = drb ^ ((2 * qh) << 5), dr1 = drb ^ ((2 * qh + 1) << 5);
 #pragma unroll
-        for (int kc = 0; kc < ((BWD1_ABL & 4) ? 0 : 8); ++kc) {
+        for (int kc = 0; kc < 8; ++kc) {
           constexpr int HI = 16 * DH * 2;
           const int ko = (kc >> 1) * TB + (kc & 1) * (32 * DH * 2), so = kc * (32 * DSROW);
           const bf16x8 k0 = ldstr(tk0 + ko, tk0 + ko + HI), k1 = ldstr(tk1 + ko, tk1 + ko + HI);
@@ -346,7 +337,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
           qacc[1][1] = MFMA(k1, s1, qacc[1][1]);
         }
       }
-      if (rank != 0 && !(BWD1_ABL & 1)) {
+      if (rank != 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the accumulated tile has landed (so has the next tile's Q | dO)
         const uint32_t lo_ = lQ + w * 4096 + ln_ * 16;
 #pragma unroll
@@ -363,8 +354,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd1_kernel(const qfx_attn_args a
         }
       }
 #pragma unroll
-      for (int fi = 0; fi < ((BWD1_ABL & 2) ? 0 : 4); ++fi)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, qacc[fi >> 1][fi & 1]), accr, ln_ * 16, aoff + fi * 1024, BWD1_STORE_AUX);
+      for (int fi = 0; fi < 4; ++fi)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, qacc[fi >> 1][fi & 1]), accr, ln_ * 16, aoff + fi * 1024, STORE_SC1);
       prev_ti = ti;
       prev_next = rank == nkb - 1 ? 0 : rank + 1;      // the last key block leaves the counter at zero for the next launch
       // next tile (rotation) and its first arriver

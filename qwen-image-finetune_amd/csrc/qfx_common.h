@@ -34,11 +34,7 @@ __device__ __forceinline__ uint32_t pack2bf_scalar(float lo, float hi) { return 
 typedef __attribute__((ext_vector_type(2))) __bf16 qfx_bf16x2;
 typedef __attribute__((ext_vector_type(2))) float qfx_f32x2;
 __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
-#if defined(QFX_PACK2BF_SCALAR)     // the 4-instruction form of rounds 1-3 (A/B lever)
-  return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-#else
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((qfx_f32x2){lo, hi}, qfx_bf16x2));
-#endif
 }
 
 // gelu(approximate="tanh"): 0.5 x (1 + tanh(u)) = x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3), evaluated with the

@@ -248,42 +248,20 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const qfx_gemm_args p) {
 // The wide counterparts 160 x 384 (two full rounds for N = 12288; 120 accumulators leave the allocator four registers short: scratch
 // reloads inside the K loop) and 160 x 256 (three rounds) were built and measured +13 % / +24 % against 256 x 256: removed.
 // The launcher picks the geometry per launch from rounds x relative tile time (qfx_gemm_grouped).
-#ifndef QFX_GEMM_NLD
-#define QFX_GEMM_NLD 4
-#endif
-#ifndef QFX_GEMM_PF_DIST
-#define QFX_GEMM_PF_DIST 0      // K tiles an L2 prefetch runs ahead of the K loop (0 = off), see the compute waves
-#endif
-#ifndef QFX_GEMM_AUX_DMA
-#define QFX_GEMM_AUX_DMA 1      // bit 0: d(GELU) epilogue, bit 1: gate + residual epilogue (measured SLOWER: profiles/r06_gemm_aux_landing.json) -- the aux rows of the next pass come in by LDS-DMA instead of a load inside the pass (0 = rounds 1-5)
-#endif
-#ifndef QFX_GEMM_NT_SAVED
-#define QFX_GEMM_NT_SAVED 0     // non-temporal stores for outputs that are only read in the backward: bit 0 the GELU epilogue's pre-activation, bit 1 the gate epilogue's pre-gate output
-#endif
-#ifndef QFX_GEMM_KSTAGGER
-#define QFX_GEMM_KSTAGGER 0     // K tiles between the starting points of neighbouring tiles' K loops (0 = every tile starts at k = 0), see the loader waves
-#endif
-constexpr int NLD = QFX_GEMM_NLD;                 // loader waves
+// Measured and not kept: an L2 prefetch ahead of the loaders (profiles/r04_gemm_operand_stream.json), K loops de-phased between
+// panel-sharing tiles (profiles/r05_gemm_kstagger.json), non-temporal stores of the outputs only the backward reads
+// (profiles/r06_nt_saved.json).
+constexpr int NLD = 4;                            // loader waves
 constexpr int WS_THREADS = 512 + 64 * NLD;
 constexpr int STG_BYTES = 2048;                   // per compute wave: 16 rows x 64 bf16 staging for the epilogue
 constexpr int QFX_NUM_CU = 256;                   // MI355X
 template <int BMT, int TN> struct TileCfg {
   static constexpr bool WIDE = TN >= 256;           // streaming K loop
-  // K depth of a ring stage.  The wide tile's operands are 64 KB per 64-deep K tile: two such stages hold ONE tile in flight.
-  // -DQFX_GEMM_WIDE_BK32 builds it with four 32-deep stages instead (32 KB each, three in flight, one barrier per 32 MFMAs and
-  // wave, 64-byte stage rows): measured 4 % SLOWER (148.0 -> 154.1 / 136.6 -> 142.4 us, profiles/r04_gemm_operand_stream.json) --
-  // the wide tile's loop period is not "DMA latency + transfer" after all; kept as an A/B lever.
-#if defined(QFX_GEMM_WIDE_BK32)
-  static constexpr int BKT = WIDE ? 32 : 64;
-#else
+  // K depth of a ring stage.  The wide tile's operands are 64 KB per 64-deep K tile: two such stages hold ONE tile in flight
+  // (four 32-deep stages measured 4 % slower: profiles/r04_gemm_operand_stream.json).
   static constexpr int BKT = 64;
-#endif
   static constexpr int STAGE = (BMT + TN) * BKT * 2;
-#if defined(QFX_GEMM_ABL_NST2)     // ablation: one K tile in flight on the narrow tiles too (how much of the K loop is DMA latency?)
-  static constexpr int NST = 2;
-#else
-  static constexpr int NST = WIDE ? (BKT == 32 ? 4 : 2) : 3;
-#endif
+  static constexpr int NST = WIDE ? 2 : 3;
   static constexpr int WRN = (BMT == 256 && TN == 128) ? 4 : 2;     // compute waves along M
   static constexpr int WCN = 8 / WRN;               // ... along N
   static constexpr int MI = BMT / WRN / 16;         // 16-row MFMA fragments per wave
@@ -350,12 +328,8 @@ __device__ __forceinline__ void tile_coord(KGroupedArgs& ga, int nwg, int bid, i
   const int tiles_m = (M + BMT - 1) / BMT, tiles_n = (N + TN - 1) / TN;
   // M-tiles a supertile walks before the next N-tile: the XCD patch is GM x (32 / GM) tiles.  8 x 4 moves the fewest operand rows per
   // XCD; the six-problem q/k/v launch (13 + 3 M-tiles per stream, K = 3072) measures 3 % faster on 4 x 8 (profiles/r05_gemm_stream_path.json),
-  // every other class 0.3-1 % slower: chosen per launch (qfx_gemm_grouped), -DQFX_GEMM_GM forces one value (A/B builds).
-#if defined(QFX_GEMM_GM)
-  constexpr int GM = QFX_GEMM_GM;
-#else
+  // every other class 0.3-1 % slower: chosen per launch (qfx_gemm_grouped).
   const int GM = ga.gm;
-#endif
   const int per = GM * tiles_n, sg = lt / per, first = sg * GM;
   const int gsz = (tiles_m - first) < GM ? (tiles_m - first) : GM;
   const int in = lt - sg * per;
@@ -371,13 +345,13 @@ template <int EPI, int BMT, int TN, bool FP8 = false, bool SPLIT = false>
 __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArgs ga_by_value) {
   static_assert(!(FP8 && !(BMT == 256 && TN == 128)), "the MX-FP8 instantiation uses the 256x128 tile (the streaming loops have no registers for 8-VGPR operands)");
   using TC = TileCfg<BMT, TN>;
-  static_assert(!SPLIT || (TC::WIDE && TC::BKT == 64 && !FP8), "split-K runs on the 256x256 bf16 tile");
+  static_assert(!SPLIT || (TC::WIDE && !FP8), "split-K runs on the 256x256 bf16 tile");
   constexpr int STAGE_BYTES = TC::STAGE, NSTAGE = TC::NST, MI = TC::MI, NI = TC::NI, NG = TC::NG, NGRP = TC::NGRP;
-  constexpr int BKT = TC::BKT;     // K depth of a ring stage (64; 32 on the wide tile)
-  static_assert(!(FP8 && BKT != 64), "the MX-FP8 operands need 64-element (128-byte) stage rows");
+  constexpr int BKT = TC::BKT;     // K depth of a ring stage
   constexpr int WCOLS = 16 * NI;   // columns per compute wave
-  // dGELU epilogue with its aux rows by LDS-DMA (round 6; see the epilogue)
-  constexpr bool AUXDMA = (QFX_GEMM_AUX_DMA != 0) && !FP8 && !SPLIT && TC::AUX_FITS && (EPI == QFX_EPI_DGELU || (EPI == QFX_EPI_GATE_RES && (QFX_GEMM_AUX_DMA & 2)));
+  // dGELU epilogue with its aux rows by LDS-DMA (round 6; see the epilogue).  The gate + residual epilogue measured slower with it
+  // (profiles/r06_gemm_aux_landing.json).
+  constexpr bool AUXDMA = !FP8 && !SPLIT && TC::AUX_FITS && EPI == QFX_EPI_DGELU;
   __shared__ __attribute__((aligned(16))) char smem[NSTAGE * STAGE_BYTES + 8 * STG_BYTES + (AUXDMA ? 8 * TC::AUXW : 0)];
   KGroupedArgs& ga = *(KGroupedArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // == ga_by_value (sole explicit argument)
 
@@ -389,30 +363,24 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
   if (w >= 8) {
     // ================================================================ loader waves
     const int lw = w - 8;
-    constexpr int CPR = BKT / 8, RPP = 64 / CPR;      // 16-byte chunks per stage row, rows per 1 KiB DMA piece (8 x 128 B or 16 x 64 B)
+    constexpr int CPR = BKT / 8, RPP = 64 / CPR;      // 16-byte chunks per stage row, rows per 1 KiB DMA piece (8 x 128 B)
     constexpr int NA = (BMT / RPP) / NLD, NB = (TN / RPP) / NLD;   // DMA pieces per K stage per loader wave
     static_assert(NLD % 2 == 0 && (BMT / RPP) % NLD == 0 && (TN / RPP) % NLD == 0 && (NSTAGE - 1) * (NA + NB) < 64, "loader split / vmcnt immediate");
     const int srow = lane / CPR, schunk = lane % CPR;
-    // source column incl. the bank swizzle, the same for every piece of a loader wave.  128-byte rows: chunk ^ ((row >> 1) & 7) (piece
-    // parity = lw & 1 for an even number of loader waves).  64-byte rows: chunk ^ (-(row >> 2) & 3) -- the four rows r, r+4, r+8, r+12
-    // that share a 64-byte slot of the 256-byte bank row then take four different chunks in every ds_read_b128 lane group.
-    const int sc = BKT == 64 ? (schunk ^ (((lw & 1) * 4 + (srow >> 1)) & 7)) * 8 : (schunk ^ ((0 - (srow >> 2)) & 3)) * 8;
+    // source column incl. the bank swizzle, the same for every piece of a loader wave: chunk ^ ((row >> 1) & 7) (piece parity =
+    // lw & 1 for an even number of loader waves)
+    const int sc = (schunk ^ (((lw & 1) * 4 + (srow >> 1)) & 7)) * 8;
     const bf16_t* pa[NA];
     const bf16_t* pb[NB];
     int ibid = blockIdx.x, it = 0, int1 = 0, intt = 0, ist = 0;
     int im0 = 0, in0 = 0, iM = 1, iN = 1;          // issue cursor's tile (rows are recomputed at the LoRA-segment switch)
     const bf16_t* iA2 = nullptr; const bf16_t* iB2 = nullptr;
     int ilda2 = 0, ildb2 = 0;
-    int ikt0 = 0;                                   // K tile the base segment starts at (split-K: the work item's half; QFX_GEMM_KSTAGGER: wraps around)
+    int ikt0 = 0;                                   // K tile the base segment starts at (split-K: the work item's half)
     auto setp = [&](int bid) {
       int gi;
       int ihalf = 0;
-#if QFX_GEMM_KSTAGGER > 0
-      int tin_, tgsz_;
-      tile_coord<BMT, TN, SPLIT>(ga, nwg, bid, gi, im0, in0, &tin_, &tgsz_, &ihalf);
-#else
       tile_coord<BMT, TN, SPLIT>(ga, nwg, bid, gi, im0, in0, nullptr, nullptr, &ihalf);
-#endif
       KArgs& p = ga.g[gi];
       int1 = p.K1 / BKT; intt = int1 + p.K2 / BKT;
       if constexpr (SPLIT) {                        // consumer: K tiles [0, kh) + the LoRA segment; producer: [kh, K1 / BKT)
@@ -420,14 +388,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
         if (ihalf) { ikt0 = kh; int1 -= kh; intt = int1; }
         else { ikt0 = 0; int1 = kh; intt = kh + p.K2 / BKT; }
       }
-#if QFX_GEMM_KSTAGGER > 0
-      // The ~32 tiles an XCD runs at a time share A panels 4 ways and B panels 8 ways and walk K in lockstep: every operand line is a
-      // compulsory L2 miss that ALL its sharers wait for together.  Starting the base segment QFX_GEMM_KSTAGGER K tiles apart by tile
-      // parity (fp32 sums are re-ordered, nothing else changes) lets half the sharers find the line already resident.  Measured
-      // (profiles/r05_gemm_kstagger.json): 1-2 % SLOWER at 2 / 4 / 8 K tiles on every launch class -- lockstep sharers merge their
-      // misses, the stream is bandwidth- not latency-bound.  A/B lever only (default 0: this code is not compiled).
-      if constexpr (!FP8) { ikt0 = ((((tin_ % tgsz_) & 1) + 2 * ((tin_ / tgsz_) & 1)) * QFX_GEMM_KSTAGGER) % int1; }
-#endif
       iA2 = p.A2; iB2 = p.B2; ilda2 = p.lda2; ildb2 = p.ldb2; iM = p.M; iN = p.N;
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
@@ -441,9 +401,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       }
     };
     bool more = true;
-#if defined(QFX_GEMM_ABL_DMA_TO_VGPR)
-    u32x4 abl_sink = {0u, 0u, 0u, 0u};
-#endif
     auto issue = [&]() {
       if (it == int1) {  // first K tile of the LoRA segment (A2 rows are never remapped)
 #pragma unroll
@@ -459,36 +416,11 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       }
       char* sA = smem + ist * STAGE_BYTES;
       char* sB = sA + BMT * BKT * 2;
-#if QFX_GEMM_KSTAGGER > 0
-      int kt_ = it < int1 ? it + ikt0 : it - int1;
-      if (it < int1 && kt_ >= int1) kt_ -= int1;
-      const int koff = kt_ * BKT;
-#else
       const int koff = (it < int1 ? it + (SPLIT ? ikt0 : 0) : it - int1) * BKT;
-#endif
-#if defined(QFX_GEMM_ABL_HALF_DMA)   // ablation (results are garbage): every other DMA piece -- is the K loop bound by the L2 -> LDS stream?
-#pragma unroll
-      for (int i = 0; i < NA; i += 2) glds16(pa[i] + koff, sA + (lw + i * NLD) * 1024);
-#pragma unroll
-      for (int i = 0; i < NB; i += 2) glds16(pb[i] + koff, sB + (lw + i * NLD) * 1024);
-#elif defined(QFX_GEMM_ABL_DMA_TO_VGPR)   // ablation (garbage results): the same requests as plain 16-byte loads into a register nobody reads -- is the
-                                         // stream bound on the L2 -> vector-memory path, or on the LDS side of the LDS-DMA?  (_B: only the weight half)
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-#if defined(QFX_GEMM_ABL_DMA_TO_VGPR_B)
-        glds16(pa[i] + koff, sA + (lw + i * NLD) * 1024);
-#else
-        asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(abl_sink) : "v"(pa[i] + koff) : "memory");
-#endif
-      }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(abl_sink) : "v"(pb[i] + koff) : "memory");
-#else
 #pragma unroll
       for (int i = 0; i < NA; ++i) glds16(pa[i] + koff, sA + (lw + i * NLD) * 1024);
 #pragma unroll
       for (int i = 0; i < NB; ++i) glds16(pb[i] + koff, sB + (lw + i * NLD) * 1024);
-#endif
       ist = ist + 1 == NSTAGE ? 0 : ist + 1;
       if (++it == intt) {
         it = 0; ibid += gridDim.x; more = ibid < nwg;
@@ -511,22 +443,14 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       }
       for (int t = 0; t < ntw; ++t) {
         // the oldest K stage in flight must have landed; the ones issued after it (PPS pieces each) may still be in flight
-#if defined(QFX_GEMM_ABL_HALF_DMA)
-        constexpr int PPS = (NA + 1) / 2 + (NB + 1) / 2;
-#else
         constexpr int PPS = NA + NB;
-#endif
-        if (NSTAGE > 3 && ahead >= 3) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(2 * PPS) : "memory");
-        else if (NSTAGE > 2 && ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(PPS) : "memory");
+        if (NSTAGE > 2 && ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(PPS) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         --ahead;
         if (more) { issue(); ++ahead; }   // into the stage every compute wave left before this barrier
       }
     }
-#if defined(QFX_GEMM_ABL_DMA_TO_VGPR)
-    asm volatile("s_waitcnt vmcnt(0)" :: "v"(abl_sink) : "memory");
-#endif
     return;
   }
 
@@ -536,8 +460,9 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
   char* stg = smem + NSTAGE * STAGE_BYTES + w * STG_BYTES;
   int buf = 0;
   (void)lane;
-  // destination of the (uncounted) prefetch loads: ONE register reserved for the whole persistent loop -- hipcc considers an asm
-  // load's destination written when the statement ends and would hand the register to something else while the data is in flight
+  // pf_sink and the tile position (tin, tgsz) are left over from an L2 prefetch that is gone (profiles/r04_gemm_operand_stream.json):
+  // nothing reads them, but without them hipcc schedules the exit and scalar code of several instantiations differently -- kept so
+  // that the device code stays the measured one.
   unsigned pf_sink = 0;
   for (int bid = blockIdx.x; bid < nwg; bid += gridDim.x) {
     int gi, m0, n0, tin, tgsz, half = 0, gtile = 0;
@@ -561,10 +486,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       if (half) { nt1 -= kh; nt2 = 0; } else nt1 = kh;
     }
     const int nt = nt1 + nt2;
-    // 64-byte stage rows (32-deep stages of the wide tile): chunk g of row li sits at g ^ (-(li >> 2) & 3), fragments are 1 KiB apart
-    const int sw32 = (0 - (li >> 2)) & 3;
-    const int offA32 = (wr * WROWS + li) * 64 + ((g ^ sw32) << 4);
-    const int offB32 = BMT * 64 + (wc * WCOLS + li) * 64 + ((g ^ sw32) << 4);
 
     f32x4 acc[MI][NI];
 #pragma unroll
@@ -572,34 +493,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
 #pragma unroll
       for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // L2 prefetch.  The K loop is bound by the loaders' L2 -> LDS stream, and that stream by latency: the ring holds at most two K
-    // tiles in flight per CU and every K tile is a first touch for the XCD's L2 (an ablation with the compute waves idle still takes
-    // 92 % of the launch: profiles/r04_gemm_loader_waves.json).  One dword load per 128-byte line, QFX_GEMM_PF_DIST K tiles ahead,
-    // turns the loaders' misses into L2 hits.  The ~32 tiles an XCD runs at a time form an 8 (M) x 4 (N) patch sharing A panels four
-    // ways and B panels eight ways, so a tile touches a quarter of its A rows (wave 0) and an eighth of its B rows (wave 1): one
-    // wave-instruction per K tile each.  Only a hint: ragged patches leave some lines to the loaders' own misses.  The loads are
-    // uncounted (asm) and their results unused.
-    const bf16_t* pfp = nullptr;
-    if constexpr (QFX_GEMM_PF_DIST > 0 && !FP8) {
-      if (w == 0) {
-        constexpr int SH = BMT / 4;
-        int gm = m0 + ((tin / tgsz) & 3) * SH + (l0 < SH ? l0 : SH - 1); gm = gm < p.M ? gm : p.M - 1;
-        pfp = p.A1 + remap_row(gm, p.rows_per_batch, p.a_batch_rows, p.a_row_off) * p.lda1;
-      } else if (w == 1) {
-        constexpr int SH = TN / 8;
-        int gn = n0 + ((tin % tgsz) & 7) * SH + (l0 < SH ? l0 : SH - 1); gn = gn < p.N ? gn : p.N - 1;
-        pfp = p.B1 + (int64_t)gn * p.ldb1;
-      }
-    }
-    auto pf = [&](int kt) {
-      if constexpr (QFX_GEMM_PF_DIST > 0 && !FP8) {
-        if (w < 2 && kt < nt1) {
-          asm volatile("global_load_dword %0, %1, off" : "+v"(pf_sink) : "v"(pfp + kt * BKT) : "memory");
-        }
-      }
-    };
-#pragma unroll 1
-    for (int d = 2; d < QFX_GEMM_PF_DIST; ++d) pf(d);
 
     // narrow tiles -- rotated K loop: the second k-step of K tile t-1 is issued AFTER barrier t, under the first fragment reads
     // of tile t, so the matrix pipe does not drain while the post-barrier ds_reads are in flight (+2..6 % in the lab).
@@ -665,11 +558,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       const unsigned zero = 0u;
       asm volatile("global_store_dword %0, %1, off sc0 sc1" :: "v"(fl), "v"(zero) : "memory");
     };
-#if defined(QFX_GEMM_ABL_NO_COMPUTE)   // ablation (garbage results): the compute waves keep the barrier protocol only -- how long does the operand stream alone take?
-    const bool wave_dead = true;
-#else
     const bool wave_dead = m0 + wr * WROWS >= p.M;   // wave-uniform
-#endif
     // ---- dGELU epilogue, aux rows by LDS-DMA (round 6).  The epilogue reads one aux row segment per lane and pass (16 per wave and
     // 256 x 256 tile) -- first touches of a 60 MB tensor written a whole forward ago: HBM latency, 128 accumulators leave no registers to
     // request them ahead (profiles/r04_gemm_aux_prefetch.json), the launch ran 180 us against 165 for the GELU epilogue that writes twice
@@ -700,7 +589,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
                 !(p.bias != nullptr && (nt2 == 0 || p.seg2_plain)) &&                           // (no bias left for the epilogue)
                 (p.c_batch_rows == 0 || r0 / p.rows_per_batch == r1 / p.rows_per_batch);        // wave-uniform
       if (use_dma) row_delta = (int)(remap_row(r0, p.rows_per_batch, p.c_batch_rows, p.c_row_off) - r0);
-      if constexpr (EPI == QFX_EPI_GATE_RES) use_dma = use_dma && r0 / p.rows_per_batch == r1 / p.rows_per_batch;      // one gate vector
       if (use_dma) { aux_issue(0, 0, l0); aux_issue(0, 1, l0); }
     }
     if constexpr (FP8) {
@@ -793,7 +681,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const char* st = smem + buf * STAGE_BYTES;
-        pf(t + QFX_GEMM_PF_DIST);
         auto rdA = [&](int kk, int mi) { return *(const bf16x8*)(st + ((offA0 + mi * (16 * BK * 2)) ^ (kk << 6))); };
         auto rdB = [&](int kk, int ni) { return *(const bf16x8*)(st + ((offB0 + ni * (16 * BK * 2)) ^ (kk << 6))); };
         // a compute wave whose rows all lie past M (the text stream's last, partly empty tile) keeps
@@ -836,34 +723,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
           for (int ni = 0; ni < NI; ++ni)
             acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1[ni], a1[mi], acc[mi][ni], 0, 0, 0);
       }
-    } else if constexpr (BKT == 32) {
-      // wide tile, 32-deep stages: one k-step per stage; the NI B fragments stay resident, the MI A fragments pass through the
-      // three-deep register ring as below
-      for (int t = 0; t < nt; ++t) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const char* st = smem + buf * STAGE_BYTES;
-        pf(t + QFX_GEMM_PF_DIST);
-        if (wave_dead) { buf = buf + 1 == NSTAGE ? 0 : buf + 1; continue; }   // see the narrow-tile loop
-        const char* pA = st + offA32;
-        const char* pB = st + offB32;
-        bf16x8 b[NI];
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) b[ni] = *(const bf16x8*)(pB + ni * 1024);
-        bf16x8 fa0 = *(const bf16x8*)(pA), fa1 = *(const bf16x8*)(pA + 1024), fa2;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          if (mi + 2 < MI) fa2 = *(const bf16x8*)(pA + (mi + 2) * 1024);
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ni], fa0, acc[mi][ni], 0, 0, 0);
-          fa0 = fa1; fa1 = fa2;
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (mid_round && t == nt1 - 1) round_base();
-        buf = buf + 1 == NSTAGE ? 0 : buf + 1;
-      }
     } else {
       // SPLIT: the base segment and the LoRA segment run as two passes of this loop with the hand-off between them, so that its
       // temporaries are not live inside the K loop (inside it they cost 450 bytes of scratch per lane)
@@ -873,8 +732,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
           const char* st = smem + buf * STAGE_BYTES;
-          pf(t + QFX_GEMM_PF_DIST);
-          if (wave_dead) { buf ^= 1; continue; }   // see the narrow-tile loop
+            if (wave_dead) { buf ^= 1; continue; }   // see the narrow-tile loop
 #pragma unroll
           for (int kk = 0; kk < 2; ++kk) {
             const char* pA = st + (offA0 ^ (kk << 6));
@@ -900,9 +758,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       if constexpr (SPLIT) {
         kpass(0, nt1);
         if (half == 0) {
-#if !defined(QFX_SPLIT_ABL_NOFIX)                 // ablation (garbage results): no hand-off on the consumer side
           if (!wave_dead) fixup();                 // the whole base sum, before it is rounded
-#endif
           if (mid_round && !wave_dead) round_base();
           kpass(nt1, nt);
         }
@@ -912,9 +768,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
     }
     if constexpr (SPLIT) {
       if (half) {                    // producer item: the partial tile leaves through the L2, no epilogue
-#if !defined(QFX_SPLIT_ABL_NOPUB)                 // ablation: the producer keeps its partial tile to itself
         if (!wave_dead) publish();
-#endif
         continue;
       }
     }
@@ -988,21 +842,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       soff_[j] = srow_[j] * 128 + ((sch_[j] ^ (srow_[j] >> 1)) << 4);
       ncol_[j] = n0 + wc * WCOLS + sch_[j] * 8;
     }
-    [[maybe_unused]] u32x4 gvp[NGC];
-    if constexpr (AUXDMA) {
-      if (use_dma) {
-        // (no pending bias on this side: its NI x 4 registers are free during the passes); gate vector(s) of the lane's columns: ONE sample per wave here
-        if constexpr (EPI == QFX_EPI_GATE_RES) {
-          static_assert(NGRP == 1, "one column group per pass");
-          const int bidx = (m0 + wr * WROWS) / p.rows_per_batch;
-#pragma unroll
-          for (int jc = 0; jc < NGC; ++jc) {
-            gvp[jc] = *(const u32x4*)(p.gate + (int64_t)bidx * p.gate_bstride + ncol_[jc]);
-            asm volatile("" : "+v"(gvp[jc]));      // (arrived before the first counted wait: hipcc puts its own wait here)
-          }
-        }
-      }
-    }
     // The passes exist twice where the landing buffer is compiled in: DMA = true is straight-line code (every lane slot stores: whole
     // 16-row groups inside M, whole column range inside N, no row mask), so the request/store order the counted waits rely on is the
     // program order; DMA = false is the general form.  One wave-uniform branch picks -- a merge INSIDE a pass made hipcc carry the
@@ -1063,34 +902,13 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
             u32x4 o2;
 #pragma unroll
             for (int q = 0; q < 4; ++q) o2[q] = pack2bf(gelu_tanh_f(y[2 * q]), gelu_tanh_f(y[2 * q + 1]));
-            if constexpr ((QFX_GEMM_NT_SAVED & 1) != 0) __builtin_nontemporal_store(yv, (u32x4*)(p.C + crow * p.ldc + n));      // h is next read a whole forward later
-            else *(u32x4*)(p.C + crow * p.ldc + n) = yv;
+            *(u32x4*)(p.C + crow * p.ldc + n) = yv;
             if (!cq_only) *(u32x4*)(p.C2 + crow * p.ldc2 + n) = o2;
             if constexpr (FP8) { if (cq) quant_store(o2, crow, n, ch); }
           } else if constexpr (EPI == QFX_EPI_GATE_RES) {
             float gl[8];
             const int jc = NGC == 1 ? 0 : j;
             u32x4 rv;
-            if constexpr (DMA) {
-              // one sample per wave on this side: the gate vector of the lane's columns was fetched before the passes (packed: 4 registers)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) { gl[2 * q] = __uint_as_float(gvp[jc][q] << 16); gl[2 * q + 1] = __uint_as_float(gvp[jc][q] & 0xffff0000u); }
-              // counted wait as in the d(GELU) branch below; with the second output (p.C2) every lane slot stores twice
-              const int pass = mi * NGRP + gq;
-              if (p.C2 == nullptr) {
-                if (pass == 0 && j == 0) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-                else if (pass == 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-              } else {
-                if (pass == 0 && j == 0) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-                else if (pass == 0) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-              }
-              rv = *(const u32x4*)(auxb + j * 1024 + lnp * 16);
-              asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rv) :: "memory");
-              constexpr int npass = MI * NGRP;
-              aux_issue(pass + 1 < npass ? pass + 1 : npass - 1, j, lnp);
-            } else {
             const int bidx = m / p.rows_per_batch;
             if (!GATE_CACHE || bidx != last_b[jc]) {
               const u32x4 gv = *(const u32x4*)(p.gate + (int64_t)bidx * p.gate_bstride + n);
@@ -1108,7 +926,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
             // (aux rows are loaded where they are used: requesting them one to MI passes ahead was measured 1-2 % SLOWER on the whole
             // step -- the extra live registers spill, and other waves already cover the round trip: profiles/r04_gemm_aux_prefetch.json)
             rv = *(const u32x4*)(p.aux + (p.aux_unmapped ? (int64_t)m : crow) * p.ldaux + n);
-            }
             u32x4 o;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1116,10 +933,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
               o[q] = pack2bf(r0 + rbf(gl[2 * q] * y[2 * q]), r1 + rbf(gl[2 * q + 1] * y[2 * q + 1]));
             }
             *(u32x4*)(p.C + crow * p.ldc + n) = o;
-            if (p.C2) {      // pre-gate linear output (rows UNMAPPED), kept for d(gate)
-              if constexpr ((QFX_GEMM_NT_SAVED & 2) != 0) __builtin_nontemporal_store(yv, (u32x4*)(p.C2 + (int64_t)m * p.ldc2 + n));
-              else *(u32x4*)(p.C2 + (int64_t)m * p.ldc2 + n) = yv;
-            }
+            if (p.C2) *(u32x4*)(p.C2 + (int64_t)m * p.ldc2 + n) = yv;      // pre-gate linear output (rows UNMAPPED), kept for d(gate)
           } else {  // QFX_EPI_DGELU
             u32x4 hv;
             if constexpr (DMA) {
@@ -1198,17 +1012,13 @@ struct GeoTable { Geo g[NGEO]; bool split_on; int split_min_k, split_bias; };
 // its own SNAPSHOT of the table -- qfx_gemm_tune() from one thread can no longer tear the table under a launch from another
 // (side-stream / data-parallel hook threads launch GEMMs concurrently with the main thread).
 // The same-XCD split-K policy lives in the same table (it used to be three loose globals read without the lock):
-// QFX_GEMM_SPLITK = 0 / 1, QFX_GEMM_SPLITK_MINK = smallest base K taken, QFX_GEMM_SPLITK_BIAS = K tiles the consumer's half is shorter by.
-#if defined(QFX_GEMM_SPLITK_DEFAULT_ON)      // A/B builds (tools/build_variants.py)
-#define QFX_SPLIT_DEFAULT true
-#else
-#define QFX_SPLIT_DEFAULT false
-#endif
+// QFX_GEMM_SPLITK = 0 / 1 (default 0), QFX_GEMM_SPLITK_MINK = smallest base K taken, QFX_GEMM_SPLITK_BIAS = K tiles the consumer's
+// half is shorter by.
 GeoTable g_geo_tab = {{
     {256, 128, 1.0, 1.00, true},
     {256, 256, 2.0, 1.09, true},
     {160, 192, 0.9375, 0.965, true},      // round 4: 0.9375 of the work at ~0.965 of the per-flop speed (profiles/r04_gemm_tiles.json)
-}, QFX_SPLIT_DEFAULT, 9216, 3};
+}, false, 9216, 3};
 std::mutex g_geo_mu;
 std::once_flag g_geo_once;
 

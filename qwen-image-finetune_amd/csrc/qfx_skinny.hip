@@ -3,12 +3,6 @@
 #include "qfx_common.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-#ifndef QFX_GRAD_HANDOFF
-#define QFX_GRAD_HANDOFF 8      // 8 = chunk partials added by a second launch (product); 0 = by the last block of the strip, with fences: see lora_grad_kernel
-#endif
-#ifndef QFX_GRAD_NT_X
-#define QFX_GRAD_NT_X 0      // lora_grad: non-temporal loads of the token-side operand (A/B lever)
-#endif
 namespace {
 
 // ---------------------------------------------------------------------------------------------
@@ -340,10 +334,7 @@ __global__ __launch_bounds__(512) void ln_down_kernel(const LnDownBatch batch_by
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4v;
 constexpr int GX_ROWB = 288;  // padded LDS row stride (bytes) of the [32 tokens][128 cols] tile
 
-#ifndef QFX_GRAD_CH
-#define QFX_GRAD_CH 512
-#endif
-constexpr int GRAD_CH = QFX_GRAD_CH;   // tokens per block: 4x fewer device-scope fp32 atomics per output element than 128 (the atomics
+constexpr int GRAD_CH = 512;   // tokens per block: 4x fewer device-scope fp32 atomics per output element than 128 (the atomics
                                // of the M/CH partial sums, not the 15 MB stream, bounded the 128-token version)
 // G[j, k] += scale * D[j, k] for the 16 NF x 128 tile a block holds in MFMA layout (D[i = rank 4g+r][j = col li] per 16 x 16 fragment)
 template <int NF>
@@ -400,11 +391,7 @@ __global__ __launch_bounds__(256) void lora_grad_kernel(const GradBatch batch_by
         int m = mb + (quad * 4 + j) * 32 + it * 16 + srow;
         m = m < p.M ? m : p.M - 1;
         const bf16_t* src = p.X + remap_row(m, p.rows_per_batch, p.x_batch_rows, p.x_row_off) * p.ldx + kc;
-#if QFX_GRAD_NT_X
-        dst[j][it] = __builtin_nontemporal_load((const u32x4*)src);      // every X element is read once per launch: keep it out of the GEMMs' L2
-#else
-        dst[j][it] = *(const u32x4*)src;
-#endif
+        dst[j][it] = *(const u32x4*)src;      // (non-temporal loads measured nothing: profiles/r06_grad_nt_x.json)
       }
   };
   f32x4 acc[NF][2];
@@ -464,12 +451,8 @@ __global__ __launch_bounds__(256) void lora_grad_kernel(const GradBatch batch_by
   const int nchunk = (p.M + CH - 1) / CH;
   if (p.ws != nullptr && nchunk > 1) {
     // ---- deterministic form (ABI 7): partial tile -> per-problem scratch, added in CHUNK ORDER (the sum does not depend on who
-    // finished when).  QFX_GRAD_HANDOFF = 8 (product): by a second launch, lora_grad_reduce_kernel -- the kernel boundary is the
-    // hand-off, this block is done.  = 0 (round 6, first version): by the LAST block of the 128-column strip in this launch (plain slab
-    // stores, every wave drains them, ONE agent-scope release by lane 0, relaxed ticket, the last arriver acquires once and reads plain
-    // -- cdna_hip_programming.md section 5): correct, but every block's release is a buffer_wbl2 of the XCD's WHOLE L2 next to the main
-    // stream's GEMMs: +1.4 ms per step (profiles/r06_grad_handoff.json; fence-free forms with sc0 sc1 stores, also with a read-back
-    // before the ticket, hand over stale slabs under the 60-block step: the same file).
+    // finished when) by a second launch, lora_grad_reduce_kernel -- the kernel boundary is the hand-off, this block is done.  A
+    // last-arriver reduction inside this launch needs a release fence per block, which cost 1.4 ms per step (profiles/r06_grad_handoff.json).
     const int chunk = (int)blockIdx.y - kb.start[pi];
     const int nstrip = (p.K + 127) / 128;      // the scratch is sized per problem (qfx_lora_grad_ws_floats), not per launch grid
     float* slab = p.ws + ((int64_t)chunk * nstrip + blockIdx.x) * (NF * 2048) + tid * 4;
@@ -477,39 +460,12 @@ __global__ __launch_bounds__(256) void lora_grad_kernel(const GradBatch batch_by
     for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
       for (int cf = 0; cf < 2; ++cf) *(f32x4*)(slab + (nf * 2 + cf) * 1024) = acc[nf][cf];
-    if constexpr ((QFX_GRAD_HANDOFF & 8) != 0) return;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = (int*)&sX[0][0];
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ROCm 7.2 may drop the wait behind buffer_wbl2: restated where it cannot)
-      const int t = __hip_atomic_fetch_add(p.ws_count + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = t == nchunk - 1;
-      if (last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __hip_atomic_store(p.ws_count + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // zero again for the next launch
-      }
-      *flag = last;
-    }
-    __syncthreads();
-    if (*flag == 0) return;
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-      for (int cf = 0; cf < 2; ++cf) acc[nf][cf] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < nchunk; ++c) {
-      const float* src = p.ws + ((int64_t)c * nstrip + blockIdx.x) * (NF * 2048) + tid * 4;
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-        for (int cf = 0; cf < 2; ++cf) acc[nf][cf] += *(const f32x4*)(src + (nf * 2 + cf) * 1024);
-    }
+    return;
   }
   grad_update<NF>(p, acc, k0, w, g, li, p.ws != nullptr);      // (scratch given: one writer per element and launch, no atomic needed -- a single chunk included)
 }
 
-// Second launch of the deterministic form (QFX_GRAD_HANDOFF = 8): block (strip, problem) adds the token-chunk partials of the first
+// Second launch of the deterministic form: block (strip, problem) adds the token-chunk partials of the first
 // launch in chunk order and updates G.  Same thread -> element map as lora_grad_kernel; the kernel boundary is the hand-off.
 template <int NF>
 __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const GradBatch batch_by_value) {
@@ -817,7 +773,6 @@ extern "C" int qfx_lora_grad_batch(const qfx_lora_grad_args* list, int32_t n, vo
     default: return QFX_EUNSUPPORTED;
   }
   QFX_CHECK_LAUNCH();
-#if (QFX_GRAD_HANDOFF & 8) != 0
   bool any = false;
   for (int i = 0; i < n; ++i) any = any || (list[i].ws && list[i].M > GRAD_CH);
   if (any) {
@@ -831,7 +786,6 @@ extern "C" int qfx_lora_grad_batch(const qfx_lora_grad_args* list, int32_t n, vo
     }
     QFX_CHECK_LAUNCH();
   }
-#endif
   return QFX_OK;
 }
 

@@ -15,7 +15,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -658,7 +657,7 @@ class _FluxPlan(_QwenPlan):
         # the block's weight-gradient problems (up to 8) go out as batched launches right before the LayerNorm backward overwrites
         # dyg_j -- their operands (dyg_j, dqkv, A2, v^T scratch, the block's kept buffers) stay intact until then; one launch each
         # they were 8 x 38 latency-bound launches on the main stream (the FLUX programs keep their gradients there)
-        gl = [] if os.environ.get("QFX_FLUX_SINGLE_BATCH", "1") != "0" else None     # None: one launch per problem (A/B switch)
+        gl = []
         if wo.lora is not None:
             kwo = self._site_bwd(p, wo, bb["site_out"], A["dyg_j"], D, M, bb["cat"], 5 * D, defer=gl)
             kwa = dict(kwo, B2=wo.lora.WeT[:D])
@@ -677,7 +676,7 @@ class _FluxPlan(_QwenPlan):
             Rp, Kext = grp["Rp"], grp["Kext"]
             Vth, Vtl = A["Vt_j"]
             Uth, Utl = bb["Uqkv"]
-            dl = [] if gl is not None else None     # the q / k / v down projections of dqkv: one launch
+            dl = []     # the q / k / v down projections of dqkv: one launch
             for sec in range(3):
                 lo = w["qkv"][sec].lora
                 if lo is None:

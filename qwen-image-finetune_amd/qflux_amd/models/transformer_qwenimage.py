@@ -135,10 +135,6 @@ class _Prog:
         """C call issued on the program's side stream (leaf work that overlaps the main stream; joined by explicit events)."""
         self.calls.append((fn, args, True))
 
-    def c_on(self, stream, fn, *args):
-        """C call issued on `stream` (a torch.cuda.Stream kept alive by the caller; forked / joined by explicit events)."""
-        self.calls.append((fn, args, stream))
-
     def py(self, fn):
         self.calls.append((None, fn))
 
@@ -154,7 +150,7 @@ class _Prog:
             if fn is None:
                 args()
             else:
-                rc = fn(*args, st if len(ent) < 3 else (self.side if ent[2] is True else ent[2]).cuda_stream)
+                rc = fn(*args, st if len(ent) < 3 else self.side.cuda_stream)
                 if rc != 0:
                     raise L.QfxError(f"{fn.__name__} failed with code {rc}")
 
@@ -679,9 +675,6 @@ class _QwenPlan:
 
     side_grads = False        # see _init_side_grads (plans that do not call it keep every launch on the main stream)
     _side_q = ()
-    _side_late = False
-    _pending_side = None
-    _ncopy = 2                # copies of the side launches' scratch operands (see _init_side_grads)
 
     def __init__(self, model, B: int, S_i: int, T: int, shapes, multires: bool = False):
         self._setup(model, B, S_i, T)
@@ -755,31 +748,21 @@ class _QwenPlan:
         self.side_grads = bool(allowed and self.has_lora and os.environ.get("QFX_SIDE_GRADS", "1") != "0"
                                and (not ff or os.environ.get("QFX_SIDE_GRADS_FF", "1") != "0"))
         self._side_q = []              # (event, prefix) of the blocks whose gradient launches are in flight on the side stream
-        # QFX_SIDE_COPIES=3 (round-6 lever): three copies of the side launches' scratch operands instead of two, so that the join with the
-        # launch of block i+2 can sit right in front of the fork of block i (two adjacent barrier packets instead of two separate bubbles)
-        self._ncopy = 3 if (self.side_grads and os.environ.get("QFX_SIDE_COPIES", "2") == "3") else 2
-        # QFX_SIDE_AT_ATTN=1 (round-6 lever): the gradient launches of block i go out in front of block i-1's ATTENTION backward (whose
-        # launches leave CUs idle in their last round) instead of in front of its feed-forward GEMMs (which they slow down by 18 us)
-        self._side_late = bool(self.side_grads and self._ncopy == 2 and os.environ.get("QFX_SIDE_AT_ATTN", "0") == "1")
-        self._pending_side = None
         if self.side_grads:
             dev = self.model.device
-            from .. import ops
-            # QFX_SIDE_CUS=16 confines the side stream to two CUs per XCD (qfx_stream_create_cu_masked).  Measured: the mask works
-            # (tools/cu_mask_probe.py) but the whole step slows from 99.7 to 127.9 ms with such a queue alive -> default: no mask
-            self.bwd.side = ops.side_stream(dev, int(os.environ.get("QFX_SIDE_CUS", "0")))
-            self._ev_fork = ops.Event()
+            # an ordinary low-priority stream: a CU-masked queue slowed the whole step (profiles/HISTORY.md, profiles/r01_cu_mask_probe.json)
+            self.bwd.side = ops.side_stream(dev)
+            self._ev_fork = torch.cuda.Event()
             # the scratch operands of those launches (dyg1, dqkv, v^T) alternate between two copies by block parity, so a launch
             # has a whole block of main-stream work to hide under (on the 16 idle CUs it runs ~5x longer than alone)
             A = self.A
             for name in ("dyg1", "dqkv", "Vt", "VtO") + (("dh", "VtF1", "VtF2") if ff else ()):
                 src = A[name]
-                for c in range(1, self._ncopy):
-                    if isinstance(src, dict):
-                        A[name + f"#{c}"] = {s: (tuple(torch.zeros_like(t) for t in v) if isinstance(v, tuple) else torch.zeros_like(v))
-                                             for s, v in src.items()}
-                    else:
-                        A[name + f"#{c}"] = torch.zeros_like(src)
+                if isinstance(src, dict):
+                    A[name + "#1"] = {s: (tuple(torch.zeros_like(t) for t in v) if isinstance(v, tuple) else torch.zeros_like(v))
+                                      for s, v in src.items()}
+                else:
+                    A[name + "#1"] = torch.zeros_like(src)
 
     def _fuse_qk_bwd(self, a, sqk, norms, norm_flags, eps):
         """Backward of the QK RMSNorm + RoPE in the epilogues of qfx_attn_bwd_dq / _dkv (one pass over dqkv and a launch less per
@@ -1226,9 +1209,7 @@ class _QwenPlan:
         by_r = {}
         for a in pending:
             by_r.setdefault(a.R, []).append(a)
-        order = sorted(by_r, reverse=True) if (side and os.environ.get("QFX_SIDE_ORDER", "0") == "wide_first") else list(by_r)
-        for r_ in order:      # (QFX_SIDE_ORDER=wide_first, round-6 lever: the widest rank class of the side-stream launches first)
-            lst = by_r[r_]
+        for lst in by_r.values():
             for i in range(0, len(lst), L.MAX_BATCH):
                 chunk = lst[i:i + L.MAX_BATCH]
                 arr = (struct * len(chunk))(*chunk)
@@ -1343,39 +1324,7 @@ class _QwenPlan:
         else:
             p.c(lib.qfx_mod_gemv, _ptr(A["tproj"]), B, 256, _ptr(P["t1_Wp"]), _ptr(P["t1_bp"]), 1, D, 0, _ptr(A["t1"]))
             p.c(lib.qfx_mod_gemv, _ptr(A["t1"]), B, D, _ptr(P["t2_Wp"]), _ptr(P["t2_bp"]), 1, D, 1, _ptr(A["temb"]))
-            # Round 6 lever (QFX_SIDE_MOD=1, default OFF): the modulation GEMVs of all blocks are ONE pass over 13.6 GB of frozen weights at
-            # HBM speed (2.2 ms of a 93 ms step with the matrix pipes idle).  With the lever only block 0's two matrices stay on the main
-            # stream, the rest go out on the side stream in three launches under the first blocks' GEMMs, each joined in front of the first
-            # block that reads its rows.  Measured (profiles/r06_step_side_mod.json): 95.35 vs 95.31 ms -- nothing.  The persistent GEMM
-            # blocks (12 waves x ~160 registers) leave no register file for a second kernel's waves on their CUs, so the side launches only
-            # run in the seams between GEMM launches: the same wall the side-stream gradient launches hit.
-            mod_joins = {}
-            if Lyr > 4 and os.environ.get("QFX_SIDE_MOD", "0") == "1":
-                side = ops.side_stream(model.device, 0)
-                p.side = side
-
-                def gemv(i0, i1, on_side):
-                    (p.c_side if on_side else p.c)(lib.qfx_mod_gemv, _ptr(A["temb"]), B, D, _ptr(P["mod_W"]) + 8 * i0, _ptr(P["mod_b"]) + 8 * i0,
-                                                   i1 - i0, 6 * D, 1, A["mods"][i0].data_ptr())
-                gemv(0, 2, False)
-                ev_fork = ops.Event()
-                p.keep.append(ev_fork)
-
-                def fork(ev=ev_fork, side=side):
-                    ev.record(torch.cuda.current_stream())
-                    ev.wait(side)
-                p.py(fork)
-                for b0, b1 in ((1, 3), (3, 9), (9, Lyr)):
-                    if b0 >= Lyr:
-                        break
-                    b1 = min(b1, Lyr)
-                    gemv(2 * b0, 2 * b1, True)
-                    ev = ops.Event()
-                    p.keep.append(ev)
-                    p.py(lambda ev=ev, side=side: ev.record(side))
-                    mod_joins[b0] = ev
-            else:
-                p.c(lib.qfx_mod_gemv, _ptr(A["temb"]), B, D, _ptr(P["mod_W"]), _ptr(P["mod_b"]), 2 * Lyr, 6 * D, 1, _ptr(A["mods"]))
+            p.c(lib.qfx_mod_gemv, _ptr(A["temb"]), B, D, _ptr(P["mod_W"]), _ptr(P["mod_b"]), 2 * Lyr, 6 * D, 1, _ptr(A["mods"]))
             p.c(lib.qfx_mod_gemv, _ptr(A["temb"]), B, D, _ptr(P["norm_out_Wp"]), _ptr(P["norm_out_bp"]), 1, 2 * D, 1, _ptr(A["mod_out"]))
         kw = self._site_fwd(p, P["img_in"], A["site"]["img_in"], A["in_img"], cfg.in_channels, rows["img"])
         self._gemm(p, A1=A["in_img"], lda1=cfg.in_channels, B1=P["img_in"].W, K1=cfg.in_channels, M=rows["img"], N=D,
@@ -1386,11 +1335,9 @@ class _QwenPlan:
                    bias=P["txt_in"].b, row_mask=self.rm_txt0, **kw)
         self.attn_args = []
         for i in range(Lyr):
-            if not self.cond and i in mod_joins:      # this block's modulation rows come from the side stream
-                p.py(lambda ev=mod_joins[i]: ev.wait(torch.cuda.current_stream()))
             mods = {"img": A["mods"][2 * i], "txt": A["mods"][2 * i + 1]}   # [B, 6D]: shift1 scale1 gate1 shift2 scale2 gate2
             self._emit_double_fwd(p, P["blocks"][i], A["blk"][i], mods, {s: A["X"][s][i] for s in ("img", "txt")},
-                                  {s: (A["X"][s][i + 1], (0, 0)) for s in ("img", "txt")}, last=(i == Lyr - 1), norm_flags=0, par=i % self._ncopy)
+                                  {s: (A["X"][s][i + 1], (0, 0)) for s in ("img", "txt")}, last=(i == Lyr - 1), norm_flags=0, par=i % 2)
         mo = A["mod_out"][0]  # [B, 2D]: scale | shift  (AdaLayerNormContinuous chunk order)
         p.c(lib.qfx_ln_modulate_fwd, _ptr(A["X"]["img"][Lyr]), _ptr(mo[:, D:2 * D]), _ptr(mo[:, 0:D]), 2 * D, _ptr(A["xn_out"]),
             rows["img"], D, rpb["img"], eps)
@@ -1579,12 +1526,11 @@ class _QwenPlan:
             self._emit_double_bwd(p, P["blocks"][i], A["blk"][i], self.attn_args[i], mods, {s: A["X"][s][i] for s in ("img", "txt")},
                                   dx2={s: A["dX"][s][cur] for s in ("img", "txt")}, out_dx={s: A["dX"][s][nxt] for s in ("img", "txt")},
                                   gate_prev=gate_prev, last=(i == Lyr - 1), first=(i == 0 and not self.full_bwd), norm_flags=0,
-                                  prefix=f"transformer_blocks.{i}.", par=i % self._ncopy,
+                                  prefix=f"transformer_blocks.{i}.", par=i % 2,
                                   dmods=({"img": A["dmods"][2 * i], "txt": A["dmods"][2 * i + 1]} if self.cond else None))
             if not self.side_grads:
                 p.mark(f"transformer_blocks.{i}.")
             cur = nxt
-        self._emit_pending_side(p)
         self._side_join(p)
         # head: the embedders' adapters (their inputs carry no gradient: rank-r launches only); d(block-0 input) = A["dX"][s][cur]
         if self.in_grad:
@@ -1605,8 +1551,8 @@ class _QwenPlan:
         ff_side = self.side_grads and self._ff_side
         dh_ = self._sb("dh", par) if ff_side else A["dh"]
         vtf = {"VtF1": self._sb("VtF1", par) if ff_side else A.get("VtF1"), "VtF2": self._sb("VtF2", par) if ff_side else A.get("VtF2")}
-        if ff_side and self._ncopy == 2:
-            self._side_join(p, keep=0 if self._side_late else 1)      # the launch of block i+2 read this parity's dh: overwritten by this block's first GEMM
+        if ff_side:
+            self._side_join(p, keep=1)      # the launch of block i+2 read this parity's dh: overwritten by this block's first GEMM
         dq2 = dqkv.view(B * S, 3 * D)
         STREAMS = (("img", 0), ("txt", 1))
         i = 0 if first else 1
@@ -1656,7 +1602,7 @@ class _QwenPlan:
             if ge:
                 self._flush_batch(p, ge, L.LoraGradArgs, lib.qfx_lora_grad_batch)
             if dmods is not None:   # d(shift2, scale2, gate2): dy = d(xm2) (fc1 dX output), LN input x1, gate side dx2 * y2
-                mg = [] if os.environ.get("QFX_MOD_GRAD_BATCH", "1") != "0" else None     # None: one launch per stream (A/B switch)
+                mg = []
                 for s, _ in live:
                     dm = dmods[s]
                     self._mod_grad(p, dy=A["dxm"][s], x=bb["x1"][s], rows=rows[s], rpb=rpb[s], dshift=dm[:, 3 * D:4 * D],
@@ -1664,8 +1610,7 @@ class _QwenPlan:
                                    row_mask=self.rmask[s], defer=mg)
                 if mg:
                     self._flush_mod_grad(p, mg)
-            if self._ncopy == 2:
-                self._side_join(p, keep=0 if self._side_late else 1)   # the launch of block i+2 read this parity's dyg1 / dqkv / v^T scratch: overwritten from here on
+            self._side_join(p, keep=1)   # the launch of block i+2 read this parity's dyg1 / dqkv / v^T scratch: overwritten from here on
             groups = []
             lnl = [self._ln_bwd_args(A["dxm"][s], bb["x1"][s], mods[s][:, 4 * D:5 * D], 6 * D, dx2[s], mods[s][:, 2 * D:3 * D], 6 * D,
                                      A["dx1"][s], dyg1[s], rows[s], D, rpb[s], eps, None) for s, sidx in live]
@@ -1696,7 +1641,6 @@ class _QwenPlan:
             self._gemm_group(p, groups)
             # ---- attention backward
             q2 = bb["qkv"].view(B * S, 3 * D)
-            self._emit_pending_side(p)          # (QFX_SIDE_AT_ATTN: the previous block's gradient launches start here)
             ops.emit_attn_backward(p, a, A)      # two-pass pair, or the one-pass kernel (QFX_ATTN_BWD)
             if not a.qk_saved:      # (else: the backward of the QK norm + RoPE runs in the epilogues of the two kernels above)
                 nq_t, nk_t, nq_i, nk_i = w["norms"]
@@ -1753,14 +1697,10 @@ class _QwenPlan:
                                               rpb=rpb[s], a_map=(S, off[s]), **kw))
             self._flush_batch(p, dl, L.LoraDownArgs, lib.qfx_lora_down_batch)
             self._flush_head_reduce(p, dhq)
-            if self.side_grads and gl and not self._side_late and os.environ.get("QFX_SIDE_FORK", "late") == "early":
-                # round-6 lever: every operand of the block's gradient launches exists from here on -- fork in front of the q/k/v dX GEMM
-                # instead of behind the block's last LayerNorm backward
-                self._emit_side(p, gl, prefix)
             if i > 0:
                 self._gemm_group(p, groups)
                 if dmods is not None:   # d(shift1, scale1, gate1): dy = d(xm1) (q/k/v dX output), LN input x_in, gate side dx1 * y1
-                    mg = [] if os.environ.get("QFX_MOD_GRAD_BATCH", "1") != "0" else None
+                    mg = []
                     for s, sidx in STREAMS:
                         dm = dmods[s]
                         dead = last and s == "txt"     # no out-projection / residual gradient on the last block's text tail
@@ -1781,29 +1721,17 @@ class _QwenPlan:
                         lnl[-1].dygq, lnl[-1].dygs, lnl[-1].lddygq, lnl[-1].dygs_rows = _ptr(pq_[0]), _ptr(pq_[1]), D, rows[s]
                 self._flush_ln(p, lnl, L.LnBwdArgs, lib.qfx_ln_modulate_bwd_batch)
         if self.side_grads and gl:
-            if self._side_late:
-                self._emit_pending_side(p)      # (a block without an attention section: nothing may be dropped)
-                self._pending_side = (gl, prefix)
-            else:
-                self._emit_side(p, gl, prefix)
+            self._emit_side(p, gl, prefix)
         else:
             self._flush_batch(p, gl, L.LoraGradArgs, lib.qfx_lora_grad_batch)
 
     def _emit_side(self, p, gl, prefix):
         """Fork, the block's batched gradient launches on the side stream, the event its join will wait for."""
-        if self._ncopy == 3:
-            self._side_join(p, keep=1)   # block i-1 overwrites the copy the launch of block i+2 read
         p.py(self._side_fork)
         self._flush_batch(p, gl, L.LoraGradArgs, lib.qfx_lora_grad_batch, side=True)
-        ev = ops.Event()
+        ev = torch.cuda.Event()
         p.py(lambda ev=ev: ev.record(self.bwd.side))
         self._side_q.append((ev, prefix))
-
-    def _emit_pending_side(self, p):
-        if self._pending_side is not None:
-            gl, prefix = self._pending_side
-            self._pending_side = None
-            self._emit_side(p, gl, prefix)
 
     def set_multires(self, img_shapes, txt_seq_lens, attention_mask, S_in=None):
         """Per-batch tables of the multi-resolution path (host-side plumbing of transformer_qwen_custom.py:72-150,175-228,

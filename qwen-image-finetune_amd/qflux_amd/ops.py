@@ -4,7 +4,6 @@ These are what the per-kernel parity tests call; the model builds cached argumen
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 
@@ -249,33 +248,6 @@ def emit_attn_backward(p, a, A):
             a.dq_acc, a.dq_turn = ws[0].data_ptr(), ws[1].data_ptr()
             p.c(lib.qfx_attn_bwd_fused, C.byref(a))
             return "1pass"
-    if os.environ.get("QFX_ATTN_BWD_CONC", "0") == "1":
-        # Round 6 lever (default OFF): the two kernels are independent once dsum = rowsum(dO * O) exists (the dQ kernel normally publishes
-        # it for dK / dV), and neither fills whole rounds of the 256 CUs at S = 2432 (456 blocks of 2 rounds, 912 of 4): dsum by the
-        # standalone pass, dQ on a second stream with its own copy of the statistics buffer, dK / dV on the main stream, join.
-        import ctypes
-        st2 = side_stream(torch.device("cuda", torch.cuda.current_device()), 0, slot=1)
-        a2 = type(a)()
-        ctypes.memmove(ctypes.byref(a2), ctypes.byref(a), ctypes.sizeof(a))
-        if "dsum_conc" not in A:
-            A["dsum_conc"] = torch.empty(a.B * a.H * a.S_pad + 1024, dtype=torch.float32, device=st2.device)
-        a2.dsum = A["dsum_conc"].data_ptr()
-        ev_f, ev_j = Event(), Event()
-        p.keep += [a2, ev_f, ev_j, st2]
-        p.c(lib.qfx_attn_bwd_prep, C.byref(a))
-
-        def fork(ev=ev_f, s=st2):
-            ev.record(torch.cuda.current_stream())
-            ev.wait(s)
-
-        def join(ev=ev_j, s=st2):
-            ev.record(s)
-            ev.wait(torch.cuda.current_stream())
-        p.py(fork)
-        p.c_on(st2, lib.qfx_attn_bwd_dq, C.byref(a2))
-        p.c(lib.qfx_attn_bwd_dkv, C.byref(a))
-        p.py(join)
-        return "2pass-concurrent"
     p.c(lib.qfx_attn_bwd_dq, C.byref(a))
     p.c(lib.qfx_attn_bwd_dkv, C.byref(a))
     return "2pass"
@@ -337,74 +309,14 @@ def sumsq_det(g, out, partials):
     L.check(lib.qfx_sumsq_det(_p(g), g.numel(), _p(out), _p(partials), partials.numel(), stream_ptr()), "qfx_sumsq_det")
 
 
-_hip = None
-
-
-class Event:
-    """Stream-ordering event for the launch programs' fork / join points.  Default: a torch.cuda.Event.  QFX_EVENT_NOFENCE=1 (round-6
-    lever): a raw HIP event created with hipEventDisableTiming | hipEventDisableSystemFence -- the record then carries no system-scope
-    release (no L2 write-back for the host's sake) in the middle of the main stream; device-side ordering between streams is all these
-    events are used for."""
-
-    def __init__(self):
-        global _hip
-        self.raw = None
-        if os.environ.get("QFX_EVENT_NOFENCE", "0") == "1":
-            if _hip is None:
-                _hip = C.CDLL("libamdhip64.so")
-                _hip.hipEventCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-                _hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-                _hip.hipStreamWaitEvent.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
-                _hip.hipEventDestroy.argtypes = [C.c_void_p]
-            h = C.c_void_p()
-            rc = _hip.hipEventCreateWithFlags(C.byref(h), 0x2 | 0x20000000)
-            if rc != 0 or not h.value:
-                raise L.QfxError(f"hipEventCreateWithFlags failed with code {rc}")
-            self.raw = h
-        else:
-            self.ev = torch.cuda.Event()
-
-    def record(self, stream):
-        if self.raw is None:
-            self.ev.record(stream)
-        else:
-            rc = _hip.hipEventRecord(self.raw, C.c_void_p(stream.cuda_stream))
-            if rc != 0:
-                raise L.QfxError(f"hipEventRecord failed with code {rc}")
-
-    def wait(self, stream):
-        """Make `stream` wait for this event."""
-        if self.raw is None:
-            stream.wait_event(self.ev)
-        else:
-            rc = _hip.hipStreamWaitEvent(C.c_void_p(stream.cuda_stream), self.raw, 0)
-            if rc != 0:
-                raise L.QfxError(f"hipStreamWaitEvent failed with code {rc}")
-
-    def __del__(self):
-        if getattr(self, "raw", None) is not None and _hip is not None:
-            _hip.hipEventDestroy(self.raw)
-            self.raw = None
-
-
 _side_streams = {}
 
 
-def side_stream(device, n_cus=16, slot=0):
-    """Process-wide CU-masked side stream of `device` (qfx_stream_create_cu_masked) as a torch stream object; n_cus = 0 or a driver
-    that refuses the mask -> an ordinary lowest-priority stream.  slot > 0: further streams, at the main stream's priority (peer work)."""
-    key = (torch.device(device).index or 0, int(n_cus), int(slot))
+def side_stream(device):
+    """Process-wide side stream of `device` at the lowest priority, as a torch stream object."""
+    key = torch.device(device).index or 0
     if key not in _side_streams:
-        st = None
-        if n_cus > 0:
-            out = C.c_void_p()
-            with torch.cuda.device(key[0]):
-                rc = lib.qfx_stream_create_cu_masked(int(n_cus), C.byref(out))
-            if rc == 0 and out.value:
-                st = torch.cuda.ExternalStream(out.value, device=torch.device("cuda", key[0]))
-        if st is None:
-            st = torch.cuda.Stream(device=torch.device("cuda", key[0]), priority=1 if slot == 0 else 0)
-        _side_streams[key] = st
+        _side_streams[key] = torch.cuda.Stream(device=torch.device("cuda", key), priority=1)
     return _side_streams[key]
 
 

@@ -269,8 +269,8 @@ def test_cfg4_properties_at_1024sq_two_blocks():
 
 def test_cfg4_step_is_bit_reproducible():
     """Every arena tensor of two identical fused steps at the cfg #4 shape (two blocks, S = 8576: four-wave attention blocks, every
-    fused epilogue) comes out bit-identical when both start from a zeroed arena.  Only the flat LoRA gradient is exempt from the
-    bit test: the weight-gradient launches (and the scalar loss) add with fp32 atomics (order-dependent in the last bit): compared to 1e-5 / 1e-6.
+    fused epilogue) comes out bit-identical when both start from a zeroed arena, the flat LoRA gradient included (lora_grad adds its
+    token chunks in a fixed order); only the scalar loss (one fp32 atomic per block of the criterion) is compared to 1e-6.
     Round 4: a codegen change made ~0.1 % of the 16-row fragments of the fused QK-norm backward irreproducible (tools/find_nondet.py
     locates the launch); nothing else in the suite looks at run-to-run equality."""
     from qflux_amd.modules import LoraConfig

@@ -70,6 +70,6 @@ def test_gemm_landing_buffer_epilogue_has_only_counted_vector_memory_operations(
         # (the last slot's store may sit in another basic block -- hipcc lays the loop's exit path out elsewhere)
         assert side[:len(want) - 1] == want[:-1], (key, " ".join(side[:len(want) + 6]))
         assert side[len(want):len(want) + 1] != ["S"], (key, "a store beyond the last lane slot")
-    # the gate + residual epilogue has the buffer only in A/B builds (QFX_GEMM_AUX_DMA bit 1, measured slower)
+    # the gate + residual epilogue has no landing buffer (measured slower: profiles/r06_gemm_aux_landing.json)
     for key in ("gate_res 256x256", "gate_res 160x192"):
         assert g.landing_side(g.seq(text, g.KERNELS[key])) == [], key

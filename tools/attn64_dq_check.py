@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""qfx_attn_bwd_dq: the 64-query kernel (QFX_ATTN_DQ64=1) against the 32-query kernel (=0) on one box -- outputs compared (dQ, dsum, fused
+"""qfx_attn_bwd_dq: the 64-query kernel (ops.attn_tune("dq64=1")) against the 32-query kernel (dq64=0) on one box -- outputs compared (dQ, dsum, fused
 rank-r partial sums; plain and with the fused QK-norm / RoPE backward), both against an fp32 autograd reference of SDPA in the plain mode,
 kernels timed interleaved.   python tools/attn64_dq_check.py [--S 2432,8576,333:2:2,...]"""
 import argparse, ctypes as C, json, math, os, sys, torch
@@ -33,7 +33,7 @@ for spec in args.S.split(","):
     st = torch.cuda.current_stream().cuda_stream
     for fused in (0, 1):
         for mode in ("0", "1"):
-            os.environ["QFX_ATTN_DQ64"] = mode
+            ops.attn_tune("dq64=" + mode)
             O = torch.zeros(Bn, S, D, dtype=BF, device=DEV); lse2 = torch.zeros(Bn, H, S_pad, device=DEV); dsum = torch.zeros(Bn, H, S_pad, device=DEV)
             dqkv = torch.zeros_like(qkv); part = torch.zeros(H, Bn * S, max(R, 1), device=DEV)
             a = ops.attn_args(Bn, S, S_pad, H, dh, 1 / math.sqrt(dh), Q=qkv[:, :, :D], K=qkv[:, :, D:2 * D], V=qkv[:, :, 2 * D:], ldq=ld, ldk=ld, ldv=ld,

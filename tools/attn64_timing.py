@@ -8,7 +8,8 @@ from qflux_amd import _lib as L
 var = C.CDLL(os.path.join(ROOT, "tools", "_ab", os.environ.get("A64T_LIB", "libqfx_a64t.so")))
 var.qfx_attn_fwd.argtypes = [C.POINTER(L.AttnArgs), C.c_void_p]; var.qfx_attn_fwd.restype = C.c_int
 var.qfx_attn_bwd_dq.argtypes = [C.POINTER(L.AttnArgs), C.c_void_p]; var.qfx_attn_bwd_dq.restype = C.c_int
-os.environ["QFX_ATTN_FWD64"] = "1"; os.environ["QFX_ATTN_DQ64"] = "1"
+var.qfx_attn_tune.argtypes = [C.c_char_p]; var.qfx_attn_tune.restype = C.c_int
+assert var.qfx_attn_tune(b"fwd64=1,dq64=1") == 0      # the variant library's own policy (it is not the one ops.attn_tune sets)
 BF = torch.bfloat16; DEV = "cuda:0"
 for S in (2432, 8576):
     Bn, H, dh = 1, 24, 128; D = H * dh; S_pad = (S + 63) // 64 * 64

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """A/B of PLAN-BUILD-TIME environment levers on the real training step (60 blocks, side-stream gradient launches, optimizer):
-    python tools/step_plan_ab.py base,QFX_ATTN_BWD_CONC=1[,KEY=VAL+KEY=VAL...] [--steps 20] [--rounds 3] [--out f.json]
+    python tools/step_plan_ab.py base,QFX_GRAD_DET=0[,KEY=VAL+KEY=VAL...] [--steps 20] [--rounds 3] [--out f.json]
 tools/step_ablate.py switches levers the LIBRARY reads per launch; levers read while the launch programs are emitted (python side) need
 their own plan.  One model; per variant the plan cache is cleared and rebuilt under the variant's environment, then the timing rounds
 swap the cached plans in and out (whole steps back to back, rounds alternate: the step is package-power-limited)."""
