@@ -493,6 +493,53 @@ typedef struct qfx_prodigy_args {
 int qfx_prodigy_init_state(double* state, double d0, void* stream);   /* d = d_max = d_hat = d0, everything else 0; synchronises */
 int qfx_prodigy_step(const qfx_prodigy_args* a, void* stream);
 
+/* ---- blockwise 8-bit Adam / AdamW with bitsandbytes' state layout (third party bitsandbytes.optim.Adam8bit / AdamW8bit and their
+ * Paged forms, selected by most of the reference's optimizer blocks, e.g. configs/face_seg_config.yaml:55-59; instantiated at
+ * base_trainer.py:884-898, stepped at :531 after clip_gradients :449-455, resumed from optimizer.bin at :327-329).  ONE launch per
+ * step over the flat LoRA buffers, driven by a block table the caller builds once per buffer layout.  Per element, with
+ * g' = g * clip (clip exactly as qfx_adamw_step computes it from gnorm_sq / max_norm / grad_scale):
+ *   8-bit block: m = qmap1[q1] * absmax1[blk], v = qmap2[q2] * absmax2[blk] (decoded), m = b1 m + (1-b1) g', v = b2 v + ((1-b2) g') g'
+ *   fp32 block:  m = m32[..], v = v32[..],                                     m = b1 m + (1-b1) g', v = b2 v + (1-b2) (g' g')
+ *   p += step_size * (m / (sqrt(v) + eps_hat)) with step_size = -lr sqrt(1-b2^t) / (1-b1^t), eps_hat = eps sqrt(1-b2^t) (both
+ *   formed in double on the host, rounded to fp32), then p *= 1 - lr wd when wd > 0 (decoupled, after the update).  The update uses
+ *   the fp32 moments, not their re-quantised images.  An element whose g' is not finite keeps p and its moments unchanged.
+ * Per 8-bit block (`len` consecutive elements of ONE tensor): absmax = max |m| (resp. |v|) over the block; each moment is stored as
+ * the nearest qmap code of m / absmax, the nearest being decided against the fp32 midpoints (q[k] + q[k+1]) / 2: x > midpoint -> the
+ * upper code, x == midpoint -> the lower one.  state1 then keeps its sign (bnb's rule: a code whose value has the other sign bit than
+ * m moves one index towards m).  A block whose absmax is 0 stores the code of 0.0 (it decodes to 0 whatever its codes).
+ * No atomics: same inputs -> same bits.  qmap1 / qmap2: fp32[256] ascending code books (signed / unsigned dynamic maps; a checkpoint
+ * carries its own).  Every pointer must be non-NULL (allocate one element for an unused buffer); p, g, q1, q2 are indexed by `off`,
+ * m32 / v32 by `state` of the fp32 entries; `off` and `state` are multiples of 4.  Rejected with QFX_EINVAL before any launch: a NULL
+ * pointer, blocksize outside {256, 2048}, n_blocks <= 0, step < 1, a negative lr. ---- */
+#define QFX_ADAM8BIT_BLOCKWISE 0
+#define QFX_ADAM8BIT_FP32 1
+typedef struct qfx_adam8bit_block {
+  int64_t off;           /* first element of the block in p / g / q1 / q2 */
+  int64_t state;         /* QFX_ADAM8BIT_BLOCKWISE: index into absmax1 / absmax2; QFX_ADAM8BIT_FP32: first element in m32 / v32 */
+  int32_t len;           /* 1 .. blocksize elements */
+  int32_t mode;          /* QFX_ADAM8BIT_BLOCKWISE or QFX_ADAM8BIT_FP32 */
+} qfx_adam8bit_block;
+typedef struct qfx_adam8bit_args {
+  float* p;              /* parameters, updated in place */
+  const float* g;        /* gradient (summed over ranks / micro-steps; scaled by grad_scale and the clip factor on the fly) */
+  uint8_t* q1;           /* state1 codes (signed map), same indexing as p */
+  uint8_t* q2;           /* state2 codes (unsigned map) */
+  float* absmax1;        /* per 8-bit block */
+  float* absmax2;
+  float* m32;            /* fp32 moments of the tensors below the 8-bit size */
+  float* v32;
+  const qfx_adam8bit_block* table;   /* device array of n_blocks entries */
+  int32_t n_blocks;
+  int32_t blocksize;     /* 256 or 2048: the largest `len` of the table */
+  const float* qmap1;    /* fp32[256] */
+  const float* qmap2;    /* fp32[256] */
+  float lr, beta1, beta2, eps, weight_decay;
+  int32_t step;          /* 1-based step count t (bias corrections) */
+  const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq_det) for the global-norm clip */
+  float max_norm, grad_scale;
+} qfx_adam8bit_args;
+int qfx_adam8bit_step(const qfx_adam8bit_args* a, void* stream);
+
 /* ---- runtime: a HIP stream confined to the first `n_cus` bits of the driver's CU mask (consecutive bits walk the 8 XCDs first, so
  * 16 = two CUs per XCD).  The persistent GEMM grids occupy 240 of the 256 CUs; leaf work of the backward (the LoRA weight-gradient
  * launches, which the reference's autograd also schedules off the dX critical path) runs here without ever taking a CU a GEMM block

@@ -873,6 +873,182 @@ __global__ __launch_bounds__(256) void prodigy_apply_kernel(float* __restrict__ 
   }
 }
 
+// ---- blockwise 8-bit Adam with bitsandbytes' state layout: see include/qfx.h.  The moment / parameter arithmetic is written out
+// operation by operation with contraction off, so every rounding point is the one of the restatement in tests/bnb8_ref.py.
+// blocksize 256: one wave per table entry, 4 elements per lane (one dwordx4 of p and of g, one dword of four codes per moment), the
+// block maximum a cross-lane reduction.  blocksize 2048: one 256-thread workgroup per entry, 8 elements per lane, maximum through LDS.
+struct A8Const { float b1, b2, omb1, omb2, step_size, eps_hat, decay, clip; int wd; };
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// number of midpoints below x (mid[255] = +inf): the nearest code, a tie (x == midpoint) going to the lower one
+__device__ __forceinline__ int a8_code(const float* mid, float x) {
+  int c = 0;
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) c += (x > mid[c + s - 1]) ? s : 0;
+  return c;
+}
+
+// one element: moments in (decoded or fp32), out updated; p updated.  bnb's two kernels associate the g'^2 term differently.
+template <bool FP32_FORM>
+__device__ __forceinline__ void a8_elem(float& p, float g, float& m, float& v, const A8Const& k) {
+#pragma clang fp contract(off)
+  const float gs = g * k.clip;
+  if (!__builtin_isfinite(gs)) return;
+  m = m * k.b1 + k.omb1 * gs;
+  v = FP32_FORM ? v * k.b2 + k.omb2 * (gs * gs) : v * k.b2 + (k.omb2 * gs) * gs;
+  p = p + k.step_size * (m / (sqrtf(v) + k.eps_hat));
+  if (k.wd) p = p * k.decay;
+}
+
+// E elements of one lane starting at element `base` of p / g / codes, n of them valid (n may be < E or <= 0)
+template <int E>
+__device__ __forceinline__ void a8_load(const float* __restrict__ src, int64_t base, int n, float (&x)[E]) {
+#pragma unroll
+  for (int j = 0; j < E; j += 4) {
+    if (n >= j + 4) {
+      const f32x4 t = *(const f32x4*)(src + base + j);
+      x[j] = t[0]; x[j + 1] = t[1]; x[j + 2] = t[2]; x[j + 3] = t[3];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) x[j + i] = (j + i < n) ? src[base + j + i] : 0.f;
+    }
+  }
+}
+template <int E>
+__device__ __forceinline__ void a8_store(float* __restrict__ dst, int64_t base, int n, const float (&x)[E]) {
+#pragma unroll
+  for (int j = 0; j < E; j += 4) {
+    if (n >= j + 4) {
+      f32x4 t; t[0] = x[j]; t[1] = x[j + 1]; t[2] = x[j + 2]; t[3] = x[j + 3];
+      *(f32x4*)(dst + base + j) = t;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) if (j + i < n) dst[base + j + i] = x[j + i];
+    }
+  }
+}
+template <int E>
+__device__ __forceinline__ void a8_load_codes(const uint8_t* __restrict__ src, int64_t base, int n, int (&c)[E]) {
+#pragma unroll
+  for (int j = 0; j < E; j += 4) {
+    if (n >= j + 4) {
+      const uint32_t w = *(const uint32_t*)(src + base + j);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c[j + i] = (w >> (8 * i)) & 0xff;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c[j + i] = (j + i < n) ? src[base + j + i] : 0;
+    }
+  }
+}
+template <int E>
+__device__ __forceinline__ void a8_store_codes(uint8_t* __restrict__ dst, int64_t base, int n, const int (&c)[E]) {
+#pragma unroll
+  for (int j = 0; j < E; j += 4) {
+    if (n >= j + 4) {     // packed 32-bit vector store
+      *(uint32_t*)(dst + base + j) = (uint32_t)c[j] | ((uint32_t)c[j + 1] << 8) | ((uint32_t)c[j + 2] << 16) | ((uint32_t)c[j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) if (j + i < n) dst[base + j + i] = (uint8_t)c[j + i];
+    }
+  }
+}
+
+// BS = 256: E = 4, a wave per entry (4 entries per workgroup and iteration); BS = 2048: E = 8, the workgroup per entry
+template <int BS>
+__global__ __launch_bounds__(256) void adam8bit_kernel(const qfx_adam8bit_args a, float step_size, float eps_hat) {
+#pragma clang fp contract(off)
+  constexpr bool WG = BS > 256;
+  constexpr int E = WG ? 8 : 4;
+  constexpr int LANES = WG ? 256 : 64;
+  static_assert(E * LANES == BS, "tile");
+  __shared__ float q1s[256], q2s[256], mid1[256], mid2[256];
+  __shared__ float red[2][2][4];
+  const int t = threadIdx.x;
+  q1s[t] = a.qmap1[t];
+  q2s[t] = a.qmap2[t];
+  mid1[t] = t < 255 ? (a.qmap1[t] + a.qmap1[t + 1]) / 2.0f : INFINITY;
+  mid2[t] = t < 255 ? (a.qmap2[t] + a.qmap2[t + 1]) / 2.0f : INFINITY;
+  A8Const k;
+  k.clip = a.grad_scale;
+  if (a.gnorm_sq != nullptr && a.max_norm > 0.f) {      // = adamw_kernel's prologue
+    const float nrm = sqrtf(*a.gnorm_sq) * a.grad_scale;
+    const float c = a.max_norm / (nrm + 1e-6f);
+    k.clip *= c < 1.0f ? c : 1.0f;
+  }
+  k.b1 = a.beta1; k.b2 = a.beta2; k.omb1 = 1.0f - a.beta1; k.omb2 = 1.0f - a.beta2;
+  k.step_size = step_size; k.eps_hat = eps_hat;
+  k.wd = a.weight_decay > 0.f; k.decay = 1.0f - a.lr * a.weight_decay;
+  __syncthreads();
+  const int lane = WG ? t : (t & 63);
+  const int64_t first = WG ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + (t >> 6);
+  const int64_t stride = WG ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
+  int parity = 0;
+  for (int64_t bi = first; bi < a.n_blocks; bi += stride) {
+    const qfx_adam8bit_block e = a.table[bi];
+    const int64_t base = e.off + (int64_t)lane * E;
+    const int n = e.len - lane * E;
+    float p[E], g[E], m[E], v[E];
+    a8_load<E>(a.p, base, n, p);
+    a8_load<E>(a.g, base, n, g);
+    if (e.mode == QFX_ADAM8BIT_FP32) {
+      const int64_t sb = e.state + (int64_t)lane * E;
+      a8_load<E>(a.m32, sb, n, m);
+      a8_load<E>(a.v32, sb, n, v);
+#pragma unroll
+      for (int j = 0; j < E; ++j) a8_elem<true>(p[j], g[j], m[j], v[j], k);
+      a8_store<E>(a.p, base, n, p);
+      a8_store<E>(a.m32, sb, n, m);
+      a8_store<E>(a.v32, sb, n, v);
+      continue;
+    }
+    int c1[E], c2[E];
+    a8_load_codes<E>(a.q1, base, n, c1);
+    a8_load_codes<E>(a.q2, base, n, c2);
+    const float am1 = a.absmax1[e.state], am2 = a.absmax2[e.state];
+    float mx1 = 0.f, mx2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      m[j] = q1s[c1[j]] * am1;
+      v[j] = q2s[c2[j]] * am2;
+      if (j < n) {
+        a8_elem<false>(p[j], g[j], m[j], v[j], k);
+        mx1 = fmaxf(mx1, fabsf(m[j]));
+        mx2 = fmaxf(mx2, fabsf(v[j]));
+      }
+    }
+    mx1 = wave_max(mx1);
+    mx2 = wave_max(mx2);
+    if (WG) {
+      if ((t & 63) == 0) { red[parity][0][t >> 6] = mx1; red[parity][1][t >> 6] = mx2; }
+      __syncthreads();
+      mx1 = fmaxf(fmaxf(red[parity][0][0], red[parity][0][1]), fmaxf(red[parity][0][2], red[parity][0][3]));
+      mx2 = fmaxf(fmaxf(red[parity][1][0], red[parity][1][1]), fmaxf(red[parity][1][2], red[parity][1][3]));
+      parity ^= 1;
+    }
+    a8_store<E>(a.p, base, n, p);
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+      const float x1 = mx1 > 0.f ? m[j] / mx1 : 0.f;
+      int c = a8_code(mid1, x1);
+      if (mx1 > 0.f && (__builtin_signbit(q1s[c]) != 0) != (__builtin_signbit(m[j]) != 0)) {      // state1 keeps its sign
+        c += m[j] > 0.f ? 1 : -1;
+        c = c < 0 ? 0 : (c > 255 ? 255 : c);
+      }
+      c1[j] = c;
+      c2[j] = a8_code(mid2, mx2 > 0.f ? v[j] / mx2 : 0.f);
+    }
+    a8_store_codes<E>(a.q1, base, n, c1);
+    a8_store_codes<E>(a.q2, base, n, c2);
+    if (lane == 0) { a.absmax1[e.state] = mx1; a.absmax2[e.state] = mx2; }
+  }
+}
+
 // ---- runtime helpers: CU-masked side stream + a probe of where blocks run --------------------------------------------------
 __global__ void where_kernel(uint32_t* __restrict__ out) {
   if (threadIdx.x == 0) {
@@ -1261,6 +1437,30 @@ extern "C" int qfx_prodigy_step(const qfx_prodigy_args* a, void* stream) {
                      (double)a->growth_rate);
   hipLaunchKernelGGL(prodigy_apply_kernel, dim3(blocks), dim3(256), 0, s, a->p, a->exp_avg, a->exp_avg_sq, a->n, a->state, a->eps,
                      a->weight_decay);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int qfx_adam8bit_step(const qfx_adam8bit_args* a, void* stream) {
+  if (!a || !a->p || !a->g || !a->q1 || !a->q2 || !a->absmax1 || !a->absmax2 || !a->m32 || !a->v32 || !a->table || !a->qmap1 ||
+      !a->qmap2)
+    return QFX_EINVAL;
+  if ((a->blocksize != 256 && a->blocksize != 2048) || a->n_blocks <= 0 || a->step < 1 || !(a->lr >= 0.f)) return QFX_EINVAL;
+  if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) return QFX_EINVAL;
+  // bnb's correction1 / correction2 / step_size, formed once in double here (the same value on every lane and every replica)
+  const double c1 = 1.0 - pow((double)a->beta1, (double)a->step);
+  const double c2 = sqrt(1.0 - pow((double)a->beta2, (double)a->step));
+  const float step_size = (float)(-(double)a->lr * c2 / c1);
+  const float eps_hat = (float)((double)a->eps * c2);
+  hipStream_t s = (hipStream_t)stream;
+  if (a->blocksize == 256) {
+    int64_t wgs = ((int64_t)a->n_blocks + 3) / 4;
+    if (wgs > 2048) wgs = 2048;
+    hipLaunchKernelGGL(adam8bit_kernel<256>, dim3((unsigned)wgs), dim3(256), 0, s, *a, step_size, eps_hat);
+  } else {
+    int64_t wgs = a->n_blocks < 2048 ? a->n_blocks : 2048;
+    hipLaunchKernelGGL(adam8bit_kernel<2048>, dim3((unsigned)wgs), dim3(256), 0, s, *a, step_size, eps_hat);
+  }
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

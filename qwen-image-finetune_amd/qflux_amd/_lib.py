@@ -122,6 +122,21 @@ class ProdigyArgs(C.Structure):
 PRODIGY_STATE = 12
 
 
+class Adam8bitBlock(C.Structure):
+    _fields_ = [("off", C.c_int64), ("state", C.c_int64), ("len", C.c_int32), ("mode", C.c_int32)]
+
+
+class Adam8bitArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("q1", C.c_void_p), ("q2", C.c_void_p), ("absmax1", C.c_void_p),
+                ("absmax2", C.c_void_p), ("m32", C.c_void_p), ("v32", C.c_void_p), ("table", C.c_void_p), ("n_blocks", C.c_int32),
+                ("blocksize", C.c_int32), ("qmap1", C.c_void_p), ("qmap2", C.c_void_p),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("step", C.c_int32), ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
+ADAM8BIT_BLOCKWISE, ADAM8BIT_FP32 = 0, 1     # qfx_adam8bit_block.mode
+
+
 class HeadLora(C.Structure):
     _fields_ = [("w_pk", C.c_void_p * 2),
                 ("part", C.c_void_p), ("part_hstride", C.c_int64), ("ld_part", C.c_int32), ("c0", C.c_int32), ("R", C.c_int32),
@@ -210,6 +225,7 @@ SYMBOLS = {
     "qfx_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _vp, _f, _f, _vp]),
     "qfx_prodigy_init_state": (C.c_int, [_vp, C.c_double, _vp]),
     "qfx_prodigy_step": (C.c_int, [C.POINTER(ProdigyArgs), _vp]),
+    "qfx_adam8bit_step": (C.c_int, [C.POINTER(Adam8bitArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),
     "qfx_stream_destroy": (C.c_int, [_vp]),
     "qfx_debug_where": (C.c_int, [_vp, _i32, _vp]),

@@ -341,6 +341,66 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, gnorm_sq=None, max_n
                                grad_scale, stream_ptr()), "qfx_adamw_step")
 
 
+class Adam8bitLayout:
+    """Block table of one flat-buffer layout for qfx_adam8bit_step, built once per layout.  `tensors[i]` = (off, numel, eight_bit,
+    first absmax index, number of absmax blocks, first element in the fp32 moment buffers) of entry i."""
+
+    def __init__(self, table, tensors, blocksize, min_8bit_size, n_absmax, n_fp32, extent):
+        self.table, self.tensors, self.blocksize, self.min_8bit_size = table, tensors, blocksize, min_8bit_size
+        self.n_blocks = table.numel() // C.sizeof(L.Adam8bitBlock)
+        self.n_absmax, self.n_fp32, self.extent = n_absmax, n_fp32, extent
+
+
+def adam8bit_block_table(entries, blocksize=256, min_8bit_size=4096, device=None):
+    """entries: (offset, numel) of every tensor in the flat buffers (offsets multiples of 4).  A tensor with numel >= min_8bit_size is
+    cut into ceil(numel / blocksize) 8-bit blocks (the last one short) with an absmax slot each, in entry order; a smaller one keeps
+    fp32 moments, packed at 64-element-aligned offsets of m32 / v32 and walked in blocksize chunks."""
+    if blocksize not in (256, 2048):
+        raise ValueError(f"adam8bit blocksize must be 256 or 2048, not {blocksize}")
+    rows, tensors, n_abs, n_fp32, extent = [], [], 0, 0, 0
+    for off, k in entries:
+        off, k = int(off), int(k)
+        if off % 4 or k <= 0:
+            raise ValueError(f"adam8bit block table: offset {off} / numel {k}")
+        nb = (k + blocksize - 1) // blocksize
+        if k >= min_8bit_size:
+            tensors.append((off, k, True, n_abs, nb, -1))
+            rows += [(off + j * blocksize, n_abs + j, min(blocksize, k - j * blocksize), L.ADAM8BIT_BLOCKWISE) for j in range(nb)]
+            n_abs += nb
+        else:
+            tensors.append((off, k, False, -1, 0, n_fp32))
+            rows += [(off + j * blocksize, n_fp32 + j * blocksize, min(blocksize, k - j * blocksize), L.ADAM8BIT_FP32) for j in range(nb)]
+            n_fp32 += (k + 63) // 64 * 64
+        extent = max(extent, off + k)
+    if not rows:
+        raise ValueError("adam8bit block table: no tensors")
+    arr = (L.Adam8bitBlock * len(rows))(*[L.Adam8bitBlock(*r) for r in rows])
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return Adam8bitLayout(table, tensors, blocksize, min_8bit_size, n_abs, n_fp32, extent)
+
+
+def adam8bit_step(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2, lr, betas, eps, weight_decay, step, gnorm_sq=None,
+                  max_norm=0.0, grad_scale=1.0):
+    """One blockwise 8-bit Adam step (bitsandbytes' Adam8bit / AdamW8bit state layout) over the flat buffers p / g; see qfx.h.
+    q1 / q2: uint8 codes indexed like p; absmax1 / absmax2: fp32[>= layout.n_absmax]; m32 / v32: fp32[>= layout.n_fp32] (one element
+    when unused); qmap1 / qmap2: fp32[256] ascending."""
+    f32, u8 = torch.float32, torch.uint8
+    for name, t, dt, need in (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
+                              ("q2", q2, u8, layout.extent), ("absmax1", absmax1, f32, max(1, layout.n_absmax)),
+                              ("absmax2", absmax2, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
+                              ("v32", v32, f32, max(1, layout.n_fp32)), ("qmap1", qmap1, f32, 256), ("qmap2", qmap2, f32, 256)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
+            raise ValueError(f"adam8bit_step: {name} must be a contiguous {dt} tensor on {p.device} with >= {need} elements")
+    if layout.table.device != p.device:
+        raise ValueError("adam8bit_step: the block table lives on another device")
+    a = L.Adam8bitArgs(_p(p), _p(g), _p(q1), _p(q2), _p(absmax1), _p(absmax2), _p(m32), _p(v32), _p(layout.table), layout.n_blocks,
+                       layout.blocksize, _p(qmap1), _p(qmap2), lr, betas[0], betas[1], eps, weight_decay, int(step), _p(gnorm_sq),
+                       max_norm, grad_scale)
+    L.check(lib.qfx_adam8bit_step(a, stream_ptr()), "qfx_adam8bit_step")
+
+
 # ---------------------------------------------------------------------------------------------- MX-FP8 (low-precision trunk)
 def quant_mxfp8(x, M=None, rows_per_batch=None, x_map=(0, 0), out=None):
     """x [*, K] bf16 (row stride x.stride(0)) -> (q uint8 [M, K], s uint8 [K/128, M, 4] tile-major scales) in the OCP MX-FP8

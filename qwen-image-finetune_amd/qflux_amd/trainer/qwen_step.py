@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from .. import ops
 from .._lib import PRODIGY_STATE as L_PRODIGY_STATE
+from . import adam8bit as A8
 
 BF = torch.bfloat16
 
@@ -53,11 +54,14 @@ class QwenLoraTrainStep:
         reference's parameter-free choice: configs/face_seg_flux_kontext_fp16_prodigy.yaml:41-47); optimizer_args = the extra
         init_args of that class (use_bias_correction, safeguard_warmup, beta3, decouple, d0, d_coef, growth_rate).  With Prodigy
         `lr` is the schedule multiplier the reference sets to 1.0.
+        "adam8bit_blockwise" / "adamw8bit_blockwise": bitsandbytes.optim.Adam8bit / AdamW8bit with their blockwise 8-bit moments and
+        state layout (trainer/adam8bit.py; weight decay decoupled, defaults 0 / 1e-2); optimizer_args: min_8bit_size (4096), blocksize
+        (256 or 2048).
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
-        if optimizer not in ("adamw", "adam", "adam8bit", "prodigy"):
+        if optimizer not in ("adamw", "adam", "adam8bit", "prodigy") + A8.BLOCKWISE:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / Prodigy
         # keeps its explicit value (the reference's Prodigy configs pass 0.01).  An EXPLICIT value is never reinterpreted.
@@ -66,22 +70,32 @@ class QwenLoraTrainStep:
             # lr + betas only) -- is Adam with blockwise 8-bit quantised moments, a device to fit 24-48 GB cards.  The LoRA state
             # here is 2 x 94 MB of fp32 next to 288 GB of HBM: the moments stay fp32 (strictly closer to exact Adam than the 8-bit
             # code book; optimizer.bin then holds fp32 exp_avg / exp_avg_sq in torch.optim.Adam's layout, not bnb's state1 / state2 /
-            # absmax blocks).  Adam's weight decay is the L2 form (added to the gradient), not AdamW's decoupled one: only the
-            # configs' weight_decay = 0 is mapped.
+            # absmax blocks; "adam8bit_blockwise" keeps those).  torch.optim.Adam's weight decay is the L2 form (added to the
+            # gradient); bnb's 8-bit Adam decays decoupled, after the update (adam8bit_blockwise).  Only the configs' weight_decay = 0
+            # is mapped here.
             if weight_decay is not None and float(weight_decay) != 0.0:
                 raise NotImplementedError(f"{optimizer} with L2 weight decay {weight_decay} (bnb adds wd * p to the gradient; the fused "
                                           "kernel implements AdamW's decoupled form only; the reference's configs use none)")
             weight_decay = 0.0
             self.optimizer_alias, optimizer = optimizer, "adamw"
         if weight_decay is None:
-            weight_decay = 0.01 if optimizer == "adamw" else 0.0
+            weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
         self.optimizer = optimizer
-        self.optimizer_args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6,
-                                   d_coef=1.0, growth_rate=float("inf"))
+        self.blockwise = optimizer in A8.BLOCKWISE
+        if self.blockwise:
+            self.optimizer_args = dict(min_8bit_size=4096, blocksize=256)
+        else:
+            self.optimizer_args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6,
+                                       d_coef=1.0, growth_rate=float("inf"))
         unknown = set(optimizer_args or {}) - set(self.optimizer_args)
-        if unknown or (optimizer_args and optimizer != "prodigy"):
+        if unknown or (optimizer_args and optimizer not in ("prodigy",) + A8.BLOCKWISE):
             raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
         self.optimizer_args.update(optimizer_args or {})
+        if self.blockwise:
+            if self.optimizer_args["blocksize"] not in A8.BLOCKSIZES or int(self.optimizer_args["min_8bit_size"]) < 1:
+                raise ValueError(f"{optimizer}: blocksize must be one of {A8.BLOCKSIZES} and min_8bit_size >= 1 ({self.optimizer_args})")
+            self.optimizer_args["min_8bit_size"] = int(self.optimizer_args["min_8bit_size"])
+        self._a8 = None
         self._ps = self._p0 = self._pstate = None
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
         self.dit = dit
@@ -307,6 +321,8 @@ class QwenLoraTrainStep:
 
     def optimizer_step(self, grad_scale=1.0):
         st = self.dit.lora_store
+        if self.blockwise:
+            return self._blockwise_step(st, grad_scale)
         if self._m is None or self._m.numel() != st.pflat.numel() or self._m.device != st.pflat.device:
             self._m = torch.zeros_like(st.pflat)
             self._v = torch.zeros_like(st.pflat)
@@ -329,6 +345,22 @@ class QwenLoraTrainStep:
                        self.weight_decay, self.global_step, gnorm_sq=self._gnorm, max_norm=self.max_grad_norm,
                        grad_scale=grad_scale)
 
+    def _ensure_a8(self, st):
+        bs, m8 = self.optimizer_args["blocksize"], self.optimizer_args["min_8bit_size"]
+        if self._a8 is None or self._a8.key != A8.BlockwiseState.layout_key(st, bs, m8):
+            self._a8 = A8.BlockwiseState(st, bs, m8)
+        if self._gnorm is None or self._gnorm.device != st.pflat.device:
+            self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
+        return self._a8
+
+    def _blockwise_step(self, st, grad_scale):
+        a8 = self._ensure_a8(st)
+        self.global_step += 1
+        if getattr(self, "_gparts", None) is None or self._gparts.device != st.pflat.device:
+            self._gparts = torch.zeros(1024, dtype=torch.float32, device=st.pflat.device)
+        ops.sumsq_det(st.gflat, self._gnorm, self._gparts)
+        a8.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm, grad_scale)
+
     def _mark_unexchanged(self):
         dp = getattr(self.dit, "_dp", None)
         if dp is not None:
@@ -346,6 +378,8 @@ class QwenLoraTrainStep:
         state = {}
         if self.optimizer == "prodigy":
             return self._prodigy_state_dict()
+        if self.blockwise:
+            return self._blockwise_state_dict()
         for i, (_, p, off, k) in enumerate(st.entries):
             if self._m is None:
                 break
@@ -354,6 +388,38 @@ class QwenLoraTrainStep:
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "params": list(range(len(st.entries)))}
         return {"state": state, "param_groups": [group], "global_step": self.global_step}
+
+    def _blockwise_state_dict(self):
+        """bitsandbytes' Optimizer2State layout: per parameter {"step", "state1", "state2", "qmap1", "qmap2", "absmax1", "absmax2"}
+        (8-bit) or {"step", "state1", "state2"} (fp32 moments, numel < min_8bit_size); the group holds lr, betas, eps, weight_decay."""
+        st = self.dit.lora_store
+        state = {}
+        if self._a8 is not None and self.global_step > 0:
+            for i, (_, p, off, k) in enumerate(st.entries):
+                state[i] = self._a8.param_state(i, p.shape, self.global_step)
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                 "params": list(range(len(st.entries)))}
+        return {"state": state, "param_groups": [group], "global_step": self.global_step}
+
+    def _load_blockwise_state_dict(self, sd):
+        st = self.dit.lora_store
+        g = sd["param_groups"][0]
+        self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
+        step = int(sd.get("global_step", 0))
+        bs, q1, q2 = A8.file_layout(sd["state"], st.entries)
+        if bs is not None:
+            self.optimizer_args["blocksize"] = bs
+        self._a8 = None
+        self._ensure_a8(st)
+        if q1 is not None:
+            self._a8.qmap1.copy_(q1); self._a8.qmap2.copy_(q2)
+        for i in range(len(st.entries)):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            self._a8.load_param_state(i, e)
+            step = max(step, int(float(e["step"])))
+        self.global_step = step
 
     _PS_KEYS = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k")
 
@@ -403,6 +469,8 @@ class QwenLoraTrainStep:
     def load_state_dict(self, sd):
         if self.optimizer == "prodigy":
             return self._load_prodigy_state_dict(sd)
+        if self.blockwise:
+            return self._load_blockwise_state_dict(sd)
         st = self.dit.lora_store
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
@@ -413,8 +481,10 @@ class QwenLoraTrainStep:
             e = sd["state"].get(i)
             if e is None:
                 continue
-            self._m[off:off + k].copy_(e["exp_avg"].reshape(-1).to(self._m.device))
-            self._v[off:off + k].copy_(e["exp_avg_sq"].reshape(-1).to(self._v.device))
+            # a bitsandbytes-layout file (state1 / state2 / absmax / qmap) resumes with its moments dequantised
+            ea, es = (e["exp_avg"], e["exp_avg_sq"]) if "exp_avg" in e else A8.bnb_moments(e)
+            self._m[off:off + k].copy_(ea.reshape(-1).to(self._m.device))
+            self._v[off:off + k].copy_(es.reshape(-1).to(self._v.device))
             step = max(step, int(float(e["step"])))
         self.global_step = int(step)
 
@@ -447,6 +517,8 @@ class QwenLoraTrainStep:
             t = getattr(self, name, None)
             if t is not None:
                 bufs.append((name, t))
+        if self._a8 is not None:
+            bufs += self._a8.buffers()
         return bufs
 
     def broadcast_state(self, src: int = 0):
@@ -457,10 +529,18 @@ class QwenLoraTrainStep:
         if self.world <= 1:
             return
         dev = self.dit.lora_store.pflat.device
-        have = torch.tensor([float(self._m is not None), float(self._pstate is not None), float(self.global_step)], device=dev)
+        a8 = self._a8 is not None
+        have = torch.tensor([float(self._m is not None), float(self._pstate is not None), float(self.global_step), float(a8),
+                             float(self.optimizer_args["blocksize"] if a8 else 0), float(self.optimizer_args["min_8bit_size"] if a8 else 0)],
+                            device=dev)
         dist.broadcast(have, src=src, group=self.group)
         st = self.dit.lora_store
         have_m, have_p = bool(have[0].item()), bool(have[1].item())
+        if bool(have[3].item()):       # blockwise 8-bit state: rank `src`'s block size / 8-bit threshold, then its buffers (appended last)
+            self.optimizer_args["blocksize"], self.optimizer_args["min_8bit_size"] = int(have[4].item()), int(have[5].item())
+            self._ensure_a8(st)
+        else:
+            self._a8 = None
         # the buffer list is derived from the AGREED flags on every rank (same collectives in the same order everywhere): buffers
         # rank `src` has are created where missing, buffers it lacks are dropped locally (a rank that had stepped before must not
         # carry moments the others do not have)
@@ -478,6 +558,7 @@ class QwenLoraTrainStep:
             self._ps = self._p0 = self._pstate = None
         self.global_step = int(have[2].item())
         bufs = [st.pflat] + ([self._m, self._v] if have_m else []) + ([self._ps, self._p0, self._pstate] if have_p else [])
+        bufs += [t for _, t in self._a8.buffers()] if self._a8 is not None else []
         for t in bufs:
             dist.broadcast(t, src=src, group=self.group)
 
@@ -489,8 +570,10 @@ class QwenLoraTrainStep:
         st = self.dit.lora_store
         dev = st.pflat.device
         sums = []
-        for name in ("lora", "_m", "_v", "_ps", "_p0", "_pstate"):      # fixed layout: a buffer a rank lacks is part of the verdict
-            t = st.pflat if name == "lora" else getattr(self, name, None)
+        a8 = dict(self._a8.buffers()) if self._a8 is not None else {}
+        for name in ("lora", "_m", "_v", "_ps", "_p0", "_pstate", "_a8_q1", "_a8_q2", "_a8_absmax1", "_a8_absmax2", "_a8_m32", "_a8_v32",
+                     "_a8_qmap1", "_a8_qmap2"):      # fixed layout: a buffer a rank lacks is part of the verdict
+            t = st.pflat if name == "lora" else (a8.get(name) if name.startswith("_a8") else getattr(self, name, None))
             if t is None:
                 sums += [torch.zeros((), dtype=torch.float64, device=dev)] * 3
                 continue
@@ -528,14 +611,24 @@ class QwenLoraTrainStep:
         return loss
 
 
-def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None) -> dict:
+_BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
+             "bitsandbytes.optim.PagedAdamW8bit")
+
+
+def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None, state_bits: int = 32) -> dict:
     """The reference's YAML `optimizer: {class_path, init_args}` (BaseTrainer.configure_optimizers, base_trainer.py:884-909) ->
     keyword arguments of QwenLoraTrainStep / FluxKontextTrainStep.
         torch.optim.AdamW                      -> optimizer="adamw"   (lr, betas, eps, weight_decay)
         bitsandbytes.optim.Adam8bit / Adam     -> optimizer="adam8bit": Adam with FP32 moments (see __init__; 8-bit states buy nothing
         bitsandbytes.optim.AdamW8bit / AdamW   -> optimizer="adamw"     next to 288 GB of HBM)
         prodigyopt.Prodigy                     -> optimizer="prodigy" + optimizer_args
+    state_bits=8 maps the four 8-bit bnb classes (Adam8bit, PagedAdam8bit, AdamW8bit, PagedAdamW8bit) to the blockwise 8-bit optimizer
+    with bnb's state layout instead: "adam8bit_blockwise" (weight decay default 0) / "adamw8bit_blockwise" (default 1e-2), min_8bit_size
+    honoured; percentile_clipping != 100, max_unorm != 0, block_wise=False, skip_zeros=True and amsgrad=True are refused; is_paged only
+    moves memory (same math).  state_bits=32 is the mapping above.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
+    if state_bits not in (8, 32):
+        raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
     a = dict(init_args or {})
     name = class_path.rsplit(".", 1)[-1]
     out = {}
@@ -544,7 +637,20 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None)
             out[k] = float(a.pop(k))
     if "betas" in a:
         out["betas"] = tuple(float(b) for b in a.pop("betas"))
-    if class_path in ("torch.optim.AdamW", "bitsandbytes.optim.AdamW8bit", "bitsandbytes.optim.AdamW", "bitsandbytes.optim.PagedAdamW8bit"):
+    if state_bits == 8 and class_path in _BNB_8BIT:
+        adamw = "AdamW" in name
+        out["optimizer"] = "adamw8bit_blockwise" if adamw else "adam8bit_blockwise"
+        out.setdefault("weight_decay", 0.01 if adamw else 0.0)
+        refused = {"percentile_clipping": (100, "percentile clipping"), "max_unorm": (0.0, "update-norm clipping (max_unorm)"),
+                   "block_wise": (True, "non-blockwise 8-bit state"), "skip_zeros": (False, "skip_zeros"), "amsgrad": (False, "amsgrad")}
+        for k, (ok, what) in refused.items():
+            if k in a and a.pop(k) != ok:
+                raise NotImplementedError(f"{class_path}: {what} is not implemented by the blockwise 8-bit step ({k} must be {ok!r})")
+        if "min_8bit_size" in a:
+            out["optimizer_args"] = {"min_8bit_size": int(a.pop("min_8bit_size"))}
+        a.pop("is_paged", None)        # paged memory: where the state lives, not what is computed
+        a.pop("optim_bits", None)      # the 8-bit classes pass 8 whatever this says
+    elif class_path in ("torch.optim.AdamW", "bitsandbytes.optim.AdamW8bit", "bitsandbytes.optim.AdamW", "bitsandbytes.optim.PagedAdamW8bit"):
         out["optimizer"] = "adamw"
     elif class_path in ("torch.optim.Adam", "bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.Adam", "bitsandbytes.optim.PagedAdam8bit"):
         out["optimizer"] = "adam8bit" if "8bit" in name else "adam"
