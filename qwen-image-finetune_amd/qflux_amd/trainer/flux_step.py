@@ -52,32 +52,30 @@ class FluxKontextTrainStep(QwenLoraTrainStep):
     def forward_backward(self, embeddings, noise=None, t=None, grad_scale=1.0, sync=True):
         """Same contract as QwenLoraTrainStep.forward_backward (criterion "mse" | "mask_edit", sync=False = no_sync micro-step)."""
         packed, target, pe, pooled, t, guidance, img_ids, txt_ids, S_t = self._prepare_flux(embeddings, noise, t)
-        dit = self.dit
-        plan = dit.get_plan(packed.shape[0], packed.shape[1], pe.shape[1], img_ids, txt_ids)
-        dit.lora_store
-        self._ensure_synced()
-        pred = plan.run_forward((packed, pooled, guidance), pe, t)
-        if self.criterion == "mask_edit":
-            B = packed.shape[0]
-            tw = self._token_weights(embeddings, B, S_t, pred.device)
-            loss, dpred = ops.mse_token_weighted_fwd_bwd(pred, target, tw, S_t, 1.0 / (B * S_t), gscale=grad_scale)
-        else:
-            loss, dpred = ops.mse_loss_fwd_bwd(pred, target, S_t, gscale=grad_scale)
-        self._mark_unexchanged()
-        plan.run_backward(dpred, on_segment=self._bucket_hook() if (self.world > 1 and sync) else None)
-        return loss
+        plan = self.dit.get_plan(packed.shape[0], packed.shape[1], pe.shape[1], img_ids, txt_ids)
+        return self._fused_pass(plan, (packed, pooled, guidance), pe, t, target, S_t, grad_scale, sync, embeddings)
 
     def train_step(self, embeddings, noise=None, t=None, micro_batches=None):
-        """One optimisation step; micro_batches = further embedding dicts of the gradient-accumulation window (as the base class)."""
-        extra = list(micro_batches or [])
-        k = 1 + len(extra)
-        loss = self.forward_backward(embeddings, noise, t, sync=not extra)
-        for j, mb in enumerate(extra):
-            loss = loss + self.forward_backward(mb, sync=(j == len(extra) - 1))
-        scale = self.allreduce_grads() / k
-        self.optimizer_step(grad_scale=scale)
-        self.zero_grad()
-        return loss / k if k > 1 else loss
+        """QwenLoraTrainStep.train_step with FLUX's keyword t (the flow-matching times, injectable like noise)."""
+        return super().train_step(embeddings, noise, t, micro_batches)
+
+    def compute_loss_multires(self, samples, txt):
+        """Autograd path: AttentionMaskMseLoss(reduction='mean') on the masked prediction (attention_mask_loss.py:146-226)."""
+        b = _build_multires_batch(self, samples, txt)
+        pred = self.dit(hidden_states=b["inp"], timestep=b["timestep"], guidance=b["guidance"], pooled_projections=b["pooled"],
+                        encoder_hidden_states=b["pe"], txt_ids=b["txt_ids"], img_ids=b["ids"], attention_mask=b["mask"],
+                        joint_attention_kwargs={}, return_dict=False)[0][:, : b["n_t_max"]]
+        el = (pred.float() - b["target"].float()) ** 2
+        tok = (el * b["tok_w"].unsqueeze(-1)).mean(dim=2)
+        return tok.sum() / (b["n_valid"] + 1e-12)
+
+    def forward_backward_multires(self, samples, txt, grad_scale=1.0, sync=True):
+        b = _build_multires_batch(self, samples, txt)
+        B, S_i, T = b["inp"].shape[0], b["inp"].shape[1], b["pe"].shape[1]
+        valid = b["mask"][:, T:].sum(dim=1).tolist()
+        plan = self.dit.get_plan_multires(B, S_i, T, b["ids"], valid)
+        return self._fused_pass(plan, (b["inp"], b["pooled"], b["guidance"]), b["pe"], b["timestep"], b["target"], b["n_t_max"], grad_scale,
+                                sync, tok_w=b["tok_w"].contiguous(), inv_denom=1.0 / (b["n_valid"] + 1e-12))
 
 
 def _build_multires_batch(step, samples, txt):
@@ -125,34 +123,3 @@ def _build_multires_batch(step, samples, txt):
     pooled = txt["pooled_prompt_embeds"].to(dev).to(dt)
     return dict(inp=inp, ids=idb, mask=full, tok_w=tok_w.to(dev), target=target, timestep=timestep, guidance=guidance, pe=pe,
                 pooled=pooled, txt_ids=txt["text_ids"].float().cpu(), n_t_max=n_t_max, n_valid=float(sum(n_t)))
-
-
-def _compute_loss_multires(self, samples, txt):
-    """Autograd path: AttentionMaskMseLoss(reduction='mean') on the masked prediction (attention_mask_loss.py:146-226)."""
-    b = _build_multires_batch(self, samples, txt)
-    pred = self.dit(hidden_states=b["inp"], timestep=b["timestep"], guidance=b["guidance"], pooled_projections=b["pooled"],
-                    encoder_hidden_states=b["pe"], txt_ids=b["txt_ids"], img_ids=b["ids"], attention_mask=b["mask"],
-                    joint_attention_kwargs={}, return_dict=False)[0][:, : b["n_t_max"]]
-    el = (pred.float() - b["target"].float()) ** 2
-    tok = (el * b["tok_w"].unsqueeze(-1)).mean(dim=2)
-    return tok.sum() / (b["n_valid"] + 1e-12)
-
-
-def _forward_backward_multires(self, samples, txt, grad_scale=1.0, sync=True):
-    b = _build_multires_batch(self, samples, txt)
-    dit = self.dit
-    B, S_i, T = b["inp"].shape[0], b["inp"].shape[1], b["pe"].shape[1]
-    valid = b["mask"][:, T:].sum(dim=1).tolist()
-    plan = dit.get_plan_multires(B, S_i, T, b["ids"], valid)
-    dit.lora_store
-    self._ensure_synced()
-    pred = plan.run_forward((b["inp"], b["pooled"], b["guidance"]), b["pe"], b["timestep"])
-    loss, dpred = ops.mse_token_weighted_fwd_bwd(pred, b["target"], b["tok_w"].contiguous(), b["n_t_max"], 1.0 / (b["n_valid"] + 1e-12),
-                                                 gscale=grad_scale)
-    self._mark_unexchanged()
-    plan.run_backward(dpred, on_segment=self._bucket_hook() if (self.world > 1 and sync) else None)
-    return loss
-
-
-FluxKontextTrainStep.compute_loss_multires = _compute_loss_multires
-FluxKontextTrainStep.forward_backward_multires = _forward_backward_multires

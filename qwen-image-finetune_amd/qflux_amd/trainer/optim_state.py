@@ -1,0 +1,207 @@
+"""Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
+file layout), ProdigyState (prodigyopt.Prodigy's) and BlockwiseState (bitsandbytes' blockwise 8-bit).  QwenLoraTrainStep
+holds one of them and knows only their common surface:
+  cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
+  LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
+  NAMES / buffers()              fixed, ordered (name, tensor) list that broadcast_state sends and check_replicas sums
+  step(store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args)   the family's one step launch
+  cls.save(state, entries, step, args) -> (extra param-group fields, per-parameter state); state may be None (no step yet)
+  cls.load(store, sd, args) -> (state or None, highest per-parameter step the family reads, else 0)"""
+from __future__ import annotations
+
+import torch
+
+from .. import ops
+from .._lib import PRODIGY_STATE
+from . import adam8bit as A8
+
+
+def _out(t, off, k, shape=None):
+    """CPU copy of one parameter's slice of a flat buffer (shaped like the parameter when given)."""
+    t = t[off:off + k]
+    return (t if shape is None else t.view(shape)).detach().cpu().clone()
+
+
+class FlatState:
+    LAYOUT_ARGS = ()
+
+    def __init__(self, store, args):
+        self.key = self.layout_key(store, args)
+
+    @classmethod
+    def layout_key(cls, store, args):
+        return (tuple((off, k) for _, _, off, k in store.entries), str(store.pflat.device)) + tuple(int(args[n]) for n in cls.LAYOUT_ARGS)
+
+    def buffers(self):
+        return [(n, getattr(self, n)) for n in self.NAMES]
+
+
+class AdamWState(FlatState):
+    """exp_avg / exp_avg_sq in fp32, indexed like pflat (also the "adam" / "adam8bit" aliases)."""
+    NAMES = ("m", "v")
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.m = torch.zeros_like(store.pflat)
+        self.v = torch.zeros_like(store.pflat)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        ops.adamw_step(store.pflat, store.gflat, self.m, self.v, lr, betas[0], betas[1], eps, weight_decay, step, gnorm_sq=gnorm_sq,
+                       max_norm=max_norm, grad_scale=grad_scale)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """torch.optim.AdamW's per-parameter {"step", "exp_avg", "exp_avg_sq"}."""
+        if state is None:
+            return {"amsgrad": False}, {}
+        return {"amsgrad": False}, {i: {"step": torch.tensor(float(step)), "exp_avg": _out(state.m, off, k, p.shape),
+                                        "exp_avg_sq": _out(state.v, off, k, p.shape)} for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        state, step = cls(store, args), 0
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            # a bitsandbytes-layout file (state1 / state2 / absmax / qmap) resumes with its moments dequantised
+            ea, es = (e["exp_avg"], e["exp_avg_sq"]) if "exp_avg" in e else A8.bnb_moments(e)
+            state.m[off:off + k].copy_(ea.reshape(-1).to(state.m.device))
+            state.v[off:off + k].copy_(es.reshape(-1).to(state.v.device))
+            step = max(step, int(float(e["step"])))
+        return state, step
+
+
+class ProdigyState(AdamWState):
+    """AdamW's two moments plus s, p0 and the fp64 device scalars d, d_max, d_numerator, d_denom, d_hat, k (pstate)."""
+    NAMES = ("m", "v", "ps", "p0", "pstate")
+    GROUP = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k")
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.ps = self.p0 = self.pstate = None     # created by the first step(), as prodigyopt does: p0 = the parameters at that call
+
+    def _create(self, p0=None):
+        self.ps = torch.zeros_like(self.m)
+        self.p0 = torch.zeros_like(self.m) if p0 is None else p0.detach().clone()
+        self.pstate = torch.zeros(PRODIGY_STATE, dtype=torch.float64, device=self.m.device)
+
+    def buffers(self):
+        if self.pstate is None:       # a state that is to receive rank src's buffers (broadcast_state)
+            self._create()
+        return super().buffers()
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        if self.pstate is None:
+            self._create(store.pflat)
+            ops.prodigy_init_state(self.pstate, args["d0"])
+        ops.prodigy_step(store.pflat, store.gflat, self.m, self.v, self.ps, self.p0, self.pstate, lr=lr, betas=betas, eps=eps,
+                         weight_decay=weight_decay, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale, **args)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """prodigyopt's layout: per parameter {"step", "s", "p0", "exp_avg", "exp_avg_sq"}; the group carries the init_args and
+        d, d_max, d_numerator, d_denom, d_hat, k (d0 defaults before the first step)."""
+        d0 = args["d0"]
+        group = dict(args, d=d0, d_max=d0, d_numerator=0.0, d_denom=0.0, d_hat=d0, k=0)
+        if state is None:
+            return group, {}
+        group.update(zip(cls.GROUP, state.pstate.cpu().tolist()))
+        group["k"] = int(group["k"])
+        return group, {i: {"step": group["k"], "s": _out(state.ps, off, k), "p0": _out(state.p0, off, k),
+                           "exp_avg": _out(state.m, off, k, p.shape), "exp_avg_sq": _out(state.v, off, k, p.shape)}
+                       for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """The step count is the group's k (QwenLoraTrainStep reads it), not the per-parameter one."""
+        g = sd["param_groups"][0]
+        for n in args:
+            if n in g:
+                args[n] = g[n]
+        if not sd["state"]:
+            return None, 0
+        state = cls(store, args)
+        state._create()
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"][i]
+            state.m[off:off + k].copy_(e["exp_avg"].reshape(-1)); state.v[off:off + k].copy_(e["exp_avg_sq"].reshape(-1))
+            state.ps[off:off + k].copy_(e["s"].reshape(-1))
+            if e["p0"].numel() == k:            # the package stores a 0-dim zero for an all-zero parameter
+                state.p0[off:off + k].copy_(e["p0"].reshape(-1))
+        state.pstate.copy_(torch.tensor([float(g[n]) for n in cls.GROUP] + [0.0] * (PRODIGY_STATE - len(cls.GROUP)), dtype=torch.float64))
+        return state, 0
+
+
+class BlockwiseState(FlatState):
+    """bitsandbytes' blockwise 8-bit Adam / AdamW (adam8bit.py): codes indexed like pflat, absmax per 8-bit block, fp32 moments of the
+    tensors below min_8bit_size, the two code books, and the block table of the layout."""
+    LAYOUT_ARGS = ("blocksize", "min_8bit_size")
+    NAMES = ("q1", "q2", "absmax1", "absmax2", "m32", "v32", "qmap1", "qmap2")
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        dev = store.pflat.device
+        self.layout = ops.adam8bit_block_table([(off, k) for _, _, off, k in store.entries], args["blocksize"], args["min_8bit_size"],
+                                               device=dev)
+        n = store.pflat.numel()
+        self.q1 = torch.zeros(n, dtype=torch.uint8, device=dev)     # bnb's initial state: codes 0, absmax 0 (decodes to 0)
+        self.q2 = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.absmax1 = torch.zeros(max(1, self.layout.n_absmax), dtype=torch.float32, device=dev)
+        self.absmax2 = torch.zeros_like(self.absmax1)
+        self.m32 = torch.zeros(max(1, self.layout.n_fp32), dtype=torch.float32, device=dev)
+        self.v32 = torch.zeros_like(self.m32)
+        self.qmap1 = A8.dynamic_map(True).to(dev)
+        self.qmap2 = A8.dynamic_map(False).to(dev)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        ops.adam8bit_step(store.pflat, store.gflat, self.q1, self.q2, self.absmax1, self.absmax2, self.m32, self.v32, self.layout,
+                          self.qmap1, self.qmap2, lr, betas, eps, weight_decay, step, gnorm_sq=gnorm_sq, max_norm=max_norm,
+                          grad_scale=grad_scale)
+
+    def param_state(self, i, shape, step):
+        """bnb's per-parameter state of entry i (CPU tensors)."""
+        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        if not eight:
+            return {"step": step, "state1": _out(self.m32, s0, k, shape), "state2": _out(self.v32, s0, k, shape)}
+        return {"step": step, "state1": _out(self.q1, off, k, shape), "state2": _out(self.q2, off, k, shape),
+                "qmap1": self.qmap1.cpu().clone(), "qmap2": self.qmap2.cpu().clone(),
+                "absmax1": _out(self.absmax1, a0, nb), "absmax2": _out(self.absmax2, a0, nb)}
+
+    def load_param_state(self, i, e):
+        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        if (e["state1"].dtype == torch.uint8) != eight:
+            raise ValueError(f"optimizer state of parameter {i} ({k} elements) is {'8-bit' if not eight else 'fp32'} in the file: it was "
+                             f"saved with another min_8bit_size than {self.layout.min_8bit_size}")
+        if not eight:
+            self.m32[s0:s0 + k].copy_(e["state1"].reshape(-1)); self.v32[s0:s0 + k].copy_(e["state2"].reshape(-1))
+            return
+        if e["absmax1"].numel() != nb or e["absmax2"].numel() != nb:
+            raise ValueError(f"optimizer state of parameter {i}: {e['absmax1'].numel()} absmax blocks, {nb} expected")
+        self.q1[off:off + k].copy_(e["state1"].reshape(-1)); self.q2[off:off + k].copy_(e["state2"].reshape(-1))
+        self.absmax1[a0:a0 + nb].copy_(e["absmax1"].reshape(-1)); self.absmax2[a0:a0 + nb].copy_(e["absmax2"].reshape(-1))
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """bnb's Optimizer2State layout: per parameter {"step", "state1", "state2", "qmap1", "qmap2", "absmax1", "absmax2"} (8-bit) or
+        {"step", "state1", "state2"} (fp32 moments, numel < min_8bit_size); no group fields of its own."""
+        if state is None or step == 0:
+            return {}, {}
+        return {}, {i: state.param_state(i, p.shape, step) for i, (_, p, _, _) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """The block size is inferred from the file's absmax sizes, the code books are the file's."""
+        bs, q1, q2 = A8.file_layout(sd["state"], store.entries)
+        if bs is not None:
+            args["blocksize"] = bs
+        state, step = cls(store, args), 0
+        if q1 is not None:
+            state.qmap1.copy_(q1); state.qmap2.copy_(q2)
+        for i in range(len(store.entries)):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            state.load_param_state(i, e)
+            step = max(step, int(float(e["step"])))
+        return state, step

@@ -21,8 +21,8 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from .._lib import PRODIGY_STATE as L_PRODIGY_STATE
 from . import adam8bit as A8
+from .optim_state import AdamWState, BlockwiseState, ProdigyState
 
 BF = torch.bfloat16
 
@@ -82,6 +82,7 @@ class QwenLoraTrainStep:
             weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
         self.optimizer = optimizer
         self.blockwise = optimizer in A8.BLOCKWISE
+        self._opt_cls = BlockwiseState if self.blockwise else {"adamw": AdamWState, "prodigy": ProdigyState}[optimizer]
         if self.blockwise:
             self.optimizer_args = dict(min_8bit_size=4096, blocksize=256)
         else:
@@ -95,8 +96,7 @@ class QwenLoraTrainStep:
             if self.optimizer_args["blocksize"] not in A8.BLOCKSIZES or int(self.optimizer_args["min_8bit_size"]) < 1:
                 raise ValueError(f"{optimizer}: blocksize must be one of {A8.BLOCKSIZES} and min_8bit_size >= 1 ({self.optimizer_args})")
             self.optimizer_args["min_8bit_size"] = int(self.optimizer_args["min_8bit_size"])
-        self._a8 = None
-        self._ps = self._p0 = self._pstate = None
+        self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
         self.dit = dit
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
@@ -106,12 +106,12 @@ class QwenLoraTrainStep:
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         self.timesteps_tbl, self.sigmas_tbl = flowmatch_tables()
         self.global_step = 0
-        self._m = self._v = None
-        self._gnorm = None
+        self._gnorm = self._gparts = None
         # data-parallel exchange overlapped with the backward: the flat gradient is all-reduced in buckets of whole DiT
         # blocks as soon as their backward segment has been enqueued (the gradient of block i is final when its segment ends)
         self.bucket_bytes = int(bucket_mb * (1 << 20))
         self._pending = []
+        self._finish_buckets = None
         self._reduced = False
         self._synced = False      # rank 0's adapter / optimizer state is broadcast before the first step (broadcast_state)
         self._synced_version = None
@@ -186,17 +186,23 @@ class QwenLoraTrainStep:
         sync=False = accelerator.accumulate()/no_sync micro-step (base_trainer.py:518): no gradient exchange is started; pass
         sync=True on the last micro-step of the window (the buckets then carry the accumulated sums)."""
         packed, target, pe, t_in, S_t = self._prepare(embeddings, noise, u)
-        dit = self.dit
-        plan = dit.get_plan(packed.shape[0], packed.shape[1], pe.shape[1], embeddings["img_shapes"], None)
-        dit.lora_store  # make sure the flat buffers / grads are attached
+        plan = self.dit.get_plan(packed.shape[0], packed.shape[1], pe.shape[1], embeddings["img_shapes"], None)
+        return self._fused_pass(plan, packed, pe, t_in, target, S_t, grad_scale, sync, embeddings)
+
+    def _fused_pass(self, plan, inputs, pe, t, target, n_tok, grad_scale, sync, embeddings=None, tok_w=None, inv_denom=None):
+        """The device part of every fused forward_backward: forward program, loss kernel, backward program.  The loss is the MSE
+        over the first n_tok predicted tokens; token-weighted with tok_w / inv_denom when given, or with the mask_edit criterion's
+        weights (embeddings["edit_mask"]).  sync: the bucketed gradient exchange runs behind the backward."""
+        self.dit.lora_store  # make sure the flat buffers / grads are attached
         self._ensure_synced()
-        pred = plan.run_forward(packed, pe, t_in)
-        if self.criterion == "mask_edit":
-            B = packed.shape[0]
-            tw = self._token_weights(embeddings, B, S_t, pred.device)
-            loss, dpred = ops.mse_token_weighted_fwd_bwd(pred, target, tw, S_t, 1.0 / (B * S_t), gscale=grad_scale)
+        pred = plan.run_forward(inputs, pe, t)
+        if tok_w is None and self.criterion == "mask_edit":
+            B = target.shape[0]
+            tok_w, inv_denom = self._token_weights(embeddings, B, n_tok, pred.device), 1.0 / (B * n_tok)
+        if tok_w is None:
+            loss, dpred = ops.mse_loss_fwd_bwd(pred, target, n_tok, gscale=grad_scale)
         else:
-            loss, dpred = ops.mse_loss_fwd_bwd(pred, target, S_t, gscale=grad_scale)
+            loss, dpred = ops.mse_token_weighted_fwd_bwd(pred, target, tok_w, n_tok, inv_denom, gscale=grad_scale)
         self._mark_unexchanged()       # local gradients are added below: whatever exchange a drop-in backward did before is stale
         plan.run_backward(dpred, on_segment=self._bucket_hook() if ((self.world > 1 or self._force_dp) and sync) else None)
         return loss
@@ -301,7 +307,7 @@ class QwenLoraTrainStep:
     def allreduce_grads(self):
         """Returns the factor the optimizer applies to the summed gradient (1/world)."""
         if self.world > 1 or self._force_dp:
-            fin = getattr(self, "_finish_buckets", None)
+            fin = self._finish_buckets
             if fin is not None:
                 fin()
                 self._finish_buckets = None
@@ -321,45 +327,25 @@ class QwenLoraTrainStep:
 
     def optimizer_step(self, grad_scale=1.0):
         st = self.dit.lora_store
-        if self.blockwise:
-            return self._blockwise_step(st, grad_scale)
-        if self._m is None or self._m.numel() != st.pflat.numel() or self._m.device != st.pflat.device:
-            self._m = torch.zeros_like(st.pflat)
-            self._v = torch.zeros_like(st.pflat)
-            self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
+        if self.opt_state is None or self.opt_state.key != self._opt_cls.layout_key(st, self.optimizer_args):
+            self.opt_state = self._opt_cls(st, self.optimizer_args)      # zeroed state of the current layout
         self.global_step += 1
-        if getattr(self, "_gparts", None) is None or self._gparts.device != st.pflat.device:
-            self._gparts = torch.zeros(1024, dtype=torch.float32, device=st.pflat.device)
-        ops.sumsq_det(st.gflat, self._gnorm, self._gparts)     # fixed reduction order: every replica computes the same clip coefficient
-        if self.optimizer == "prodigy":
-            if self._pstate is None or self._ps.numel() != st.pflat.numel():
-                self._ps = torch.zeros_like(st.pflat)
-                self._p0 = st.pflat.detach().clone()     # parameters at the first step() call
-                self._pstate = torch.zeros(L_PRODIGY_STATE, dtype=torch.float64, device=st.pflat.device)
-                ops.prodigy_init_state(self._pstate, self.optimizer_args["d0"])
-            ops.prodigy_step(st.pflat, st.gflat, self._m, self._v, self._ps, self._p0, self._pstate, lr=self.lr, betas=self.betas,
-                             eps=self.eps, weight_decay=self.weight_decay, gnorm_sq=self._gnorm, max_norm=self.max_grad_norm,
-                             grad_scale=grad_scale, **self.optimizer_args)
-            return
-        ops.adamw_step(st.pflat, st.gflat, self._m, self._v, self.lr, self.betas[0], self.betas[1], self.eps,
-                       self.weight_decay, self.global_step, gnorm_sq=self._gnorm, max_norm=self.max_grad_norm,
-                       grad_scale=grad_scale)
-
-    def _ensure_a8(self, st):
-        bs, m8 = self.optimizer_args["blocksize"], self.optimizer_args["min_8bit_size"]
-        if self._a8 is None or self._a8.key != A8.BlockwiseState.layout_key(st, bs, m8):
-            self._a8 = A8.BlockwiseState(st, bs, m8)
         if self._gnorm is None or self._gnorm.device != st.pflat.device:
             self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
-        return self._a8
-
-    def _blockwise_step(self, st, grad_scale):
-        a8 = self._ensure_a8(st)
-        self.global_step += 1
-        if getattr(self, "_gparts", None) is None or self._gparts.device != st.pflat.device:
             self._gparts = torch.zeros(1024, dtype=torch.float32, device=st.pflat.device)
-        ops.sumsq_det(st.gflat, self._gnorm, self._gparts)
-        a8.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm, grad_scale)
+        ops.sumsq_det(st.gflat, self._gnorm, self._gparts)     # fixed reduction order: every replica computes the same clip coefficient
+        self.opt_state.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm,
+                            grad_scale, self.optimizer_args)
+
+    @property
+    def _m(self):
+        """AdamW's / Prodigy's fp32 exp_avg over the flat buffer (read-only; None before the first step and for the 8-bit state)."""
+        return getattr(self.opt_state, "m", None)
+
+    @property
+    def _v(self):
+        """exp_avg_sq, as _m."""
+        return getattr(self.opt_state, "v", None)
 
     def _mark_unexchanged(self):
         dp = getattr(self.dit, "_dp", None)
@@ -372,121 +358,20 @@ class QwenLoraTrainStep:
 
     # ------------------------------------------------------------------ optimizer / resume state (base_trainer.py:827-875,944-1002)
     def state_dict(self):
-        """torch.optim.AdamW-style state: {"state": {i: {"step","exp_avg","exp_avg_sq"}}, "param_groups": [...]} with one entry
-        per LoRA parameter in named_parameters() order (what accelerate's optimizer.bin holds for the reference)."""
+        """{"state": {i: per-parameter state}, "param_groups": [...]} with one entry per LoRA parameter in named_parameters() order
+        (what accelerate's optimizer.bin holds for the reference), in the optimizer's own layout: torch.optim.AdamW's, prodigyopt's
+        or bitsandbytes' (optim_state)."""
         st = self.dit.lora_store
-        state = {}
-        if self.optimizer == "prodigy":
-            return self._prodigy_state_dict()
-        if self.blockwise:
-            return self._blockwise_state_dict()
-        for i, (_, p, off, k) in enumerate(st.entries):
-            if self._m is None:
-                break
-            state[i] = {"step": torch.tensor(float(self.global_step)), "exp_avg": self._m[off:off + k].view(p.shape).detach().cpu().clone(),
-                        "exp_avg_sq": self._v[off:off + k].view(p.shape).detach().cpu().clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
-                 "params": list(range(len(st.entries)))}
+        extra, state = self._opt_cls.save(self.opt_state, st.entries, self.global_step, self.optimizer_args)
+        group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.weight_decay, **extra,
+                     params=list(range(len(st.entries))))
         return {"state": state, "param_groups": [group], "global_step": self.global_step}
-
-    def _blockwise_state_dict(self):
-        """bitsandbytes' Optimizer2State layout: per parameter {"step", "state1", "state2", "qmap1", "qmap2", "absmax1", "absmax2"}
-        (8-bit) or {"step", "state1", "state2"} (fp32 moments, numel < min_8bit_size); the group holds lr, betas, eps, weight_decay."""
-        st = self.dit.lora_store
-        state = {}
-        if self._a8 is not None and self.global_step > 0:
-            for i, (_, p, off, k) in enumerate(st.entries):
-                state[i] = self._a8.param_state(i, p.shape, self.global_step)
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                 "params": list(range(len(st.entries)))}
-        return {"state": state, "param_groups": [group], "global_step": self.global_step}
-
-    def _load_blockwise_state_dict(self, sd):
-        st = self.dit.lora_store
-        g = sd["param_groups"][0]
-        self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
-        step = int(sd.get("global_step", 0))
-        bs, q1, q2 = A8.file_layout(sd["state"], st.entries)
-        if bs is not None:
-            self.optimizer_args["blocksize"] = bs
-        self._a8 = None
-        self._ensure_a8(st)
-        if q1 is not None:
-            self._a8.qmap1.copy_(q1); self._a8.qmap2.copy_(q2)
-        for i in range(len(st.entries)):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
-            self._a8.load_param_state(i, e)
-            step = max(step, int(float(e["step"])))
-        self.global_step = step
-
-    _PS_KEYS = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k")
-
-    def _prodigy_state_dict(self):
-        """prodigyopt layout: per-parameter {"step","s","p0","exp_avg","exp_avg_sq"}; the group carries d, d_max, d_numerator,
-        d_denom, d_hat, k next to the init_args."""
-        st = self.dit.lora_store
-        state = {}
-        group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.weight_decay, **self.optimizer_args)
-        d0 = self.optimizer_args["d0"]
-        group.update(d=d0, d_max=d0, d_numerator=0.0, d_denom=0.0, d_hat=d0, k=0)
-        if self._pstate is not None:
-            vals = self._pstate.cpu().tolist()
-            group.update({n: vals[i] for i, n in enumerate(self._PS_KEYS)})
-            group["k"] = int(group["k"])
-            for i, (_, p, off, k) in enumerate(st.entries):
-                state[i] = {"step": group["k"], "s": self._ps[off:off + k].detach().cpu().clone(),
-                            "p0": self._p0[off:off + k].detach().cpu().clone(),
-                            "exp_avg": self._m[off:off + k].view(p.shape).detach().cpu().clone(),
-                            "exp_avg_sq": self._v[off:off + k].view(p.shape).detach().cpu().clone()}
-        group["params"] = list(range(len(st.entries)))
-        return {"state": state, "param_groups": [group], "global_step": self.global_step}
-
-    def _load_prodigy_state_dict(self, sd):
-        st = self.dit.lora_store
-        g = sd["param_groups"][0]
-        self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
-        for n in self.optimizer_args:
-            if n in g:
-                self.optimizer_args[n] = g[n]
-        self.global_step = int(sd.get("global_step", g.get("k", 0)))
-        self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
-        if not sd["state"]:
-            self._pstate = None
-            return
-        self._m = torch.zeros_like(st.pflat); self._v = torch.zeros_like(st.pflat)
-        self._ps = torch.zeros_like(st.pflat); self._p0 = torch.zeros_like(st.pflat)
-        for i, (_, p, off, k) in enumerate(st.entries):
-            e = sd["state"][i]
-            self._m[off:off + k].copy_(e["exp_avg"].reshape(-1)); self._v[off:off + k].copy_(e["exp_avg_sq"].reshape(-1))
-            self._ps[off:off + k].copy_(e["s"].reshape(-1))
-            if e["p0"].numel() == k:            # the package stores a 0-dim zero for an all-zero parameter
-                self._p0[off:off + k].copy_(e["p0"].reshape(-1))
-        vals = [float(g[n]) for n in self._PS_KEYS] + [0.0] * (L_PRODIGY_STATE - len(self._PS_KEYS))
-        self._pstate = torch.tensor(vals, dtype=torch.float64).to(st.pflat.device)
 
     def load_state_dict(self, sd):
-        if self.optimizer == "prodigy":
-            return self._load_prodigy_state_dict(sd)
-        if self.blockwise:
-            return self._load_blockwise_state_dict(sd)
-        st = self.dit.lora_store
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
-        self._m = torch.zeros_like(st.pflat); self._v = torch.zeros_like(st.pflat)
-        self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
-        step = sd.get("global_step", 0)
-        for i, (_, p, off, k) in enumerate(st.entries):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
-            # a bitsandbytes-layout file (state1 / state2 / absmax / qmap) resumes with its moments dequantised
-            ea, es = (e["exp_avg"], e["exp_avg_sq"]) if "exp_avg" in e else A8.bnb_moments(e)
-            self._m[off:off + k].copy_(ea.reshape(-1).to(self._m.device))
-            self._v[off:off + k].copy_(es.reshape(-1).to(self._v.device))
-            step = max(step, int(float(e["step"])))
-        self.global_step = int(step)
+        self.opt_state, step = self._opt_cls.load(self.dit.lora_store, sd, self.optimizer_args)
+        self.global_step = max(int(sd.get("global_step", g.get("k", 0))), step)    # a package's own file: its group's count k, if any
 
     def save_checkpoint(self, save_dir, extra_state=None):
         """checkpoint-<e>-<step> folder of the reference (base_trainer.py:827-875): pytorch_lora_weights.safetensors (diffusers
@@ -510,70 +395,45 @@ class QwenLoraTrainStep:
 
     # ------------------------------------------------------------------ replica consistency (main.py:58, base_trainer.py:384-393)
     def _state_buffers(self):
-        """Every flat buffer that must be identical on all ranks: adapter weights, then the optimizer's moment / Prodigy buffers."""
-        st = self.dit.lora_store
-        bufs = [("lora", st.pflat)]
-        for name in ("_m", "_v", "_ps", "_p0", "_pstate"):
-            t = getattr(self, name, None)
-            if t is not None:
-                bufs.append((name, t))
-        if self._a8 is not None:
-            bufs += self._a8.buffers()
-        return bufs
+        """Every flat buffer that must be identical on all ranks: adapter weights, then the optimizer state's (None where this rank
+        has no state: the list has the same length on every rank)."""
+        opt = self.opt_state.buffers() if self.opt_state is not None else [(n, None) for n in self._opt_cls.NAMES]
+        return [("lora", self.dit.lora_store.pflat)] + opt
 
     def broadcast_state(self, src: int = 0):
         """Rank `src`'s adapter weights (+ optimizer state, + step count) to every rank: what DDP's constructor does for the
         reference's LoRA container (base_trainer.py:384-393; the reference otherwise relies on equal seeds, main.py:58).  Called
         once before the first step and after load_checkpoint / load_lora_adapter: a resumed or re-injected adapter set must not
-        depend on every rank having read identical files.  Which optimizer buffers exist is agreed on first (rank `src` decides)."""
+        depend on every rank having read identical files.  Whether rank `src` has optimizer state, its step count and the layout
+        ints of its state (optim_state LAYOUT_ARGS) are agreed on first."""
         if self.world <= 1:
             return
-        dev = self.dit.lora_store.pflat.device
-        a8 = self._a8 is not None
-        have = torch.tensor([float(self._m is not None), float(self._pstate is not None), float(self.global_step), float(a8),
-                             float(self.optimizer_args["blocksize"] if a8 else 0), float(self.optimizer_args["min_8bit_size"] if a8 else 0)],
-                            device=dev)
-        dist.broadcast(have, src=src, group=self.group)
-        st = self.dit.lora_store
-        have_m, have_p = bool(have[0].item()), bool(have[1].item())
-        if bool(have[3].item()):       # blockwise 8-bit state: rank `src`'s block size / 8-bit threshold, then its buffers (appended last)
-            self.optimizer_args["blocksize"], self.optimizer_args["min_8bit_size"] = int(have[4].item()), int(have[5].item())
-            self._ensure_a8(st)
+        st, cls = self.dit.lora_store, self._opt_cls
+        head = torch.tensor([int(self.opt_state is not None), self.global_step] + [int(self.optimizer_args[n]) for n in cls.LAYOUT_ARGS],
+                            dtype=torch.int64, device=st.pflat.device)
+        dist.broadcast(head, src=src, group=self.group)
+        have, self.global_step, *ints = head.tolist()
+        # the buffer list is derived from the AGREED header on every rank (same collectives in the same order everywhere): state
+        # rank `src` has is created where missing, state it lacks is dropped locally (a rank that had stepped before must not carry
+        # moments the others do not have)
+        if have:
+            self.optimizer_args.update(zip(cls.LAYOUT_ARGS, ints))
+            if self.opt_state is None or self.opt_state.key != cls.layout_key(st, self.optimizer_args):
+                self.opt_state = cls(st, self.optimizer_args)
         else:
-            self._a8 = None
-        # the buffer list is derived from the AGREED flags on every rank (same collectives in the same order everywhere): buffers
-        # rank `src` has are created where missing, buffers it lacks are dropped locally (a rank that had stepped before must not
-        # carry moments the others do not have)
-        if have_m:
-            if self._m is None or self._m.numel() != st.pflat.numel():
-                self._m, self._v = torch.zeros_like(st.pflat), torch.zeros_like(st.pflat)
-                self._gnorm = torch.zeros((), dtype=torch.float32, device=dev)
-        else:
-            self._m = self._v = None
-        if have_p:
-            if self._pstate is None or self._ps is None or self._ps.numel() != st.pflat.numel():
-                self._ps, self._p0 = torch.zeros_like(st.pflat), torch.zeros_like(st.pflat)
-                self._pstate = torch.zeros(L_PRODIGY_STATE, dtype=torch.float64, device=dev)
-        else:
-            self._ps = self._p0 = self._pstate = None
-        self.global_step = int(have[2].item())
-        bufs = [st.pflat] + ([self._m, self._v] if have_m else []) + ([self._ps, self._p0, self._pstate] if have_p else [])
-        bufs += [t for _, t in self._a8.buffers()] if self._a8 is not None else []
-        for t in bufs:
-            dist.broadcast(t, src=src, group=self.group)
+            self.opt_state = None
+        for _, t in self._state_buffers():
+            if t is not None:
+                dist.broadcast(t, src=src, group=self.group)
 
     def check_replicas(self, what: str = "adapter weights"):
         """Raises if the adapter weights (and optimizer buffers) differ between ranks: two order-sensitive fp64 checksums per
         buffer, gathered and compared on every rank.  Cheap (one small all-gather); call it after loading state and periodically."""
         if self.world <= 1:
             return True
-        st = self.dit.lora_store
-        dev = st.pflat.device
+        dev = self.dit.lora_store.pflat.device
         sums = []
-        a8 = dict(self._a8.buffers()) if self._a8 is not None else {}
-        for name in ("lora", "_m", "_v", "_ps", "_p0", "_pstate", "_a8_q1", "_a8_q2", "_a8_absmax1", "_a8_absmax2", "_a8_m32", "_a8_v32",
-                     "_a8_qmap1", "_a8_qmap2"):      # fixed layout: a buffer a rank lacks is part of the verdict
-            t = st.pflat if name == "lora" else (a8.get(name) if name.startswith("_a8") else getattr(self, name, None))
+        for _, t in self._state_buffers():      # fixed layout: a buffer a rank lacks is part of the verdict
             if t is None:
                 sums += [torch.zeros((), dtype=torch.float64, device=dev)] * 3
                 continue

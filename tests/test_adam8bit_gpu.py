@@ -182,7 +182,7 @@ def test_trainer_blockwise_learns_saves_bnb_layout_and_resumes_bit_identically(t
     assert torch.equal(b.lora_store.pflat.detach().cpu(), want)
 
 
-def test_flux_step_runs_with_blockwise_optimizer():
+def test_flux_step_runs_with_blockwise_optimizer_state():
     from common import FLUX_TINY
     from oracle import flux_dit as FO
     from qflux_amd.models import FluxTransformer2DModel
@@ -204,7 +204,7 @@ def test_flux_step_runs_with_blockwise_optimizer():
     before = m.lora_store.pflat.detach().clone()
     loss = step.train_step(emb, noise=torch.randn(2, 24, 64, generator=g), t=torch.tensor([0.3, 0.8]))
     assert torch.isfinite(loss).all() and not torch.equal(before, m.lora_store.pflat)
-    assert step.state_dict()["state"][0]["step"] == 1 and step._a8.layout.n_absmax > 0
+    assert step.state_dict()["state"][0]["step"] == 1 and step.opt_state.layout.n_absmax > 0
 
 
 @pytest.mark.parametrize("bs", [256, 2048])

@@ -243,14 +243,16 @@ def _worker_broadcast(rank, world, port, q):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from qflux_amd.trainer import QwenLoraTrainStep
+    from qflux_amd.trainer.optim_state import AdamWState
     toy = _toy_model(with_cond=False)
     st = toy.lora_store
     with torch.no_grad():
         st.pflat.copy_(torch.randn(st.pflat.shape, generator=torch.Generator().manual_seed(100 + rank)))
     step = QwenLoraTrainStep(toy)
     if rank == 0:      # only rank 0 carries optimizer state (it loaded optimizer.bin)
-        step._m = torch.full_like(st.pflat, 0.25)
-        step._v = torch.full_like(st.pflat, 0.5)
+        step.opt_state = AdamWState(st, step.optimizer_args)
+        step.opt_state.m.fill_(0.25)
+        step.opt_state.v.fill_(0.5)
         step.global_step = 17
     flagged = False
     try:
@@ -268,8 +270,83 @@ def _worker_broadcast(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_rank0_broadcast_of_adapter_and_optimizer_state_world3():
+def test_rank0_broadcast_of_adapter_and_adamw_state_world3():
     assert _spawn(_worker_broadcast, 3, 35500) == [(0, True), (1, True), (2, True)]
+
+
+def _family_file(optimizer, st):
+    """A resumable optimizer.bin of the toy's adapters after 3 steps, built on the CPU: prodigyopt's layout from the oracle,
+    bitsandbytes' from its restatement (min_8bit_size 100: the 192-element adapters go 8-bit, the 32-element ones keep fp32)."""
+    g = torch.Generator().manual_seed(4)
+    ps = [torch.randn(p.shape, generator=g) * 0.1 for _, p in st.params()]
+    if optimizer == "prodigy":
+        from oracle.prodigy import Prodigy
+        opt = Prodigy(ps, lr=1.0)
+    else:
+        import bnb8_ref as R
+        opt = R.Adam8bitRef(ps, lr=1e-3, min_8bit_size=100)
+    for _ in range(3):
+        opt.step([torch.randn(p.shape, generator=g) for p in ps])
+    if optimizer == "prodigy":
+        return {"state": dict(enumerate(opt.state)), "param_groups": [dict(opt.group, params=list(range(len(ps))))], "global_step": 3}
+    return opt.state_dict()
+
+
+def _worker_family_broadcast(rank, world, port, q, optimizer):
+    """The rank-0 broadcast and the replica check for the Prodigy and the blockwise 8-bit state (_worker_broadcast: AdamW's): rank 0
+    alone resumed a file. check_replicas() must flag that, broadcast_state() must repair it -- the blockwise layout ints (block size,
+    8-bit threshold) included, which the other ranks were built with differently -- and a stray state of a non-src rank is dropped
+    when src has none."""
+    for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "qwen-image-finetune_amd")):
+        sys.path.insert(0, p)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from qflux_amd.trainer import QwenLoraTrainStep
+    toy = _toy_model()
+    st = toy.lora_store
+    with torch.no_grad():
+        st.pflat.copy_(torch.randn(st.pflat.shape, generator=torch.Generator().manual_seed(100 + rank)))
+    sd = _family_file(optimizer, st)
+    blockwise = optimizer != "prodigy"
+    args = ({"min_8bit_size": 100} if rank == 0 else {"blocksize": 2048}) if blockwise else None
+    step = QwenLoraTrainStep(toy, optimizer=optimizer, optimizer_args=args)
+    if rank == 0:
+        step.load_state_dict(sd)
+    flagged = False
+    try:
+        step.check_replicas()
+    except RuntimeError:
+        flagged = True
+    step.broadcast_state()
+    ok = flagged and step.check_replicas() and step.global_step == 3
+    ok = ok and torch.equal(st.pflat, torch.randn(st.pflat.shape, generator=torch.Generator().manual_seed(100)))
+    if blockwise:
+        ok = ok and step.optimizer_args == {"min_8bit_size": 100, "blocksize": 256}
+    out = step.state_dict()
+    ok = ok and list(out["state"]) == list(sd["state"])
+    for i, e in sd["state"].items():
+        o = out["state"][i]
+        ok = ok and list(o) == list(e) and int(o["step"]) == 3
+        ok = ok and all(torch.equal(o[k], v) for k, v in e.items() if torch.is_tensor(v))
+    if not blockwise:
+        ok = ok and all(out["param_groups"][0][k] == sd["param_groups"][0][k] for k in ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k"))
+    # a NON-src rank carries state, src has none: the same collective sequence everywhere, the stray state is dropped
+    step = QwenLoraTrainStep(toy, optimizer=optimizer, optimizer_args={"min_8bit_size": 100} if blockwise else None)
+    if rank == 1:
+        step.load_state_dict(sd)
+    step.broadcast_state()
+    ok = ok and step.state_dict()["state"] == {} and step.global_step == 0 and step.check_replicas()
+    q.put((rank, bool(ok)))
+    dist.destroy_process_group()
+
+
+def test_rank0_broadcast_of_prodigy_state_world2():
+    assert _spawn(_worker_family_broadcast, 2, 39500, extra=("prodigy",)) == [(0, True), (1, True)]
+
+
+def test_rank0_broadcast_of_blockwise_8bit_state_world2():
+    assert _spawn(_worker_family_broadcast, 2, 39700, extra=("adamw8bit_blockwise",)) == [(0, True), (1, True)]
 
 
 def _worker_ragged(rank, world, port, q, root):
@@ -346,6 +423,7 @@ def _worker_advice_r3(rank, world, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from qflux_amd.dp import LoraGradSync
     from qflux_amd.trainer import QwenLoraTrainStep
+    from qflux_amd.trainer.optim_state import AdamWState
     toy = _toy_model(with_cond=False)
     toy._dp = LoraGradSync(toy)            # what dit.enable_data_parallel() installs (add_adapter does it under a process group)
     toy._version = 0
@@ -371,12 +449,13 @@ def _worker_advice_r3(rank, world, port, q):
     ok = ok and toy._dp.exchanged is False
     # (b) a NON-src rank carries moments, src has none: same collective sequence everywhere, the stray buffers are dropped
     if rank == 1:
-        step._m = torch.full_like(st.pflat, 3.0)
-        step._v = torch.full_like(st.pflat, 4.0)
+        step.opt_state = AdamWState(st, step.optimizer_args)
+        step.opt_state.m.fill_(3.0)
+        step.opt_state.v.fill_(4.0)
     with torch.no_grad():
         st.pflat.fill_(float(10 + rank))
     step.broadcast_state()
-    ok = ok and step._m is None and step._v is None and bool(st.pflat.eq(10.0).all())
+    ok = ok and step.opt_state is None and step._m is None and step._v is None and bool(st.pflat.eq(10.0).all())
     ok = ok and step.check_replicas()
     # (c) _ensure_synced: once per model version
     step._synced = False
@@ -403,5 +482,5 @@ def _worker_advice_r3(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_advice_r3_exchange_flag_broadcast_symmetry_and_resync_world2():
+def test_advice_r3_exchange_flag_broadcast_symmetry_and_resync_of_opt_state_world2():
     assert _spawn(_worker_advice_r3, 2, 37500) == [(0, True), (1, True)]

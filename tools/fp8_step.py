@@ -27,7 +27,7 @@ for mode_ in modes:
     os.environ["QFX_FP8_FUSED_QUANT"] = "0" if opt == "unfused" else "1"
     dit.quantize_trunk(None if mode == "none" else mode)
     # every mode starts from the same adapter weights / optimizer state and sees the same noise: losses are comparable
-    dit.lora_store.pflat.copy_(p0); step._m = None; step.global_step = 0
+    dit.lora_store.pflat.copy_(p0); step.opt_state = None; step.global_step = 0
     torch.manual_seed(7)
     ms, l = t()
     mode = mode_
