@@ -468,6 +468,21 @@ int qfx_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, floa
                    float eps, float weight_decay, float bias_corr1, float bias_corr2,
                    const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale, void* stream);
 
+/* ---- torch.optim.SGD, the fourth optimizer the reference documents (docs/guide/training.md:768-826, configuration.md:67,163-166:
+ * momentum 0.9, weight_decay 1e-4; instantiated generically at base_trainer.py:884-909, stepped at :531 after clip_gradients
+ * :449-455).  ONE launch over the flat fp32 LoRA buffers.  With clip exactly as qfx_adamw_step computes it from gnorm_sq / max_norm /
+ * grad_scale (gnorm_sq == NULL or max_norm <= 0: clip = grad_scale), per element:
+ *   gi = g * clip + weight_decay * p                            (L2 form; the clip comes first, as clip_grad_norm_ precedes step())
+ *   momentum != 0:  buf = first ? gi : momentum * buf + (1 - dampening) * gi       (torch's first step applies no dampening)
+ *                   gi  = nesterov ? gi + momentum * buf : buf
+ *   p -= lr * gi
+ * buf [n] may be NULL iff momentum == 0 (it is then neither read nor written); `first` != 0 on the step that creates buf (its
+ * contents are then ignored).  No atomics: same inputs -> same bits.  Rejected with QFX_EINVAL before any launch: a NULL p or g,
+ * n <= 0, a NULL buf with momentum != 0, nesterov with momentum <= 0 or dampening != 0 (torch's ValueError). ---- */
+int qfx_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening, float weight_decay,
+                 int32_t nesterov, int32_t first, const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale,
+                 void* stream);
+
 /* ---- Prodigy, the reference's parameter-free optimizer choice (third party prodigyopt.Prodigy, requirements.txt:33; selected by
  * configs/face_seg_flux_kontext_fp16_prodigy.yaml:41-47 and the optimizer section of every tests/test_configs/test_example_*.yaml;
  * instantiated generically at base_trainer.py:884-898, stepped at :531 after clip_gradients :449-455).  One fused step over the

@@ -798,6 +798,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// torch.optim.SGD over the flat LoRA buffers after adamw_kernel's clip prologue (include/qfx.h).  buf is never touched when mom == 0.
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  int64_t n, float lr, float mom, float damp, float wd, int nesterov, int first,
+                                                  const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
+  float clip = grad_scale;
+  if (gnorm_sq != nullptr && max_norm > 0.f) {
+    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
+    const float c = max_norm / (nrm + 1e-6f);
+    clip *= c < 1.0f ? c : 1.0f;
+  }
+  const float keep = 1.0f - damp;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float pi = p[i];
+    float gi = g[i] * clip;
+    if (wd != 0.f) gi += wd * pi;
+    if (mom != 0.f) {
+      const float bi = first ? gi : mom * buf[i] + keep * gi;
+      buf[i] = bi;
+      gi = nesterov ? gi + mom * bi : bi;
+    }
+    p[i] = pi - lr * gi;
+  }
+}
+
 // ---- Prodigy (prodigyopt 1.x, Adam variant) over the flat LoRA buffers: see include/qfx.h.  Host scalars of the package (Python
 // float64: d, d_max, d_numerator, d_denom, k) live in a device double[QFX_PRODIGY_STATE] so the step never synchronises.
 enum { PS_D = 0, PS_DMAX, PS_NUM, PS_DEN, PS_DHAT, PS_K, PS_ACC_NUM, PS_ACC_DEN, PS_DLR, PS_SKIP };
@@ -1407,6 +1431,20 @@ extern "C" int qfx_adamw_step(float* p, const float* g, float* m, float* v, int6
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                      weight_decay, bias_corr1, bias_corr2, gnorm_sq, max_norm, grad_scale);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int qfx_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening,
+                            float weight_decay, int32_t nesterov, int32_t first, const float* gnorm_sq, float max_norm,
+                            float grad_scale, void* stream) {
+  if (!p || !g || n <= 0) return QFX_EINVAL;
+  if (!buf && momentum != 0.f) return QFX_EINVAL;
+  if (nesterov && (!(momentum > 0.f) || dampening != 0.f)) return QFX_EINVAL;
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, momentum, dampening,
+                     weight_decay, nesterov, first, gnorm_sq, max_norm, grad_scale);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

@@ -223,6 +223,7 @@ SYMBOLS = {
     "qfx_sumsq": (C.c_int, [_vp, _i64, _vp, _vp]),
     "qfx_sumsq_det": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp]),
     "qfx_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _vp, _f, _f, _vp]),
+    "qfx_sgd_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _i32, _i32, _vp, _f, _f, _vp]),
     "qfx_prodigy_init_state": (C.c_int, [_vp, C.c_double, _vp]),
     "qfx_prodigy_step": (C.c_int, [C.POINTER(ProdigyArgs), _vp]),
     "qfx_adam8bit_step": (C.c_int, [C.POINTER(Adam8bitArgs), _vp]),

@@ -322,6 +322,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._hf_peft_config_loaded = True
         self._invalidate()
         self._adapter_gen += 1
+        self._lora.tag()
         # The reference wraps its LoRA container in DDP right after this call (base_trainer.py:384-393); the kernels write dA / dB
         # straight into the flat gradient buffer, so the model exchanges them itself.  Under an initialised multi-rank process
         # group that happens without an extra line in the trainer (no-op otherwise; call enable_data_parallel(...) again to
@@ -405,6 +406,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         names = load_lora_adapter(self, path, adapter_name, lora_alpha)
         self._invalidate()
         self._adapter_gen += 1
+        self._lora.tag()
         return names
 
     def quantize_trunk(self, mode: str | None = "mxfp8"):

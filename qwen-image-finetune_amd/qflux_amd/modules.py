@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 import re
+import weakref
 
 import torch
 import torch.nn as nn
@@ -115,6 +116,19 @@ def match_target(name: str, target_modules) -> bool:
     return any(name == t or name.endswith("." + t) for t in target_modules)
 
 
+class _StoreRef:
+    """Weak back-reference from a packed parameter to its LoraStore; a pickled or copied parameter carries a dead one."""
+
+    def __init__(self, store=None):
+        self._ref = weakref.ref(store) if store is not None else None
+
+    def __call__(self):
+        return self._ref() if self._ref is not None else None
+
+    def __reduce__(self):
+        return (_StoreRef, ())
+
+
 class LoraStore:
     """Flat fp32 parameter / gradient buffers for every adapter weight of a model."""
 
@@ -126,6 +140,12 @@ class LoraStore:
 
     def params(self):
         return [(n, p) for n, p in self.model.named_parameters() if "lora_" in n]
+
+    def tag(self) -> None:
+        """Back-reference on every adapter parameter: how qflux_amd.optim finds the store of the parameters it is given.  Set when
+        adapters are injected (the reference builds its optimizer before the first forward packs them) and when the store packs."""
+        for _, p in self.params():
+            p._lora_store = _StoreRef(self)
 
     def rebuild(self, device=None) -> None:
         """(Re)pack all adapter params into one flat buffer on `device`, keeping values and Parameter identity."""
@@ -151,6 +171,7 @@ class LoraStore:
             entries.append((n, p, off, k))
             off += (k + 63) // 64 * 64
         self.pflat, self.gflat, self.entries = pflat, gflat, entries
+        self.tag()
 
     def is_consistent(self, device) -> bool:
         if self.pflat is None:

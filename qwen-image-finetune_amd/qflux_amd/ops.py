@@ -341,6 +341,14 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, gnorm_sq=None, max_n
                                grad_scale, stream_ptr()), "qfx_adamw_step")
 
 
+def sgd_step(p, g, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False, gnorm_sq=None, max_norm=0.0,
+             grad_scale=1.0):
+    """One torch.optim.SGD step over the flat buffers p / g (qfx.h); buf: the momentum buffer, None iff momentum == 0; first: buf is
+    created by this step (buf = the decayed gradient, no dampening)."""
+    L.check(lib.qfx_sgd_step(_p(p), _p(g), _p(buf), p.numel(), lr, momentum, dampening, weight_decay, int(bool(nesterov)),
+                             int(bool(first)), _p(gnorm_sq), max_norm, grad_scale, stream_ptr()), "qfx_sgd_step")
+
+
 class Adam8bitLayout:
     """Block table of one flat-buffer layout for qfx_adam8bit_step, built once per layout.  `tensors[i]` = (off, numel, eight_bit,
     first absmax index, number of absmax blocks, first element in the fp32 moment buffers) of entry i."""

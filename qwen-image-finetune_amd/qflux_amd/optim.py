@@ -1,0 +1,167 @@
+"""The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
+
+BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD) that optimizer is one of the classes below and
+`optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
+class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
+and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
+the two ways of driving the model and with the original packages'.
+
+`params` must be exactly the adapter parameters of ONE model, in one group.  The loop has clipped already
+(accelerator.clip_grad_norm_, base_trainer.py:449-455), so step() launches without the fused clip; lr, betas, eps, weight_decay and
+momentum are read from param_groups[0] at every step (schedulers write there).  step() never synchronises with the host.
+"""
+from __future__ import annotations
+
+import torch
+
+from .trainer import optim_state as OS
+from .trainer.qwen_step import optimizer_kwargs_from_config
+
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD"]
+
+
+def _find_store(param_groups):
+    """The LoraStore whose parameters are exactly those of the one group; ValueError naming the first offender otherwise."""
+    if len(param_groups) != 1:
+        raise ValueError(f"{len(param_groups)} parameter groups: the fused step runs over one model's adapter parameters in ONE group "
+                         "(parameter group 1 is the first offender)")
+    params, store = param_groups[0]["params"], None
+    for i, p in enumerate(params):
+        ref = getattr(p, "_lora_store", None)
+        st = ref() if ref is not None else None
+        if st is None:
+            raise ValueError(f"parameter {i} (shape {tuple(p.shape)}) is not an adapter parameter of a qflux_amd model")
+        if store is not None and st is not store:
+            raise ValueError(f"parameter {i} (shape {tuple(p.shape)}) belongs to another model than parameter 0: one optimizer steps one "
+                             "model's adapters")
+        store = st
+    if store is None:
+        raise ValueError("no parameters")
+    have = {id(p) for p in params}
+    for n, p in store.params():
+        if id(p) not in have:
+            raise ValueError(f"adapter parameter {n!r} of the model is missing: stepping a subset of the adapter set is not supported")
+    return store
+
+
+class _FlatOptimizer(torch.optim.Optimizer):
+    _PATH = None       # the class path optimizer_kwargs_from_config knows this class by
+
+    def __init__(self, params, _own_args=None, **init_args):
+        """init_args: the stood-in class's keywords, mapped (and refused) as the YAML's are; _own_args: optimizer_args beyond them."""
+        kw = optimizer_kwargs_from_config(self._PATH, init_args)
+        _, self.family, self._cls, wd, self._args = OS.resolve_family(kw["optimizer"], kw.get("weight_decay"),
+                                                                      dict(kw.get("optimizer_args") or {}, **(_own_args or {})) or None)
+        # the family's own group fields (SGD's momentum, Prodigy's init_args) are visible in the group, as in the package's
+        own = {n: v for n, v in self._args.items() if n in self._cls.save(None, [], 0, self._args)[0]}
+        super().__init__(params, dict(lr=kw["lr"], betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-8), weight_decay=wd, **own))
+        self._raw_store = _find_store(self.param_groups)
+        self._opt_state = None
+        self._step_count_fused = 0
+
+    def _store(self):
+        """The model's store through its `lora_store` property: packed on the model's current device, gradient views attached (the
+        set-to-none zero_grad drops them; accelerator.prepare() / .to() move the module)."""
+        return getattr(self._raw_store.model, "lora_store", self._raw_store)
+
+    def _group(self):
+        g = self.param_groups[0]
+        for n in self._args:
+            if n in g:
+                self._args[n] = g[n]
+        return g
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g, st = self._group(), self._store()
+        st.ensure_grads()
+        if self._opt_state is None or self._opt_state.key != self._cls.layout_key(st, self._args):
+            self._opt_state = self._cls(st, self._args)      # zeroed state of the current layout
+        self._step_count_fused += 1
+        self._opt_state.step(st, g["lr"], g["betas"], g["eps"], g["weight_decay"], self._step_count_fused, None, 0.0, 1.0, self._args)
+        return loss
+
+    def state_dict(self):
+        g = self._group()
+        return OS.state_dict(self._cls, self._opt_state, self._store(), self._step_count_fused, self._args, g["lr"], g["betas"], g["eps"],
+                             g["weight_decay"])
+
+    def load_state_dict(self, state_dict):
+        g = self._group()
+        hyper = {n: g[n] for n in ("lr", "betas", "eps", "weight_decay")}
+        self._opt_state, self._step_count_fused = OS.load_state_dict(self._cls, self._store(), state_dict, self._args, hyper)
+        g.update(hyper)
+        g.update({n: v for n, v in self._args.items() if n in g})
+
+
+class AdamW(_FlatOptimizer):
+    """torch.optim.AdamW (fp32 moments, decoupled weight decay)."""
+    _PATH = "qflux_amd.optim.AdamW"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        if amsgrad or maximize or differentiable:
+            raise NotImplementedError("amsgrad / maximize / differentiable are not implemented by the fused AdamW step")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+
+class Adam(_FlatOptimizer):
+    """torch.optim.Adam with weight_decay 0 (its L2 decay is not implemented: QwenLoraTrainStep(optimizer="adam"))."""
+    _PATH = "qflux_amd.optim.Adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        if amsgrad or maximize or differentiable:
+            raise NotImplementedError("amsgrad / maximize / differentiable are not implemented by the fused Adam step")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+
+class Adam8bit(_FlatOptimizer):
+    """bitsandbytes.optim.Adam8bit: blockwise 8-bit moments in bitsandbytes' state layout (trainer/adam8bit.py).  blocksize (256 or
+    2048) is this class's own keyword; a file brings its own."""
+    _PATH = "qflux_amd.optim.Adam8bit"
+    _WD = 0.0
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, amsgrad=False, optim_bits=32, args=None,
+                 min_8bit_size=4096, percentile_clipping=100, block_wise=True, is_paged=False, *, blocksize=256):
+        if args is not None:
+            raise NotImplementedError("bitsandbytes' `args` override object is not supported")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=self._WD if weight_decay is None else weight_decay,
+                         amsgrad=amsgrad, optim_bits=optim_bits, min_8bit_size=min_8bit_size, percentile_clipping=percentile_clipping,
+                         block_wise=block_wise, is_paged=is_paged, _own_args={"blocksize": blocksize})
+
+
+class AdamW8bit(Adam8bit):
+    """bitsandbytes.optim.AdamW8bit: Adam8bit with weight_decay 1e-2 by default."""
+    _PATH = "qflux_amd.optim.AdamW8bit"
+    _WD = 1e-2
+
+
+class Prodigy(_FlatOptimizer):
+    """prodigyopt.Prodigy (decoupled weight decay only)."""
+    _PATH = "qflux_amd.optim.Prodigy"
+
+    def __init__(self, params, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0, decouple=True, use_bias_correction=False,
+                 safeguard_warmup=False, d0=1e-6, d_coef=1.0, growth_rate=float("inf"), fsdp_in_use=False, slice_p=1):
+        if fsdp_in_use or slice_p != 1:
+            raise NotImplementedError("fsdp_in_use / slice_p are not implemented by the fused Prodigy step")
+        super().__init__(params, lr=lr, betas=betas, beta3=beta3, eps=eps, weight_decay=weight_decay, decouple=decouple,
+                         use_bias_correction=use_bias_correction, safeguard_warmup=safeguard_warmup, d0=d0, d_coef=d_coef,
+                         growth_rate=growth_rate)
+
+
+class SGD(_FlatOptimizer):
+    """torch.optim.SGD (momentum, dampening, Nesterov, L2 weight decay)."""
+    _PATH = "qflux_amd.optim.SGD"
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, foreach=None,
+                 differentiable=False, fused=None):
+        if differentiable:
+            raise NotImplementedError("differentiable is not implemented by the fused SGD step")
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                         maximize=maximize)

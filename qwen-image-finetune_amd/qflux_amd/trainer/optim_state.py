@@ -1,9 +1,9 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
-file layout), ProdigyState (prodigyopt.Prodigy's) and BlockwiseState (bitsandbytes' blockwise 8-bit).  QwenLoraTrainStep
-holds one of them and knows only their common surface:
+file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit) and SgdState (torch.optim.SGD's).
+QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
-  NAMES / buffers()              fixed, ordered (name, tensor) list that broadcast_state sends and check_replicas sums
+  cls.names(args) / buffers()    fixed, ordered (name, tensor) list that broadcast_state sends and check_replicas sums
   step(store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args)   the family's one step launch
   cls.save(state, entries, step, args) -> (extra param-group fields, per-parameter state); state may be None (no step yet)
   cls.load(store, sd, args) -> (state or None, highest per-parameter step the family reads, else 0)"""
@@ -31,6 +31,11 @@ class FlatState:
     @classmethod
     def layout_key(cls, store, args):
         return (tuple((off, k) for _, _, off, k in store.entries), str(store.pflat.device)) + tuple(int(args[n]) for n in cls.LAYOUT_ARGS)
+
+    @classmethod
+    def names(cls, args):
+        """The buffer names of a state built with `args`: what a rank without state lists in their place."""
+        return cls.NAMES
 
     def buffers(self):
         return [(n, getattr(self, n)) for n in self.NAMES]
@@ -205,3 +210,130 @@ class BlockwiseState(FlatState):
             state.load_param_state(i, e)
             step = max(step, int(float(e["step"])))
         return state, step
+
+
+class SgdState(FlatState):
+    """torch.optim.SGD: one momentum buffer indexed like pflat, only when momentum != 0.  `first` marks the step that creates the
+    buffer (torch: buf = the decayed gradient, no dampening); a state that was loaded or received from another rank has stepped."""
+    NAMES = ("buf",)
+    DEFAULTS = dict(momentum=0.0, dampening=0.0, nesterov=False)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.buf = torch.zeros_like(store.pflat) if args["momentum"] != 0 else None
+        self.first = True
+
+    @classmethod
+    def layout_key(cls, store, args):
+        return super().layout_key(store, args) + (args["momentum"] != 0,)
+
+    @classmethod
+    def names(cls, args):
+        return cls.NAMES if args["momentum"] != 0 else ()
+
+    @staticmethod
+    def validate(args):
+        """torch.optim.SGD's constructor checks."""
+        if args["momentum"] < 0.0:
+            raise ValueError(f"Invalid momentum value: {args['momentum']}")
+        if args["nesterov"] and (args["momentum"] <= 0 or args["dampening"] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+    def buffers(self):
+        self.first = False            # listed for a broadcast or a replica check: the state of a run that has stepped
+        return [("buf", self.buf)] if self.buf is not None else []
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        ops.sgd_step(store.pflat, store.gflat, self.buf, lr, args["momentum"], args["dampening"], weight_decay, args["nesterov"],
+                     first=self.first, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+        self.first = False
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """torch.optim.SGD's layout: per parameter {"momentum_buffer"} (no state without momentum or before the first step); the
+        group carries momentum, dampening, nesterov, maximize."""
+        group = dict(momentum=args["momentum"], dampening=args["dampening"], nesterov=args["nesterov"], maximize=False)
+        if state is None or state.buf is None or state.first:
+            return group, {}
+        return group, {i: {"momentum_buffer": _out(state.buf, off, k, p.shape)} for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        g = sd["param_groups"][0]
+        if g.get("maximize", False):
+            raise NotImplementedError("SGD with maximize=True")
+        for n in cls.DEFAULTS:
+            if n in g:
+                args[n] = g[n]
+        cls.validate(args)
+        if not sd["state"] or args["momentum"] == 0:
+            return None, 0
+        state = cls(store, args)
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is not None and e.get("momentum_buffer") is not None:
+                state.buf[off:off + k].copy_(e["momentum_buffer"].reshape(-1))
+        state.first = False
+        return state, 0
+
+
+def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
+    """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
+    state class, weight decay, the family's optimizer_args with defaults filled in)."""
+    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd") + A8.BLOCKWISE:
+        raise ValueError(f"unknown optimizer {optimizer!r}")
+    alias = None
+    # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / SGD; Prodigy
+    # keeps its explicit value (the reference's Prodigy configs pass 0.01).  An EXPLICIT value is never reinterpreted.
+    if optimizer in ("adam", "adam8bit"):
+        # bitsandbytes.optim.Adam8bit -- what most of the reference's YAMLs select (configs/face_seg_config.yaml:56-59:
+        # lr + betas only) -- is Adam with blockwise 8-bit quantised moments, a device to fit 24-48 GB cards.  The LoRA state
+        # here is 2 x 94 MB of fp32 next to 288 GB of HBM: the moments stay fp32 (strictly closer to exact Adam than the 8-bit
+        # code book; optimizer.bin then holds fp32 exp_avg / exp_avg_sq in torch.optim.Adam's layout, not bnb's state1 / state2 /
+        # absmax blocks; "adam8bit_blockwise" keeps those).  torch.optim.Adam's weight decay is the L2 form (added to the
+        # gradient); bnb's 8-bit Adam decays decoupled, after the update (adam8bit_blockwise).  Only the configs' weight_decay = 0
+        # is mapped here.
+        if weight_decay is not None and float(weight_decay) != 0.0:
+            raise NotImplementedError(f"{optimizer} with L2 weight decay {weight_decay} (bnb adds wd * p to the gradient; the fused "
+                                      "kernel implements AdamW's decoupled form only; the reference's configs use none)")
+        weight_decay = 0.0
+        alias, optimizer = optimizer, "adamw"
+    if weight_decay is None:
+        weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
+    blockwise = optimizer in A8.BLOCKWISE
+    cls = BlockwiseState if blockwise else {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState}[optimizer]
+    if blockwise:
+        args = dict(min_8bit_size=4096, blocksize=256)
+    elif optimizer == "sgd":
+        args = dict(SgdState.DEFAULTS)
+    else:
+        args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
+                    growth_rate=float("inf"))
+    unknown = set(optimizer_args or {}) - set(args)
+    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd") + A8.BLOCKWISE):
+        raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
+    args.update(optimizer_args or {})
+    if blockwise:
+        if args["blocksize"] not in A8.BLOCKSIZES or int(args["min_8bit_size"]) < 1:
+            raise ValueError(f"{optimizer}: blocksize must be one of {A8.BLOCKSIZES} and min_8bit_size >= 1 ({args})")
+        args["min_8bit_size"] = int(args["min_8bit_size"])
+    if optimizer == "sgd":
+        SgdState.validate(args)
+    return alias, optimizer, cls, weight_decay, args
+
+
+def state_dict(cls, state, store, step, args, lr, betas, eps, weight_decay):
+    """{"state": {i: per-parameter state}, "param_groups": [...], "global_step"} with one entry per LoRA parameter in
+    named_parameters() order (what accelerate's optimizer.bin holds for the reference), in the family's own layout."""
+    extra, per = cls.save(state, store.entries, step, args)
+    group = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, **extra, params=list(range(len(store.entries))))
+    return {"state": per, "param_groups": [group], "global_step": step}
+
+
+def load_state_dict(cls, store, sd, args, hyper):
+    """Inverse of state_dict: updates args and hyper (lr, betas, eps, weight_decay; a family without betas / eps, such as
+    torch.optim.SGD's own file, keeps the current values) in place and returns (state or None, step count)."""
+    g = sd["param_groups"][0]
+    hyper.update(lr=g["lr"], betas=tuple(g.get("betas", hyper["betas"])), eps=g.get("eps", hyper["eps"]), weight_decay=g["weight_decay"])
+    state, step = cls.load(store, sd, args)
+    return state, max(int(sd.get("global_step", g.get("k", 0))), step)    # a package's own file: its group's count k, if any

@@ -22,7 +22,8 @@ import torch.distributed as dist
 
 from .. import ops
 from . import adam8bit as A8
-from .optim_state import AdamWState, BlockwiseState, ProdigyState
+from . import optim_state as OS
+from .optim_state import resolve_family
 
 BF = torch.bfloat16
 
@@ -57,45 +58,15 @@ class QwenLoraTrainStep:
         "adam8bit_blockwise" / "adamw8bit_blockwise": bitsandbytes.optim.Adam8bit / AdamW8bit with their blockwise 8-bit moments and
         state layout (trainer/adam8bit.py; weight decay decoupled, defaults 0 / 1e-2); optimizer_args: min_8bit_size (4096), blocksize
         (256 or 2048).
+        "sgd": torch.optim.SGD, the fourth optimizer the reference documents (docs/guide/training.md:768-826: momentum 0.9, weight_decay
+        1e-4; weight decay in the L2 form, default 0); optimizer_args: momentum (0), dampening (0), nesterov (False); betas / eps unused.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
-        if optimizer not in ("adamw", "adam", "adam8bit", "prodigy") + A8.BLOCKWISE:
-            raise ValueError(f"unknown optimizer {optimizer!r}")
-        # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / Prodigy
-        # keeps its explicit value (the reference's Prodigy configs pass 0.01).  An EXPLICIT value is never reinterpreted.
-        if optimizer in ("adam", "adam8bit"):
-            # bitsandbytes.optim.Adam8bit -- what most of the reference's YAMLs select (configs/face_seg_config.yaml:56-59:
-            # lr + betas only) -- is Adam with blockwise 8-bit quantised moments, a device to fit 24-48 GB cards.  The LoRA state
-            # here is 2 x 94 MB of fp32 next to 288 GB of HBM: the moments stay fp32 (strictly closer to exact Adam than the 8-bit
-            # code book; optimizer.bin then holds fp32 exp_avg / exp_avg_sq in torch.optim.Adam's layout, not bnb's state1 / state2 /
-            # absmax blocks; "adam8bit_blockwise" keeps those).  torch.optim.Adam's weight decay is the L2 form (added to the
-            # gradient); bnb's 8-bit Adam decays decoupled, after the update (adam8bit_blockwise).  Only the configs' weight_decay = 0
-            # is mapped here.
-            if weight_decay is not None and float(weight_decay) != 0.0:
-                raise NotImplementedError(f"{optimizer} with L2 weight decay {weight_decay} (bnb adds wd * p to the gradient; the fused "
-                                          "kernel implements AdamW's decoupled form only; the reference's configs use none)")
-            weight_decay = 0.0
-            self.optimizer_alias, optimizer = optimizer, "adamw"
-        if weight_decay is None:
-            weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
-        self.optimizer = optimizer
+        self.optimizer_alias, self.optimizer, self._opt_cls, weight_decay, self.optimizer_args = resolve_family(optimizer, weight_decay,
+                                                                                                                optimizer_args)
         self.blockwise = optimizer in A8.BLOCKWISE
-        self._opt_cls = BlockwiseState if self.blockwise else {"adamw": AdamWState, "prodigy": ProdigyState}[optimizer]
-        if self.blockwise:
-            self.optimizer_args = dict(min_8bit_size=4096, blocksize=256)
-        else:
-            self.optimizer_args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6,
-                                       d_coef=1.0, growth_rate=float("inf"))
-        unknown = set(optimizer_args or {}) - set(self.optimizer_args)
-        if unknown or (optimizer_args and optimizer not in ("prodigy",) + A8.BLOCKWISE):
-            raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
-        self.optimizer_args.update(optimizer_args or {})
-        if self.blockwise:
-            if self.optimizer_args["blocksize"] not in A8.BLOCKSIZES or int(self.optimizer_args["min_8bit_size"]) < 1:
-                raise ValueError(f"{optimizer}: blocksize must be one of {A8.BLOCKSIZES} and min_8bit_size >= 1 ({self.optimizer_args})")
-            self.optimizer_args["min_8bit_size"] = int(self.optimizer_args["min_8bit_size"])
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
         self.dit = dit
@@ -361,17 +332,13 @@ class QwenLoraTrainStep:
         """{"state": {i: per-parameter state}, "param_groups": [...]} with one entry per LoRA parameter in named_parameters() order
         (what accelerate's optimizer.bin holds for the reference), in the optimizer's own layout: torch.optim.AdamW's, prodigyopt's
         or bitsandbytes' (optim_state)."""
-        st = self.dit.lora_store
-        extra, state = self._opt_cls.save(self.opt_state, st.entries, self.global_step, self.optimizer_args)
-        group = dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.weight_decay, **extra,
-                     params=list(range(len(st.entries))))
-        return {"state": state, "param_groups": [group], "global_step": self.global_step}
+        return OS.state_dict(self._opt_cls, self.opt_state, self.dit.lora_store, self.global_step, self.optimizer_args, self.lr, self.betas,
+                             self.eps, self.weight_decay)
 
     def load_state_dict(self, sd):
-        g = sd["param_groups"][0]
-        self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
-        self.opt_state, step = self._opt_cls.load(self.dit.lora_store, sd, self.optimizer_args)
-        self.global_step = max(int(sd.get("global_step", g.get("k", 0))), step)    # a package's own file: its group's count k, if any
+        hyper = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+        self.opt_state, self.global_step = OS.load_state_dict(self._opt_cls, self.dit.lora_store, sd, self.optimizer_args, hyper)
+        self.lr, self.betas, self.eps, self.weight_decay = hyper["lr"], hyper["betas"], hyper["eps"], hyper["weight_decay"]
 
     def save_checkpoint(self, save_dir, extra_state=None):
         """checkpoint-<e>-<step> folder of the reference (base_trainer.py:827-875): pytorch_lora_weights.safetensors (diffusers
@@ -397,7 +364,7 @@ class QwenLoraTrainStep:
     def _state_buffers(self):
         """Every flat buffer that must be identical on all ranks: adapter weights, then the optimizer state's (None where this rank
         has no state: the list has the same length on every rank)."""
-        opt = self.opt_state.buffers() if self.opt_state is not None else [(n, None) for n in self._opt_cls.NAMES]
+        opt = self.opt_state.buffers() if self.opt_state is not None else [(n, None) for n in self._opt_cls.names(self.optimizer_args)]
         return [("lora", self.dit.lora_store.pflat)] + opt
 
     def broadcast_state(self, src: int = 0):
@@ -471,6 +438,10 @@ class QwenLoraTrainStep:
         return loss
 
 
+# qflux_amd.optim class -> (the class it stands in for, the state_bits it implies)
+_OWN_CLASSES = {"qflux_amd.optim.AdamW": ("torch.optim.AdamW", 32), "qflux_amd.optim.Adam": ("torch.optim.Adam", 32),
+                "qflux_amd.optim.Adam8bit": ("bitsandbytes.optim.Adam8bit", 8), "qflux_amd.optim.AdamW8bit": ("bitsandbytes.optim.AdamW8bit", 8),
+                "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0)}
 _BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
              "bitsandbytes.optim.PagedAdamW8bit")
 
@@ -486,11 +457,19 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     with bnb's state layout instead: "adam8bit_blockwise" (weight decay default 0) / "adamw8bit_blockwise" (default 1e-2), min_8bit_size
     honoured; percentile_clipping != 100, max_unorm != 0, block_wise=False, skip_zeros=True and amsgrad=True are refused; is_paged only
     moves memory (same math).  state_bits=32 is the mapping above.
+    The torch.optim classes of qflux_amd.optim (the drop-in loop's optimizers) map to the family each of them runs, whatever state_bits
+    says: AdamW -> "adamw", Adam -> "adam", Adam8bit / AdamW8bit -> "adam8bit_blockwise" / "adamw8bit_blockwise" (the class is named for
+    its state), Prodigy -> "prodigy", SGD -> "sgd" + optimizer_args (momentum, dampening, nesterov; maximize is refused).
+    torch.optim.SGD itself is not mapped.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
     a = dict(init_args or {})
     name = class_path.rsplit(".", 1)[-1]
+    given = class_path
+    if class_path in _OWN_CLASSES:
+        class_path, bits = _OWN_CLASSES[class_path]
+        state_bits = bits or state_bits
     out = {}
     for k in ("lr", "eps", "weight_decay"):
         if k in a:
@@ -505,7 +484,7 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
                    "block_wise": (True, "non-blockwise 8-bit state"), "skip_zeros": (False, "skip_zeros"), "amsgrad": (False, "amsgrad")}
         for k, (ok, what) in refused.items():
             if k in a and a.pop(k) != ok:
-                raise NotImplementedError(f"{class_path}: {what} is not implemented by the blockwise 8-bit step ({k} must be {ok!r})")
+                raise NotImplementedError(f"{given}: {what} is not implemented by the blockwise 8-bit step ({k} must be {ok!r})")
         if "min_8bit_size" in a:
             out["optimizer_args"] = {"min_8bit_size": int(a.pop("min_8bit_size"))}
         a.pop("is_paged", None)        # paged memory: where the state lives, not what is computed
@@ -515,6 +494,12 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     elif class_path in ("torch.optim.Adam", "bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.Adam", "bitsandbytes.optim.PagedAdam8bit"):
         out["optimizer"] = "adam8bit" if "8bit" in name else "adam"
         out.setdefault("weight_decay", 0.0)
+    elif given == "qflux_amd.optim.SGD":
+        out["optimizer"] = "sgd"
+        if a.pop("maximize", False):
+            raise NotImplementedError(f"{given}: maximize=True is not implemented")
+        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("momentum", "dampening", "nesterov")}
+        a.pop("differentiable", None)
     elif class_path == "prodigyopt.Prodigy":
         out["optimizer"] = "prodigy"
         out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("beta3", "decouple", "use_bias_correction", "safeguard_warmup", "d0",
@@ -524,7 +509,7 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     for k in ("min_8bit_size", "percentile_clipping", "block_wise", "optim_bits", "is_paged", "amsgrad", "foreach", "fused"):
         a.pop(k, None)       # knobs of the 8-bit state / torch dispatch: no meaning for the fused fp32 step
     if a:
-        raise NotImplementedError(f"unsupported optimizer init_args for {class_path}: {sorted(a)}")
+        raise NotImplementedError(f"unsupported optimizer init_args for {given}: {sorted(a)}")
     return out
 
 
