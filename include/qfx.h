@@ -555,6 +555,53 @@ typedef struct qfx_adam8bit_args {
 } qfx_adam8bit_args;
 int qfx_adam8bit_step(const qfx_adam8bit_args* a, void* stream);
 
+/* ---- Adafactor (third party transformers.optimization.Adafactor, the optimizer LoRA fine-tuning stacks offer next to the ones
+ * above; in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909, stepped at :531 after
+ * clip_gradients :449-455).  ONE launch steps every tensor of the flat fp32 LoRA buffers, one workgroup per tensor, driven by a device
+ * table the caller builds once per buffer layout.  Per tensor of rows x cols elements, with g' = g * clip (clip exactly as
+ * qfx_adamw_step computes it from gnorm_sq / max_norm / grad_scale), everything in fp32:
+ *   RMS = |p|_2 / sqrt(numel) (before the update, stored in rms[]);  lr_t = lr * (scale_parameter ? max(eps2, RMS) : 1)
+ *   u = g'^2 + eps1
+ *   factored:    row = beta2t row + (1 - beta2t) mean(u, cols),  col = beta2t col + (1 - beta2t) mean(u, rows)
+ *                upd = (rsqrt(row / mean(row)) [:, None] * rsqrt(col) [None, :]) * g'
+ *   unfactored:  v = beta2t v + (1 - beta2t) u,  upd = rsqrt(v) * g'
+ *   upd = upd / max(1, rms(upd) / clip_threshold) * lr_t;  use_beta1: m = beta1 m + (1 - beta1) upd, upd = m
+ *   weight_decay != 0: p += p * (-weight_decay * lr_t);  p -= upd
+ * `lr` is the relative step min(warmup_init ? 1e-6 t : 1e-2, 1 / sqrt(t)) or the external learning rate, beta2t = 1 - t^decay_rate;
+ * the caller forms them (and 1 - beta2t, 1 - beta1) in double and rounds to fp32.  A tensor whose g' holds a non-finite value is
+ * skipped whole: p, its statistics, m and rms[] stay as they were; the other tensors step.  Every reduction runs inside the tensor's
+ * workgroup in an order fixed by its shape, no atomics: same inputs -> same bits.  p, g are indexed by `off`, m by `m`; row, col, v,
+ * rms must be non-NULL (allocate one element for an unused buffer), m only with use_beta1.  Rejected with QFX_EINVAL before any
+ * launch: n_tensors < 0, with n_tensors > 0 a NULL table or buffer, a negative lr, beta2t outside [0, 1), clip_threshold <= 0,
+ * negative eps1 / eps2 / weight_decay, beta1 outside [0, 1).  n_tensors == 0 does nothing.  The table itself lives on the device
+ * and cannot be checked here: its builder bounds rows * cols by 2^30 and every offset by its buffer. ---- */
+typedef struct qfx_adafactor_tensor {
+  int64_t off;           /* first element of the tensor in p / g */
+  int64_t row;           /* factored: first of its `rows` elements in row */
+  int64_t col;           /* factored: first of its `cols` elements in col */
+  int64_t v;             /* unfactored: first of its `cols` elements in v */
+  int64_t m;             /* first element in m (read only with use_beta1) */
+  int32_t rows, cols;    /* the matrix; an unfactored tensor is 1 x numel */
+  int32_t rms;           /* index into rms */
+  int32_t factored;      /* 1: at least two dimensions */
+} qfx_adafactor_tensor;
+typedef struct qfx_adafactor_args {
+  float* p;              /* parameters, updated in place */
+  const float* g;        /* gradient (summed over ranks / micro-steps; scaled by grad_scale and the clip factor on the fly) */
+  float* row;            /* exp_avg_sq_row of every factored tensor */
+  float* col;            /* exp_avg_sq_col */
+  float* v;              /* exp_avg_sq of every unfactored tensor */
+  float* m;              /* exp_avg, may be NULL without use_beta1 */
+  float* rms;            /* one RMS per tensor */
+  const qfx_adafactor_tensor* table;   /* device array of n_tensors entries */
+  int32_t n_tensors;
+  int32_t scale_parameter, use_beta1;
+  float lr, beta2t, one_minus_beta2t, eps1, eps2, clip_threshold, beta1, one_minus_beta1, weight_decay;
+  const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq_det) for the global-norm clip */
+  float max_norm, grad_scale;
+} qfx_adafactor_args;
+int qfx_adafactor_step(const qfx_adafactor_args* a, void* stream);
+
 /* ---- runtime: a HIP stream confined to the first `n_cus` bits of the driver's CU mask (consecutive bits walk the 8 XCDs first, so
  * 16 = two CUs per XCD).  The persistent GEMM grids occupy 240 of the 256 CUs; leaf work of the backward (the LoRA weight-gradient
  * launches, which the reference's autograd also schedules off the dX critical path) runs here without ever taking a CU a GEMM block

@@ -137,6 +137,20 @@ class Adam8bitArgs(C.Structure):
 ADAM8BIT_BLOCKWISE, ADAM8BIT_FP32 = 0, 1     # qfx_adam8bit_block.mode
 
 
+class AdafactorTensor(C.Structure):
+    _fields_ = [("off", C.c_int64), ("row", C.c_int64), ("col", C.c_int64), ("v", C.c_int64), ("m", C.c_int64),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("rms", C.c_int32), ("factored", C.c_int32)]
+
+
+class AdafactorArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("row", C.c_void_p), ("col", C.c_void_p), ("v", C.c_void_p), ("m", C.c_void_p),
+                ("rms", C.c_void_p), ("table", C.c_void_p), ("n_tensors", C.c_int32), ("scale_parameter", C.c_int32),
+                ("use_beta1", C.c_int32), ("lr", C.c_float), ("beta2t", C.c_float), ("one_minus_beta2t", C.c_float),
+                ("eps1", C.c_float), ("eps2", C.c_float), ("clip_threshold", C.c_float), ("beta1", C.c_float),
+                ("one_minus_beta1", C.c_float), ("weight_decay", C.c_float), ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float),
+                ("grad_scale", C.c_float)]
+
+
 class HeadLora(C.Structure):
     _fields_ = [("w_pk", C.c_void_p * 2),
                 ("part", C.c_void_p), ("part_hstride", C.c_int64), ("ld_part", C.c_int32), ("c0", C.c_int32), ("R", C.c_int32),
@@ -227,6 +241,7 @@ SYMBOLS = {
     "qfx_prodigy_init_state": (C.c_int, [_vp, C.c_double, _vp]),
     "qfx_prodigy_step": (C.c_int, [C.POINTER(ProdigyArgs), _vp]),
     "qfx_adam8bit_step": (C.c_int, [C.POINTER(Adam8bitArgs), _vp]),
+    "qfx_adafactor_step": (C.c_int, [C.POINTER(AdafactorArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),
     "qfx_stream_destroy": (C.c_int, [_vp]),
     "qfx_debug_where": (C.c_int, [_vp, _i32, _vp]),

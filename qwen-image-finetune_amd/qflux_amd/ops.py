@@ -4,6 +4,7 @@ These are what the per-kernel parity tests call; the model builds cached argumen
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -407,6 +408,85 @@ def adam8bit_step(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2
                        layout.blocksize, _p(qmap1), _p(qmap2), lr, betas[0], betas[1], eps, weight_decay, int(step), _p(gnorm_sq),
                        max_norm, grad_scale)
     L.check(lib.qfx_adam8bit_step(a, stream_ptr()), "qfx_adam8bit_step")
+
+
+class AdafactorLayout:
+    """Descriptor table of one flat-buffer layout for qfx_adafactor_step, built once per layout.  `tensors[i]` = (off, rows, cols,
+    factored, first element in row, in col, in v) of entry i (-1 where the entry has none); n_row / n_col / n_v: elements the row /
+    col / v buffers need; extent: elements p / g / m need."""
+
+    def __init__(self, table, tensors, n_row, n_col, n_v, extent):
+        self.table, self.tensors, self.n_row, self.n_col, self.n_v, self.extent = table, tensors, n_row, n_col, n_v, extent
+        self.n_tensors = len(tensors)
+
+
+def adafactor_table(entries, device=None):
+    """entries: (offset, shape) of every tensor in the flat buffers.  A 2-D tensor is factored (rows + cols statistics, packed in
+    entry order), a 0-/1-D one keeps an elementwise second moment in v; exp_avg is indexed like the parameters."""
+    rows_, tensors, n_row, n_col, n_v, extent = [], [], 0, 0, 0, 0
+    for i, (off, shape) in enumerate(entries):
+        off, shape = int(off), tuple(int(d) for d in shape)
+        if len(shape) > 2:
+            raise ValueError(f"adafactor table: entry {i} has {len(shape)} dimensions (adapter matrices are 2-D; more is not implemented)")
+        numel = 1
+        for d in shape:
+            numel *= d
+        if off < 0 or numel <= 0 or numel > 1 << 30:
+            raise ValueError(f"adafactor table: entry {i}: offset {off} / shape {shape}")
+        if len(shape) == 2:
+            tensors.append((off, shape[0], shape[1], True, n_row, n_col, -1))
+            rows_.append((off, n_row, n_col, 0, off, shape[0], shape[1], i, 1))
+            n_row, n_col = n_row + shape[0], n_col + shape[1]
+        else:
+            tensors.append((off, 1, numel, False, -1, -1, n_v))
+            rows_.append((off, 0, 0, n_v, off, 1, numel, i, 0))
+            n_v += numel
+        extent = max(extent, off + numel)
+    if not rows_:
+        raise ValueError("adafactor table: no tensors")
+    arr = (L.AdafactorTensor * len(rows_))(*[L.AdafactorTensor(*r) for r in rows_])
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return AdafactorLayout(table, tensors, n_row, n_col, n_v, extent)
+
+
+def adafactor_scalars(step, lr=None, decay_rate=-0.8, relative_step=True, warmup_init=False):
+    """(lr or the relative step, beta2_t, 1 - beta2_t) of 1-based step `step`, formed in double (what the launch rounds to fp32)."""
+    if relative_step:
+        lr = min(1e-6 * step if warmup_init else 1e-2, 1.0 / math.sqrt(step))
+    beta2t = 1.0 - math.pow(step, decay_rate)
+    return float(lr), beta2t, 1.0 - beta2t
+
+
+def adafactor_step(p, g, row, col, v, m, rms, layout, step, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None,
+                   weight_decay=0.0, scale_parameter=True, relative_step=True, warmup_init=False, gnorm_sq=None, max_norm=0.0,
+                   grad_scale=1.0):
+    """One Adafactor step (transformers.optimization.Adafactor) over the flat buffers p / g; see qfx.h.  row / col / v: fp32 with >=
+    layout.n_row / n_col / n_v elements (one when unused); m: fp32 like p, None iff beta1 is None; rms: fp32[layout.n_tensors];
+    step: 1-based count t.  lr: the external learning rate, None with relative_step."""
+    if relative_step and lr is not None:
+        raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+    if warmup_init and not relative_step:
+        raise ValueError("`warmup_init=True` requires `relative_step=True`")
+    if lr is None and not relative_step:
+        raise ValueError("adafactor_step: relative_step=False needs a learning rate")
+    if int(step) < 1:
+        raise ValueError(f"adafactor_step: step {step} (counted from 1)")
+    f32 = torch.float32
+    for name, t, need in (("p", p, layout.extent), ("g", g, layout.extent), ("row", row, max(1, layout.n_row)),
+                          ("col", col, max(1, layout.n_col)), ("v", v, max(1, layout.n_v)), ("rms", rms, layout.n_tensors)) + \
+            ((("m", m, layout.extent),) if beta1 is not None else ()):
+        if t is None or t.dtype != f32 or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
+            raise ValueError(f"adafactor_step: {name} must be a contiguous float32 tensor on {p.device} with >= {need} elements")
+    if layout.table.device != p.device:
+        raise ValueError("adafactor_step: the descriptor table lives on another device")
+    lr_t, beta2t, omb2 = adafactor_scalars(int(step), lr, decay_rate, relative_step, warmup_init)
+    b1 = 0.0 if beta1 is None else float(beta1)
+    a = L.AdafactorArgs(_p(p), _p(g), _p(row), _p(col), _p(v), _p(m) if beta1 is not None else None, _p(rms), _p(layout.table),
+                        layout.n_tensors, int(bool(scale_parameter)), int(beta1 is not None), lr_t, beta2t, omb2, float(eps[0]),
+                        float(eps[1]), float(clip_threshold), b1, 1.0 - b1, float(weight_decay), _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_adafactor_step(a, stream_ptr()), "qfx_adafactor_step")
 
 
 # ---------------------------------------------------------------------------------------------- MX-FP8 (low-precision trunk)

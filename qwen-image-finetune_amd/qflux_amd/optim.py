@@ -1,7 +1,7 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
@@ -18,7 +18,7 @@ import torch
 from .trainer import optim_state as OS
 from .trainer.qwen_step import optimizer_kwargs_from_config
 
-__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD"]
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor"]
 
 
 def _find_store(param_groups):
@@ -55,7 +55,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
                                                                       dict(kw.get("optimizer_args") or {}, **(_own_args or {})) or None)
         # the family's own group fields (SGD's momentum, Prodigy's init_args) are visible in the group, as in the package's
         own = {n: v for n, v in self._args.items() if n in self._cls.save(None, [], 0, self._args)[0]}
-        super().__init__(params, dict(lr=kw["lr"], betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-8), weight_decay=wd, **own))
+        super().__init__(params, dict(dict(lr=kw["lr"], betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-8), weight_decay=wd), **own))
         self._raw_store = _find_store(self.param_groups)
         self._opt_state = None
         self._step_count_fused = 0
@@ -165,3 +165,13 @@ class SGD(_FlatOptimizer):
             raise NotImplementedError("differentiable is not implemented by the fused SGD step")
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                          maximize=maximize)
+
+
+class Adafactor(_FlatOptimizer):
+    """transformers.optimization.Adafactor (factored second moments, update clipping, relative step / parameter scaling)."""
+    _PATH = "qflux_amd.optim.Adafactor"
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                 scale_parameter=True, relative_step=True, warmup_init=False):
+        super().__init__(params, lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
+                         weight_decay=weight_decay, scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init)

@@ -1,5 +1,6 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
-file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit) and SgdState (torch.optim.SGD's).
+file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's) and
+AdafactorState (transformers.optimization.Adafactor's).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
@@ -277,10 +278,117 @@ class SgdState(FlatState):
         return state, 0
 
 
+class AdafactorState(FlatState):
+    """transformers.optimization.Adafactor: factored second moments of every adapter matrix (one vector per row, one per column,
+    packed in entry order), an elementwise one for tensors with fewer than two dimensions, the RMS of every tensor as of its last
+    step, and exp_avg indexed like pflat when beta1 is given.  Zeros are the package's initial state.  `eps` is the package's pair
+    (added to the squared gradient, floor of the parameter scale) and lives in the optimizer_args: the train step's own eps is unused."""
+    NAMES = ("row", "col", "v", "rms", "m")
+    DEFAULTS = dict(eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, scale_parameter=True, relative_step=True,
+                    warmup_init=False)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        dev = store.pflat.device
+        self.layout = ops.adafactor_table([(off, p.shape) for _, p, off, _ in store.entries], device=dev)
+        z = lambda n: torch.zeros(max(1, n), dtype=torch.float32, device=dev)
+        self.row, self.col, self.v, self.rms = z(self.layout.n_row), z(self.layout.n_col), z(self.layout.n_v), z(self.layout.n_tensors)
+        self.m = torch.zeros_like(store.pflat) if args["beta1"] is not None else None
+
+    @classmethod
+    def layout_key(cls, store, args):
+        return super().layout_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries), args["beta1"] is not None)
+
+    @classmethod
+    def names(cls, args):
+        return cls.NAMES if args["beta1"] is not None else cls.NAMES[:-1]
+
+    @staticmethod
+    def validate(args, lr=False):
+        """The package's constructor checks; lr=False: the learning rate is not known here."""
+        if args["warmup_init"] and not args["relative_step"]:
+            raise ValueError("`warmup_init=True` requires `relative_step=True`")
+        if lr is not False and lr is not None and args["relative_step"]:
+            raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+        if lr is None and not args["relative_step"]:
+            raise ValueError("Adafactor with relative_step=False needs a learning rate (lr=None)")
+        eps = args["eps"]
+        if not isinstance(eps, (tuple, list)) or len(eps) != 2:
+            raise ValueError(f"Adafactor's eps is a pair (eps1, eps2), not {eps!r}")
+        args["eps"] = (float(eps[0]), float(eps[1]))
+        if not args["clip_threshold"] > 0:
+            raise ValueError(f"Invalid clip_threshold value: {args['clip_threshold']}")
+        if args["beta1"] is not None and not 0.0 <= args["beta1"] < 1.0:
+            raise ValueError(f"Invalid beta1 value: {args['beta1']}")
+
+    def buffers(self):
+        return [(n, getattr(self, n)) for n in self.NAMES if getattr(self, n) is not None]
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        self.validate(args, lr)
+        ops.adafactor_step(store.pflat, store.gflat, self.row, self.col, self.v, self.m, self.rms, self.layout, step, lr=lr,
+                           weight_decay=weight_decay, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale, **args)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """transformers' layout: per parameter {"step", "RMS", "exp_avg_sq_row" [rows], "exp_avg_sq_col" [cols]} (two or more
+        dimensions) or {"step", "RMS", "exp_avg_sq"} (fewer), plus "exp_avg" with beta1; the group carries the package's options."""
+        group = {n: args[n] for n in cls.DEFAULTS}
+        if state is None or step == 0:
+            return group, {}
+        per = {}
+        for i, (_, p, off, k) in enumerate(entries):
+            _, rows, cols, factored, r0, c0, v0 = state.layout.tensors[i]
+            e = {"step": step, "RMS": state.rms[i].detach().cpu().clone()}
+            if factored:
+                e["exp_avg_sq_row"], e["exp_avg_sq_col"] = _out(state.row, r0, rows), _out(state.col, c0, cols)
+            else:
+                e["exp_avg_sq"] = _out(state.v, v0, k, p.shape)
+            if state.m is not None:
+                e["exp_avg"] = _out(state.m, off, k, p.shape)
+            per[i] = e
+        return group, per
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """Every statistic must have the shape the parameter implies; a file written without beta1 cannot resume a run with it."""
+        g = sd["param_groups"][0]
+        for n in cls.DEFAULTS:
+            if n in g:
+                args[n] = g[n]
+        cls.validate(args)
+        if not sd["state"]:
+            return None, 0
+        state, step, rms = cls(store, args), 0, [0.0] * len(store.entries)
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            _, rows, cols, factored, r0, c0, v0 = state.layout.tensors[i]
+            want = {"exp_avg_sq_row": (rows,), "exp_avg_sq_col": (cols,)} if factored else {"exp_avg_sq": tuple(p.shape)}
+            if state.m is not None:
+                want["exp_avg"] = tuple(p.shape)
+            for n, shape in want.items():
+                if n not in e:
+                    raise ValueError(f"optimizer state of parameter {i} (shape {tuple(p.shape)}) has no {n!r}: {sorted(e)}")
+                if tuple(e[n].shape) != shape:
+                    raise ValueError(f"optimizer state of parameter {i}: {n} has shape {tuple(e[n].shape)}, {shape} expected")
+            if factored:
+                state.row[r0:r0 + rows].copy_(e["exp_avg_sq_row"]); state.col[c0:c0 + cols].copy_(e["exp_avg_sq_col"])
+            else:
+                state.v[v0:v0 + k].copy_(e["exp_avg_sq"].reshape(-1))
+            if state.m is not None:
+                state.m[off:off + k].copy_(e["exp_avg"].reshape(-1))
+            rms[i] = float(e.get("RMS", 0.0))
+            step = max(step, int(float(e["step"])))
+        state.rms.copy_(torch.tensor(rms, dtype=torch.float32))
+        return state, step
+
+
 def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
     state class, weight decay, the family's optimizer_args with defaults filled in)."""
-    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd") + A8.BLOCKWISE:
+    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor") + A8.BLOCKWISE:
         raise ValueError(f"unknown optimizer {optimizer!r}")
     alias = None
     # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / SGD; Prodigy
@@ -301,16 +409,18 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     if weight_decay is None:
         weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
     blockwise = optimizer in A8.BLOCKWISE
-    cls = BlockwiseState if blockwise else {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState}[optimizer]
+    cls = BlockwiseState if blockwise else {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState}[optimizer]
     if blockwise:
         args = dict(min_8bit_size=4096, blocksize=256)
     elif optimizer == "sgd":
         args = dict(SgdState.DEFAULTS)
+    elif optimizer == "adafactor":
+        args = dict(AdafactorState.DEFAULTS)
     else:
         args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                     growth_rate=float("inf"))
     unknown = set(optimizer_args or {}) - set(args)
-    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd") + A8.BLOCKWISE):
+    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor") + A8.BLOCKWISE):
         raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
     args.update(optimizer_args or {})
     if blockwise:
@@ -319,6 +429,8 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         args["min_8bit_size"] = int(args["min_8bit_size"])
     if optimizer == "sgd":
         SgdState.validate(args)
+    if optimizer == "adafactor":
+        AdafactorState.validate(args)
     return alias, optimizer, cls, weight_decay, args
 
 
@@ -326,14 +438,18 @@ def state_dict(cls, state, store, step, args, lr, betas, eps, weight_decay):
     """{"state": {i: per-parameter state}, "param_groups": [...], "global_step"} with one entry per LoRA parameter in
     named_parameters() order (what accelerate's optimizer.bin holds for the reference), in the family's own layout."""
     extra, per = cls.save(state, store.entries, step, args)
-    group = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, **extra, params=list(range(len(store.entries))))
+    group = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    group.update(extra, params=list(range(len(store.entries))))       # a family's own field wins (Adafactor's eps is its pair)
     return {"state": per, "param_groups": [group], "global_step": step}
 
 
 def load_state_dict(cls, store, sd, args, hyper):
     """Inverse of state_dict: updates args and hyper (lr, betas, eps, weight_decay; a family without betas / eps, such as
-    torch.optim.SGD's own file, keeps the current values) in place and returns (state or None, step count)."""
+    torch.optim.SGD's or transformers' Adafactor's own file, keeps the current values) in place and returns (state or None, step count)."""
     g = sd["param_groups"][0]
-    hyper.update(lr=g["lr"], betas=tuple(g.get("betas", hyper["betas"])), eps=g.get("eps", hyper["eps"]), weight_decay=g["weight_decay"])
+    eps = g.get("eps", hyper["eps"])
+    if isinstance(eps, (tuple, list)):      # Adafactor's pair is one of its optimizer_args (cls.load reads it), not the scalar eps
+        eps = hyper["eps"]
+    hyper.update(lr=g["lr"], betas=tuple(g.get("betas", hyper["betas"])), eps=eps, weight_decay=g["weight_decay"])
     state, step = cls.load(store, sd, args)
     return state, max(int(sd.get("global_step", g.get("k", 0))), step)    # a package's own file: its group's count k, if any

@@ -60,12 +60,18 @@ class QwenLoraTrainStep:
         (256 or 2048).
         "sgd": torch.optim.SGD, the fourth optimizer the reference documents (docs/guide/training.md:768-826: momentum 0.9, weight_decay
         1e-4; weight decay in the L2 form, default 0); optimizer_args: momentum (0), dampening (0), nesterov (False); betas / eps unused.
+        "adafactor": transformers.optimization.Adafactor (factored second moments per adapter matrix, update clipping; weight decay
+        scaled by the step's learning rate, default 0); optimizer_args: eps ((1e-30, 1e-3)), clip_threshold (1.0), decay_rate (-0.8),
+        beta1 (None), scale_parameter (True), relative_step (True), warmup_init (False).  lr must be None with relative_step (the
+        default) and a float without it; betas / eps unused.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
         self.optimizer_alias, self.optimizer, self._opt_cls, weight_decay, self.optimizer_args = resolve_family(optimizer, weight_decay,
                                                                                                                 optimizer_args)
+        if self.optimizer == "adafactor":
+            self._opt_cls.validate(self.optimizer_args, lr)
         self.blockwise = optimizer in A8.BLOCKWISE
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
@@ -441,7 +447,9 @@ class QwenLoraTrainStep:
 # qflux_amd.optim class -> (the class it stands in for, the state_bits it implies)
 _OWN_CLASSES = {"qflux_amd.optim.AdamW": ("torch.optim.AdamW", 32), "qflux_amd.optim.Adam": ("torch.optim.Adam", 32),
                 "qflux_amd.optim.Adam8bit": ("bitsandbytes.optim.Adam8bit", 8), "qflux_amd.optim.AdamW8bit": ("bitsandbytes.optim.AdamW8bit", 8),
-                "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0)}
+                "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0),
+                "qflux_amd.optim.Adafactor": ("transformers.optimization.Adafactor", 0)}
+_ADAFACTOR = ("transformers.optimization.Adafactor", "transformers.Adafactor")
 _BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
              "bitsandbytes.optim.PagedAdamW8bit")
 
@@ -461,6 +469,9 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     says: AdamW -> "adamw", Adam -> "adam", Adam8bit / AdamW8bit -> "adam8bit_blockwise" / "adamw8bit_blockwise" (the class is named for
     its state), Prodigy -> "prodigy", SGD -> "sgd" + optimizer_args (momentum, dampening, nesterov; maximize is refused).
     torch.optim.SGD itself is not mapped.
+        transformers.optimization.Adafactor / transformers.Adafactor / qflux_amd.optim.Adafactor -> optimizer="adafactor" + optimizer_args
+    (eps pair, clip_threshold, decay_rate, beta1, scale_parameter, relative_step, warmup_init); lr is None with relative_step (the
+    package's default) and the package's refusals apply: lr with relative_step, warmup_init without it, no lr without it.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -471,6 +482,17 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         class_path, bits = _OWN_CLASSES[class_path]
         state_bits = bits or state_bits
     out = {}
+    if class_path in _ADAFACTOR:
+        # lr may be None (relative_step) and eps is the package's pair: both are read here, the package's own refusals apply
+        out["optimizer"] = "adafactor"
+        if "betas" in a:
+            raise NotImplementedError(f"unsupported optimizer init_args for {given}: ['betas']")
+        lr = a.pop("lr", None)
+        out["lr"] = None if lr is None else float(lr)
+        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in OS.AdafactorState.DEFAULTS}
+        if "eps" in out["optimizer_args"]:
+            out["optimizer_args"]["eps"] = tuple(float(e) for e in out["optimizer_args"]["eps"])
+        OS.AdafactorState.validate(dict(OS.AdafactorState.DEFAULTS, **out["optimizer_args"]), out["lr"])
     for k in ("lr", "eps", "weight_decay"):
         if k in a:
             out[k] = float(a.pop(k))
@@ -500,6 +522,8 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
             raise NotImplementedError(f"{given}: maximize=True is not implemented")
         out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("momentum", "dampening", "nesterov")}
         a.pop("differentiable", None)
+    elif class_path in _ADAFACTOR:
+        pass
     elif class_path == "prodigyopt.Prodigy":
         out["optimizer"] = "prodigy"
         out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("beta3", "decouple", "use_bias_correction", "safeguard_warmup", "d0",
