@@ -1,6 +1,6 @@
 """Tensor-level wrappers over the C ABI (one Python function per entry point of include/qfx.h).
 These are what the per-kernel parity tests call; the model builds cached argument structs instead
-(models/transformer_qwenimage.py) so that a training step is a flat list of C calls."""
+(plan/qwen.py, plan/flux.py) so that a training step is a flat list of C calls."""
 from __future__ import annotations
 
 import ctypes as C

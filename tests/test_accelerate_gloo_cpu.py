@@ -64,7 +64,7 @@ def _worker(rank, world, port, q):
             self.calls.append(on_segment is not None)
 
     class _Fn(torch.autograd.Function):
-        """Same shape as _QwenDiTFn (models/transformer_qwenimage.py): LoRA parameters are inputs only so that autograd schedules the
+        """Same shape as _QwenDiTFn (plan/qwen.py): LoRA parameters are inputs only so that autograd schedules the
         node; backward returns None for all of them."""
 
         @staticmethod
