@@ -602,6 +602,44 @@ typedef struct qfx_adafactor_args {
 } qfx_adafactor_args;
 int qfx_adafactor_step(const qfx_adafactor_args* a, void* stream);
 
+/* ---- Lion (Chen et al., "Symbolic Discovery of Optimization Algorithms", 2023; third party lion_pytorch.Lion and
+ * bitsandbytes.optim.Lion / Lion8bit / PagedLion8bit, the one-moment optimizer LoRA fine-tuning stacks offer next to the ones above;
+ * in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909, stepped at :531 after
+ * clip_gradients :449-455).  ONE launch over the flat LoRA buffers.  Per element, with g' = g * clip (clip exactly as qfx_adamw_step
+ * computes it from gnorm_sq / max_norm / grad_scale), everything in fp32, 1 - b1, 1 - b2 and decay = 1 - lr wd formed in fp32:
+ *   c = m b1 + (1 - b1) g'          (two products and one sum, each rounded: never contracted into an FMA, the sign of c decides)
+ *   p = p decay                     (only when wd > 0: decoupled, BEFORE the update)
+ *   p = p - lr sgn(c)               (sgn(0) = 0)
+ *   m = m b2 + (1 - b2) g'          (the same un-contracted form)
+ * An element whose g' is not finite keeps p and m unchanged.  The step count does not enter the arithmetic.
+ * qfx_lion_step: m [n] in fp32, 16-byte accesses when p, g and m are 16-byte aligned.
+ * qfx_lion8bit_step: bitsandbytes' blockwise 8-bit state of ONE moment, driven by the block table of qfx_adam8bit_step (same
+ * struct, same builder).  8-bit block: m = qmap1[q1] * absmax1[blk] decoded, updated as above, then stored exactly as
+ * qfx_adam8bit_step stores state1 -- absmax = max |m| over the block, the nearest code against the fp32 midpoints with a tie going
+ * to the lower one, then the keep-the-sign rule; a block whose absmax is 0 stores the code of 0.0.  The parameter update uses the
+ * fp32 m, not its re-quantised image.  fp32 entries keep their moment in m32.  Every pointer must be non-NULL (allocate one element
+ * for an unused buffer); p, g, q1 are indexed by `off`, m32 by `state` of the fp32 entries; `off` and `state` are multiples of 4.
+ * No atomics: same inputs -> same bits.  Rejected with QFX_EINVAL before any launch: a NULL p, g or m (8-bit: any NULL pointer but
+ * gnorm_sq), n <= 0, a negative lr, a beta outside [0, 1), a negative weight_decay, and for the 8-bit entry n_blocks <= 0 or a
+ * blocksize outside {256, 2048}. ---- */
+int qfx_lion_step(float* p, const float* g, float* m, int64_t n, float lr, float beta1, float beta2, float weight_decay,
+                  const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale, void* stream);
+typedef struct qfx_lion8bit_args {
+  float* p;              /* parameters, updated in place */
+  const float* g;        /* gradient (summed over ranks / micro-steps; scaled by grad_scale and the clip factor on the fly) */
+  uint8_t* q1;           /* state1 codes (signed map), same indexing as p */
+  float* absmax1;        /* per 8-bit block */
+  float* m32;            /* fp32 moment of the tensors below the 8-bit size */
+  const qfx_adam8bit_block* table;   /* device array of n_blocks entries */
+  int32_t n_blocks;
+  int32_t blocksize;     /* 256 or 2048: the largest `len` of the table */
+  const float* qmap1;    /* fp32[256] */
+  float lr, beta1, beta2, weight_decay;
+  const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq_det) for the global-norm clip */
+  float max_norm, grad_scale;
+} qfx_lion8bit_args;
+int qfx_lion8bit_step(const qfx_lion8bit_args* a, void* stream);
+
 /* ---- runtime: a HIP stream confined to the first `n_cus` bits of the driver's CU mask (consecutive bits walk the 8 XCDs first, so
  * 16 = two CUs per XCD).  The persistent GEMM grids occupy 240 of the 256 CUs; leaf work of the backward (the LoRA weight-gradient
  * launches, which the reference's autograd also schedules off the dX critical path) runs here without ever taking a CU a GEMM block

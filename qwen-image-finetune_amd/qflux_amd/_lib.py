@@ -151,6 +151,13 @@ class AdafactorArgs(C.Structure):
                 ("grad_scale", C.c_float)]
 
 
+class Lion8bitArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("q1", C.c_void_p), ("absmax1", C.c_void_p), ("m32", C.c_void_p),
+                ("table", C.c_void_p), ("n_blocks", C.c_int32), ("blocksize", C.c_int32), ("qmap1", C.c_void_p),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("weight_decay", C.c_float),
+                ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
 class HeadLora(C.Structure):
     _fields_ = [("w_pk", C.c_void_p * 2),
                 ("part", C.c_void_p), ("part_hstride", C.c_int64), ("ld_part", C.c_int32), ("c0", C.c_int32), ("R", C.c_int32),
@@ -242,6 +249,8 @@ SYMBOLS = {
     "qfx_prodigy_step": (C.c_int, [C.POINTER(ProdigyArgs), _vp]),
     "qfx_adam8bit_step": (C.c_int, [C.POINTER(Adam8bitArgs), _vp]),
     "qfx_adafactor_step": (C.c_int, [C.POINTER(AdafactorArgs), _vp]),
+    "qfx_lion_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _f, _f, _vp]),
+    "qfx_lion8bit_step": (C.c_int, [C.POINTER(Lion8bitArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),
     "qfx_stream_destroy": (C.c_int, [_vp]),
     "qfx_debug_where": (C.c_int, [_vp, _i32, _vp]),

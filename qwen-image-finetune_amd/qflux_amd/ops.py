@@ -410,6 +410,32 @@ def adam8bit_step(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2
     L.check(lib.qfx_adam8bit_step(a, stream_ptr()), "qfx_adam8bit_step")
 
 
+def lion_step(p, g, m, lr, beta1, beta2, weight_decay=0.0, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """One Lion step (lion_pytorch.Lion / bitsandbytes.optim.Lion) over the flat fp32 buffers p / g with the one moment m; see qfx.h."""
+    for name, t in (("p", p), ("g", g), ("m", m)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < p.numel() or t.device != p.device:
+            raise ValueError(f"lion_step: {name} must be a contiguous float32 tensor on {p.device} with >= {p.numel()} elements")
+    L.check(lib.qfx_lion_step(_p(p), _p(g), _p(m), p.numel(), lr, beta1, beta2, weight_decay, _p(gnorm_sq), max_norm, grad_scale,
+                              stream_ptr()), "qfx_lion_step")
+
+
+def lion8bit_step(p, g, q1, absmax1, m32, layout, qmap1, lr, betas, weight_decay=0.0, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """One blockwise 8-bit Lion step (bitsandbytes' Lion8bit state layout) over the flat buffers p / g; see qfx.h.  layout: an
+    adam8bit_block_table; q1: uint8 codes indexed like p; absmax1: fp32[>= layout.n_absmax]; m32: fp32[>= layout.n_fp32] (one element
+    when unused); qmap1: fp32[256] ascending."""
+    f32, u8 = torch.float32, torch.uint8
+    for name, t, dt, need in (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
+                              ("absmax1", absmax1, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
+                              ("qmap1", qmap1, f32, 256)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
+            raise ValueError(f"lion8bit_step: {name} must be a contiguous {dt} tensor on {p.device} with >= {need} elements")
+    if layout.table.device != p.device:
+        raise ValueError("lion8bit_step: the block table lives on another device")
+    a = L.Lion8bitArgs(_p(p), _p(g), _p(q1), _p(absmax1), _p(m32), _p(layout.table), layout.n_blocks, layout.blocksize, _p(qmap1),
+                       lr, betas[0], betas[1], weight_decay, _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_lion8bit_step(a, stream_ptr()), "qfx_lion8bit_step")
+
+
 class AdafactorLayout:
     """Descriptor table of one flat-buffer layout for qfx_adafactor_step, built once per layout.  `tensors[i]` = (off, rows, cols,
     factored, first element in row, in col, in v) of entry i (-1 where the entry has none); n_row / n_col / n_v: elements the row /

@@ -1,7 +1,7 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, Lion, Lion8bit, PagedLion8bit) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
@@ -18,7 +18,7 @@ import torch
 from .trainer import optim_state as OS
 from .trainer.qwen_step import optimizer_kwargs_from_config
 
-__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor"]
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit"]
 
 
 def _find_store(param_groups):
@@ -175,3 +175,33 @@ class Adafactor(_FlatOptimizer):
                  scale_parameter=True, relative_step=True, warmup_init=False):
         super().__init__(params, lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
                          weight_decay=weight_decay, scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init)
+
+
+class Lion(_FlatOptimizer):
+    """lion_pytorch.Lion (one fp32 moment, sign update, decoupled weight decay before the update).  use_triton only says where the
+    package runs the same arithmetic; decoupled_weight_decay=True and the cautious variant are not implemented."""
+    _PATH = "lion_pytorch.Lion"        # mapped as the class it stands in for: its own path is not a name optimizer_kwargs_from_config knows
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0, cautious_factor=1.0, use_triton=False,
+                 decoupled_weight_decay=False):
+        super().__init__(params, lr=lr, betas=betas, weight_decay=weight_decay, cautious_factor=cautious_factor, use_triton=use_triton,
+                         decoupled_weight_decay=decoupled_weight_decay)
+
+
+class Lion8bit(_FlatOptimizer):
+    """bitsandbytes.optim.Lion8bit: the moment in blockwise 8-bit codes, bitsandbytes' one-state layout (trainer/adam8bit.py).
+    blocksize (256 or 2048) is this class's own keyword; a file brings its own."""
+    _PATH = "qflux_amd.optim.Lion8bit"
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0, optim_bits=32, args=None, min_8bit_size=4096,
+                 percentile_clipping=100, block_wise=True, is_paged=False, *, blocksize=256):
+        if args is not None:
+            raise NotImplementedError("bitsandbytes' `args` override object is not supported")
+        super().__init__(params, lr=lr, betas=betas, weight_decay=weight_decay, optim_bits=optim_bits, min_8bit_size=min_8bit_size,
+                         percentile_clipping=percentile_clipping, block_wise=block_wise, is_paged=is_paged,
+                         _own_args={"blocksize": blocksize})
+
+
+class PagedLion8bit(Lion8bit):
+    """bitsandbytes.optim.PagedLion8bit: paged memory only moves the state, the step is Lion8bit's."""
+    _PATH = "qflux_amd.optim.PagedLion8bit"

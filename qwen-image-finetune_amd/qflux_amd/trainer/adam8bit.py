@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 BLOCKWISE = ("adam8bit_blockwise", "adamw8bit_blockwise")
+LION_BLOCKWISE = ("lion8bit_blockwise",)      # bitsandbytes.optim.Lion8bit: ONE moment in the same layout (optim_state.LionBlockwiseState)
 BLOCKSIZES = (256, 2048)
 
 
@@ -52,9 +53,17 @@ def bnb_moments(e: dict):
             dequantize(e["state2"], e["qmap2"].float(), e["absmax2"].float(), bs))
 
 
+def bnb_moment1(e: dict):
+    """state1 in fp32 of one bnb-layout parameter state with ONE moment (Lion: there is no state2)."""
+    if e["state1"].dtype != torch.uint8:
+        return e["state1"].float()
+    bs = infer_blocksize(e["state1"].numel(), e["absmax1"].numel())
+    return dequantize(e["state1"], e["qmap1"].float(), e["absmax1"].float(), bs)
+
+
 def file_layout(states: dict, entries):
     """(blocksize, qmap1, qmap2) of a bnb-layout state dict: the block size inferred from the absmax sizes (one for all tensors), the
-    code books of the first 8-bit tensor (None when every tensor is below the 8-bit size)."""
+    code books of the first 8-bit tensor (None when every tensor is below the 8-bit size; qmap2 also for a one-moment file)."""
     bs, q1, q2 = None, None, None
     for i, (_, _, _, k) in enumerate(entries):
         e = states.get(i)
@@ -65,5 +74,5 @@ def file_layout(states: dict, entries):
             raise ValueError(f"optimizer state mixes block sizes {bs} and {b}")
         bs = b
         if q1 is None:
-            q1, q2 = e["qmap1"].float(), e["qmap2"].float()
+            q1, q2 = e["qmap1"].float(), (e["qmap2"].float() if "qmap2" in e else None)
     return bs, q1, q2

@@ -1,6 +1,7 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
-file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's) and
-AdafactorState (transformers.optimization.Adafactor's).
+file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
+AdafactorState (transformers.optimization.Adafactor's), LionState (lion_pytorch.Lion's) and LionBlockwiseState (bitsandbytes'
+Lion8bit).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
@@ -385,10 +386,124 @@ class AdafactorState(FlatState):
         return state, step
 
 
+class LionState(FlatState):
+    """lion_pytorch.Lion / bitsandbytes.optim.Lion: the one moment exp_avg in fp32, indexed like pflat.  eps is unused."""
+    NAMES = ("exp_avg",)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.exp_avg = torch.zeros_like(store.pflat)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        ops.lion_step(store.pflat, store.gflat, self.exp_avg, lr, betas[0], betas[1], weight_decay, gnorm_sq=gnorm_sq, max_norm=max_norm,
+                      grad_scale=grad_scale)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """lion_pytorch's layout: per parameter {"exp_avg"} (no step count: it does not enter the arithmetic); lr, betas and
+        weight_decay in the group.  A state exists from the first step or a loaded file on (a lion_pytorch file counts no steps)."""
+        if state is None:
+            return {}, {}
+        return {}, {i: {"exp_avg": _out(state.exp_avg, off, k, p.shape)} for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """Either lion_pytorch's {"exp_avg"} or a bitsandbytes Lion file's {"step", "state1"} (fp32 as it is, 8-bit codes dequantised)."""
+        if not sd["state"]:
+            return None, 0
+        state, step = cls(store, args), 0
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            ea = e["exp_avg"] if "exp_avg" in e else A8.bnb_moment1(e)
+            if ea.numel() != k:
+                raise ValueError(f"optimizer state of parameter {i}: {ea.numel()} elements, {k} expected")
+            state.exp_avg[off:off + k].copy_(ea.reshape(-1).float())
+            step = max(step, int(float(e.get("step", 0))))
+        return state, step
+
+
+class LionBlockwiseState(FlatState):
+    """bitsandbytes.optim.Lion8bit / PagedLion8bit: BlockwiseState with ONE moment -- codes indexed like pflat, absmax per 8-bit block,
+    the fp32 moment of the tensors below min_8bit_size, the signed code book, and the same block table."""
+    LAYOUT_ARGS = ("blocksize", "min_8bit_size")
+    NAMES = ("q1", "absmax1", "m32", "qmap1")
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        dev = store.pflat.device
+        self.layout = ops.adam8bit_block_table([(off, k) for _, _, off, k in store.entries], args["blocksize"], args["min_8bit_size"],
+                                               device=dev)
+        self.q1 = torch.zeros(store.pflat.numel(), dtype=torch.uint8, device=dev)     # bnb's initial state: codes 0, absmax 0
+        self.absmax1 = torch.zeros(max(1, self.layout.n_absmax), dtype=torch.float32, device=dev)
+        self.m32 = torch.zeros(max(1, self.layout.n_fp32), dtype=torch.float32, device=dev)
+        self.qmap1 = A8.dynamic_map(True).to(dev)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        ops.lion8bit_step(store.pflat, store.gflat, self.q1, self.absmax1, self.m32, self.layout, self.qmap1, lr, betas, weight_decay,
+                          gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+
+    def param_state(self, i, shape, step):
+        """bnb's per-parameter state of entry i (CPU tensors)."""
+        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        if not eight:
+            return {"step": step, "state1": _out(self.m32, s0, k, shape)}
+        return {"step": step, "state1": _out(self.q1, off, k, shape), "qmap1": self.qmap1.cpu().clone(),
+                "absmax1": _out(self.absmax1, a0, nb)}
+
+    def load_param_state(self, i, e):
+        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        if (e["state1"].dtype == torch.uint8) != eight:
+            raise ValueError(f"optimizer state of parameter {i} ({k} elements) is {'8-bit' if not eight else 'fp32'} in the file: it was "
+                             f"saved with another min_8bit_size than {self.layout.min_8bit_size}")
+        if not eight:
+            self.m32[s0:s0 + k].copy_(e["state1"].reshape(-1))
+            return
+        if e["absmax1"].numel() != nb:
+            raise ValueError(f"optimizer state of parameter {i}: {e['absmax1'].numel()} absmax blocks, {nb} expected")
+        self.q1[off:off + k].copy_(e["state1"].reshape(-1))
+        self.absmax1[a0:a0 + nb].copy_(e["absmax1"].reshape(-1))
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """bnb's Optimizer1State layout: per parameter {"step", "state1", "qmap1", "absmax1"} (8-bit) or {"step", "state1"} (fp32
+        moment, numel < min_8bit_size); no group fields of its own."""
+        if state is None or step == 0:
+            return {}, {}
+        return {}, {i: state.param_state(i, p.shape, step) for i, (_, p, _, _) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """The block size is inferred from the file's absmax sizes, the code book is the file's."""
+        bs, q1, _ = A8.file_layout(sd["state"], store.entries)
+        if bs is not None:
+            args["blocksize"] = bs
+        state, step = cls(store, args), 0
+        if q1 is not None:
+            state.qmap1.copy_(q1)
+        for i in range(len(store.entries)):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            state.load_param_state(i, e)
+            step = max(step, int(float(e["step"])))
+        return state, step
+
+
+LION = ("lion",) + A8.LION_BLOCKWISE
+
+
+def default_betas(optimizer):
+    """The betas a train step uses when its caller gives none: the optimizer class's own default -- (0.9, 0.99) for Lion (both
+    packages), (0.9, 0.999) for every other family (torch.optim.AdamW's, the train steps' default so far)."""
+    return (0.9, 0.99) if optimizer in LION else (0.9, 0.999)
+
+
 def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
     state class, weight decay, the family's optimizer_args with defaults filled in)."""
-    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor") + A8.BLOCKWISE:
+    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor") + A8.BLOCKWISE + LION:
         raise ValueError(f"unknown optimizer {optimizer!r}")
     alias = None
     # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / SGD; Prodigy
@@ -408,10 +523,13 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         alias, optimizer = optimizer, "adamw"
     if weight_decay is None:
         weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
-    blockwise = optimizer in A8.BLOCKWISE
-    cls = BlockwiseState if blockwise else {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState}[optimizer]
+    blockwise = optimizer in A8.BLOCKWISE + A8.LION_BLOCKWISE
+    cls = (LionBlockwiseState if optimizer in A8.LION_BLOCKWISE else BlockwiseState) if blockwise else \
+        {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState, "lion": LionState}[optimizer]
     if blockwise:
         args = dict(min_8bit_size=4096, blocksize=256)
+    elif optimizer == "lion":
+        args = {}
     elif optimizer == "sgd":
         args = dict(SgdState.DEFAULTS)
     elif optimizer == "adafactor":
@@ -420,7 +538,7 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                     growth_rate=float("inf"))
     unknown = set(optimizer_args or {}) - set(args)
-    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor") + A8.BLOCKWISE):
+    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor") + A8.BLOCKWISE + A8.LION_BLOCKWISE):
         raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
     args.update(optimizer_args or {})
     if blockwise:

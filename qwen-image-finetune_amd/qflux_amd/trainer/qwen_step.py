@@ -48,7 +48,7 @@ def map_mask_to_latent(image_mask: torch.Tensor) -> torch.Tensor:
 
 
 class QwenLoraTrainStep:
-    def __init__(self, dit, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, max_grad_norm=1.0,
+    def __init__(self, dit, lr=1e-4, betas=None, eps=1e-8, weight_decay=None, max_grad_norm=1.0,
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
                  bucket_mb=24.0, optimizer="adamw", optimizer_args=None):
         """optimizer: "adamw" (torch.optim.AdamW semantics, lr/betas/eps/weight_decay above) or "prodigy" (prodigyopt.Prodigy, the
@@ -64,6 +64,13 @@ class QwenLoraTrainStep:
         scaled by the step's learning rate, default 0); optimizer_args: eps ((1e-30, 1e-3)), clip_threshold (1.0), decay_rate (-0.8),
         beta1 (None), scale_parameter (True), relative_step (True), warmup_init (False).  lr must be None with relative_step (the
         default) and a float without it; betas / eps unused.
+        "lion": lion_pytorch.Lion / bitsandbytes.optim.Lion (one fp32 moment, the update is lr times the sign of the interpolated
+        moment; weight decay decoupled, before the update, default 0); no optimizer_args; eps unused.  "lion8bit_blockwise":
+        bitsandbytes.optim.Lion8bit / PagedLion8bit with the moment in blockwise 8-bit codes and bnb's one-state layout;
+        optimizer_args: min_8bit_size (4096), blocksize (256 or 2048).
+        betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, (0.9, 0.999) --
+        torch.optim.AdamW's, this constructor's default before Lion -- for every other one; betas given explicitly are never
+        reinterpreted.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
@@ -76,6 +83,7 @@ class QwenLoraTrainStep:
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
         self.dit = dit
+        betas = OS.default_betas(self.optimizer) if betas is None else tuple(betas)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
         self.weight_dtype = weight_dtype
@@ -448,8 +456,12 @@ class QwenLoraTrainStep:
 _OWN_CLASSES = {"qflux_amd.optim.AdamW": ("torch.optim.AdamW", 32), "qflux_amd.optim.Adam": ("torch.optim.Adam", 32),
                 "qflux_amd.optim.Adam8bit": ("bitsandbytes.optim.Adam8bit", 8), "qflux_amd.optim.AdamW8bit": ("bitsandbytes.optim.AdamW8bit", 8),
                 "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0),
-                "qflux_amd.optim.Adafactor": ("transformers.optimization.Adafactor", 0)}
+                "qflux_amd.optim.Adafactor": ("transformers.optimization.Adafactor", 0),
+                "qflux_amd.optim.Lion8bit": ("bitsandbytes.optim.Lion8bit", 8),
+                "qflux_amd.optim.PagedLion8bit": ("bitsandbytes.optim.PagedLion8bit", 8)}
 _ADAFACTOR = ("transformers.optimization.Adafactor", "transformers.Adafactor")
+_LION = ("lion_pytorch.Lion", "bitsandbytes.optim.Lion", "bitsandbytes.optim.Lion32bit")
+_BNB_LION_8BIT = ("bitsandbytes.optim.Lion8bit", "bitsandbytes.optim.PagedLion8bit")
 _BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
              "bitsandbytes.optim.PagedAdamW8bit")
 
@@ -472,6 +484,14 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         transformers.optimization.Adafactor / transformers.Adafactor / qflux_amd.optim.Adafactor -> optimizer="adafactor" + optimizer_args
     (eps pair, clip_threshold, decay_rate, beta1, scale_parameter, relative_step, warmup_init); lr is None with relative_step (the
     package's default) and the package's refusals apply: lr with relative_step, warmup_init without it, no lr without it.
+        lion_pytorch.Lion / bitsandbytes.optim.Lion / Lion32bit -> optimizer="lion" (lr, betas, weight_decay;
+    betas left out = the class's (0.9, 0.99), weight decay default 0); lion_pytorch's use_triton and decoupled_weight_decay=False are
+    accepted (where the arithmetic runs; the plain decoupled form), decoupled_weight_decay=True and cautious_factor != 1 are refused.
+        bitsandbytes.optim.Lion8bit / PagedLion8bit -> "lion" (fp32 moment) with state_bits=32, "lion8bit_blockwise" (bnb's one-state
+    8-bit layout, min_8bit_size honoured) with state_bits=8 -- the Adam8bit rule, with the same init_args refused;
+    qflux_amd.optim.Lion8bit / PagedLion8bit always map to the blockwise form.  The path qflux_amd.optim.Lion itself is NOT mapped
+    here and keeps raising (tests/test_optim_classes_cpu.py pins that refusal): the class exists and steps "lion", a config for the
+    fused train step names lion_pytorch.Lion, whose keywords it takes.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -498,9 +518,9 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
             out[k] = float(a.pop(k))
     if "betas" in a:
         out["betas"] = tuple(float(b) for b in a.pop("betas"))
-    if state_bits == 8 and class_path in _BNB_8BIT:
+    if state_bits == 8 and class_path in _BNB_8BIT + _BNB_LION_8BIT:
         adamw = "AdamW" in name
-        out["optimizer"] = "adamw8bit_blockwise" if adamw else "adam8bit_blockwise"
+        out["optimizer"] = "lion8bit_blockwise" if class_path in _BNB_LION_8BIT else "adamw8bit_blockwise" if adamw else "adam8bit_blockwise"
         out.setdefault("weight_decay", 0.01 if adamw else 0.0)
         refused = {"percentile_clipping": (100, "percentile clipping"), "max_unorm": (0.0, "update-norm clipping (max_unorm)"),
                    "block_wise": (True, "non-blockwise 8-bit state"), "skip_zeros": (False, "skip_zeros"), "amsgrad": (False, "amsgrad")}
@@ -516,6 +536,14 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     elif class_path in ("torch.optim.Adam", "bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.Adam", "bitsandbytes.optim.PagedAdam8bit"):
         out["optimizer"] = "adam8bit" if "8bit" in name else "adam"
         out.setdefault("weight_decay", 0.0)
+    elif class_path in _LION + _BNB_LION_8BIT:
+        out["optimizer"] = "lion"
+        out.setdefault("weight_decay", 0.0)
+        if a.pop("decoupled_weight_decay", False):
+            raise NotImplementedError(f"{given}: decoupled_weight_decay=True (weight decay scaled by lr / the initial lr) is not implemented")
+        if float(a.pop("cautious_factor", 1.0)) != 1.0:
+            raise NotImplementedError(f"{given}: the cautious variant (cautious_factor != 1) is not implemented")
+        a.pop("use_triton", None)      # where lion_pytorch runs the same arithmetic
     elif given == "qflux_amd.optim.SGD":
         out["optimizer"] = "sgd"
         if a.pop("maximize", False):
