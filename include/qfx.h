@@ -640,6 +640,56 @@ typedef struct qfx_lion8bit_args {
 } qfx_lion8bit_args;
 int qfx_lion8bit_step(const qfx_lion8bit_args* a, void* stream);
 
+/* ---- Muon (Jordan et al., "Muon: An optimizer for hidden layers in neural networks", 2024; torch.optim.Muon, the one mainstream
+ * optimizer defined per MATRIX; in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909,
+ * stepped at :531 after clip_gradients :449-455).  ONE launch, one workgroup per adapter matrix, driven by a device table.  Per
+ * matrix [rows, cols] (row-major at `off` in p / g / buf), with g' = g * clip (clip exactly as qfx_adamw_step computes it from
+ * gnorm_sq / max_norm / grad_scale) and lerp(x, y, w) = w < 0.5 ? fma(w, y - x, x) : fma(w - 1, y - x, y) (ATen's lerp), the
+ * rounding points of torch.optim.Muon:
+ *   buf = lerp(buf, g', 1 - momentum)                                    fp32; 1 - momentum formed in double by the caller
+ *   u   = nesterov ? lerp(g', buf, momentum) : buf                       fp32
+ *   X   = bf16(u), transposed when rows > cols: X is [s, n], s = min(rows, cols) <= 96
+ *   X   = bf16(X / max(bf16(sqrt(sum X^2)), bf16(eps)))                  the sum in fp32
+ *   ns_steps times:  G = bf16(X X^T);  H = bf16(b G + c (G G));  X = bf16(a X + H X)
+ *                    bf16 operands, fp32 accumulation (v_mfma_f32_16x16x32_bf16; s padded to a multiple of 16 and n to a multiple
+ *                    of 32 by zeros, which change no sum)
+ *   p   = fma(-(lr lr_ratio), O, p (1 - lr weight_decay))                fp32; O = X, transposed back
+ * g' is rounded to fp32 before it is used (the file is compiled without FMA contraction): a clipped step equals a step on the
+ * pre-scaled gradient bit for bit.
+ * lr_ratio is torch's _adjust_lr per matrix: sqrt(max(1, rows / cols)) ("original" / None) or 0.2 sqrt(max(rows, cols))
+ * ("match_rms_adamw").  An all-zero g' gives O = 0 exactly (only the decay moves p).  A matrix whose g' holds a non-finite value is
+ * skipped whole: p and buf stay as they were; the other matrices step.  X lives in LDS when its padded image takes at most 96 KB
+ * ([16, 3072] exactly) and otherwise in this workgroup's slot of the bf16 workspace `ws`, which the caller allocates with
+ * qfx_muon_ws_bytes(host copy of the table, n_tensors) bytes (0 when every matrix fits LDS; QFX_EINVAL for a table with a matrix
+ * whose short side exceeds 96, with rows * cols > 2^30 or with a negative offset).  A matrix that fits neither LDS nor the slot
+ * ws_bytes provides, or that the builder would have refused, is left unchanged: the kernel never writes past a slot.  No atomics,
+ * nothing crosses a workgroup, every sum runs in an order fixed by the shape: same inputs -> same bits.  Rejected with QFX_EINVAL
+ * before any launch: n_tensors < 0, with n_tensors > 0 a NULL table, p, g or buf, a NULL or unaligned (16 B) ws with ws_bytes > 0,
+ * a negative lr, weight_decay or momentum, ns_steps outside [0, 100), eps <= 0.  n_tensors == 0 does nothing. ---- */
+typedef struct qfx_muon_tensor {
+  int64_t off;           /* first element of the matrix in p / g / buf */
+  int32_t rows, cols;
+  float lr_ratio;        /* adjusted lr = lr * lr_ratio */
+  int32_t reserved;      /* 0 */
+} qfx_muon_tensor;
+typedef struct qfx_muon_args {
+  float* p;              /* parameters, updated in place */
+  const float* g;        /* gradient (summed over ranks / micro-steps; scaled by grad_scale and the clip factor on the fly) */
+  float* buf;            /* momentum buffer, indexed like p */
+  uint16_t* ws;          /* bf16 workspace, may be NULL with ws_bytes == 0 */
+  int64_t ws_bytes;      /* bytes allocated behind ws */
+  const qfx_muon_tensor* table;   /* device array of n_tensors entries */
+  int32_t n_tensors;
+  int32_t nesterov, ns_steps;
+  float lr, weight_decay, momentum, one_minus_momentum;
+  float a, b, c;         /* ns_coefficients */
+  float eps;
+  const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq_det) for the global-norm clip */
+  float max_norm, grad_scale;
+} qfx_muon_args;
+int64_t qfx_muon_ws_bytes(const qfx_muon_tensor* host_table, int32_t n_tensors);
+int qfx_muon_step(const qfx_muon_args* a, void* stream);
+
 /* ---- runtime: a HIP stream confined to the first `n_cus` bits of the driver's CU mask (consecutive bits walk the 8 XCDs first, so
  * 16 = two CUs per XCD).  The persistent GEMM grids occupy 240 of the 256 CUs; leaf work of the backward (the LoRA weight-gradient
  * launches, which the reference's autograd also schedules off the dX critical path) runs here without ever taking a CU a GEMM block

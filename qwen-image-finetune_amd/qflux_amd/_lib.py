@@ -158,6 +158,18 @@ class Lion8bitArgs(C.Structure):
                 ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
+class MuonTensor(C.Structure):
+    _fields_ = [("off", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("lr_ratio", C.c_float), ("reserved", C.c_int32)]
+
+
+class MuonArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("table", C.c_void_p), ("n_tensors", C.c_int32), ("nesterov", C.c_int32), ("ns_steps", C.c_int32),
+                ("lr", C.c_float), ("weight_decay", C.c_float), ("momentum", C.c_float), ("one_minus_momentum", C.c_float),
+                ("a", C.c_float), ("b", C.c_float), ("c", C.c_float), ("eps", C.c_float),
+                ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
 class HeadLora(C.Structure):
     _fields_ = [("w_pk", C.c_void_p * 2),
                 ("part", C.c_void_p), ("part_hstride", C.c_int64), ("ld_part", C.c_int32), ("c0", C.c_int32), ("R", C.c_int32),
@@ -251,6 +263,8 @@ SYMBOLS = {
     "qfx_adafactor_step": (C.c_int, [C.POINTER(AdafactorArgs), _vp]),
     "qfx_lion_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _f, _f, _vp]),
     "qfx_lion8bit_step": (C.c_int, [C.POINTER(Lion8bitArgs), _vp]),
+    "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),
+    "qfx_muon_step": (C.c_int, [C.POINTER(MuonArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),
     "qfx_stream_destroy": (C.c_int, [_vp]),
     "qfx_debug_where": (C.c_int, [_vp, _i32, _vp]),

@@ -436,6 +436,83 @@ def lion8bit_step(p, g, q1, absmax1, m32, layout, qmap1, lr, betas, weight_decay
     L.check(lib.qfx_lion8bit_step(a, stream_ptr()), "qfx_lion8bit_step")
 
 
+MUON_ADJUST_LR = (None, "original", "match_rms_adamw")
+MUON_MAX_SHORT_SIDE = 96
+
+
+class MuonLayout:
+    """Descriptor table of one flat-buffer layout for qfx_muon_step, built once per layout.  `tensors[i]` = (off, rows, cols, lr
+    ratio) of matrix i; extent: elements p / g / buf need; ws_bytes: what the bf16 workspace needs (0 when every X fits LDS)."""
+
+    def __init__(self, table, tensors, extent, ws_bytes, adjust_lr_fn):
+        self.table, self.tensors, self.extent, self.ws_bytes, self.adjust_lr_fn = table, tensors, extent, ws_bytes, adjust_lr_fn
+        self.n_tensors = len(tensors)
+
+
+def muon_lr_ratio(adjust_lr_fn, rows, cols):
+    """torch.optim._muon._adjust_lr's factor on the learning rate of a [rows, cols] matrix."""
+    if adjust_lr_fn not in MUON_ADJUST_LR:
+        raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+    if adjust_lr_fn == "match_rms_adamw":
+        return 0.2 * math.sqrt(max(rows, cols))
+    return math.sqrt(max(1, rows / cols))
+
+
+def muon_table(entries, adjust_lr_fn=None, device=None):
+    """entries: (offset, shape) of every matrix in the flat buffers.  Muon is defined on 2-D parameters only (torch's refusal), and the
+    kernel keeps the Gram matrix of the short side on chip: min(rows, cols) <= 96, which every adapter matrix satisfies."""
+    rows_, tensors, extent = [], [], 0
+    for i, (off, shape) in enumerate(entries):
+        off, shape = int(off), tuple(int(d) for d in shape)
+        if len(shape) != 2:
+            raise ValueError(f"Muon only supports 2D parameters whereas we found a parameter with size: {shape}")
+        r, c = shape
+        if off < 0 or r <= 0 or c <= 0 or r * c > 1 << 30:
+            raise ValueError(f"muon table: entry {i}: offset {off} / shape {shape}")
+        if min(r, c) > MUON_MAX_SHORT_SIDE:
+            raise ValueError(f"muon table: entry {i} has shape {shape}: the short side of a matrix is at most {MUON_MAX_SHORT_SIDE} "
+                             "(an adapter's rank); larger Gram matrices are not implemented")
+        ratio = muon_lr_ratio(adjust_lr_fn, r, c)
+        tensors.append((off, r, c, ratio))
+        rows_.append((off, r, c, ratio, 0))
+        extent = max(extent, off + r * c)
+    if not rows_:
+        raise ValueError("muon table: no tensors")
+    arr = (L.MuonTensor * len(rows_))(*[L.MuonTensor(*r) for r in rows_])
+    ws_bytes = int(lib.qfx_muon_ws_bytes(arr, len(rows_)))
+    if ws_bytes < 0:
+        raise ValueError("muon table: refused by qfx_muon_ws_bytes")
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return MuonLayout(table, tensors, extent, ws_bytes, adjust_lr_fn)
+
+
+def muon_step(p, g, buf, ws, layout, lr, weight_decay=0.1, momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.7750, 2.0315),
+              eps=1e-7, ns_steps=5, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """One Muon step (torch.optim.Muon) over the flat fp32 buffers p / g with the momentum buffer buf; see qfx.h.  layout: a
+    muon_table (the adjust_lr_fn is part of it); ws: bf16 (or int16) workspace of >= layout.ws_bytes bytes, None when that is 0."""
+    for name, t in (("p", p), ("g", g), ("buf", buf)):
+        if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < layout.extent or t.device != p.device:
+            raise ValueError(f"muon_step: {name} must be a contiguous float32 tensor on {p.device} with >= {layout.extent} elements")
+    if layout.table.device != p.device:
+        raise ValueError("muon_step: the descriptor table lives on another device")
+    have = 0
+    if ws is not None:
+        if ws.element_size() != 2 or not ws.is_cuda or not ws.is_contiguous() or ws.device != p.device:
+            raise ValueError(f"muon_step: ws must be a contiguous 2-byte tensor on {p.device}")
+        have = ws.numel() * 2
+    if have < layout.ws_bytes:
+        raise ValueError(f"muon_step: the workspace holds {have} bytes, the layout needs {layout.ws_bytes}")
+    if len(ns_coefficients) != 3:
+        raise ValueError("Coefficients must be a tuple of exactly 3 values")
+    ca, cb, cc = (float(x) for x in ns_coefficients)
+    a = L.MuonArgs(_p(p), _p(g), _p(buf), _p(ws), have, _p(layout.table), layout.n_tensors, int(bool(nesterov)), int(ns_steps),
+                   float(lr), float(weight_decay), float(momentum), 1.0 - float(momentum), ca, cb, cc, float(eps),
+                   _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_muon_step(a, stream_ptr()), "qfx_muon_step")
+
+
 class AdafactorLayout:
     """Descriptor table of one flat-buffer layout for qfx_adafactor_step, built once per layout.  `tensors[i]` = (off, rows, cols,
     factored, first element in row, in col, in v) of entry i (-1 where the entry has none); n_row / n_col / n_v: elements the row /

@@ -1,7 +1,7 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, Lion, Lion8bit, PagedLion8bit) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, Lion, Lion8bit, PagedLion8bit, Muon) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
@@ -18,7 +18,7 @@ import torch
 from .trainer import optim_state as OS
 from .trainer.qwen_step import optimizer_kwargs_from_config
 
-__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit"]
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon"]
 
 
 def _find_store(param_groups):
@@ -205,3 +205,18 @@ class Lion8bit(_FlatOptimizer):
 class PagedLion8bit(Lion8bit):
     """bitsandbytes.optim.PagedLion8bit: paged memory only moves the state, the step is Lion8bit's."""
     _PATH = "qflux_amd.optim.PagedLion8bit"
+
+
+class Muon(_FlatOptimizer):
+    """torch.optim.Muon (momentum, Newton-Schulz orthogonalisation of every adapter matrix's update in bf16, decoupled weight decay,
+    the learning rate adjusted per matrix shape).  eps is Muon's own: the floor of the update's Frobenius norm."""
+    _PATH = "qflux_amd.optim.Muon"
+
+    def __init__(self, params, lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.7750, 2.0315),
+                 eps=1e-7, ns_steps=5, adjust_lr_fn=None):
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
+        super().__init__(params, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, ns_coefficients=ns_coefficients,
+                         eps=eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn)

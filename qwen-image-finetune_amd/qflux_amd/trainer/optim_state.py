@@ -1,7 +1,7 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
 file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
-AdafactorState (transformers.optimization.Adafactor's), LionState (lion_pytorch.Lion's) and LionBlockwiseState (bitsandbytes'
-Lion8bit).
+AdafactorState (transformers.optimization.Adafactor's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
+Lion8bit) and MuonState (torch.optim.Muon's).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
@@ -491,6 +491,86 @@ class LionBlockwiseState(FlatState):
         return state, step
 
 
+class MuonState(FlatState):
+    """torch.optim.Muon: one fp32 momentum buffer indexed like pflat (zeros are the class's initial state), the per-matrix descriptor
+    table of the layout (adjust_lr_fn shapes it: the lr ratio of every matrix is an entry) and the bf16 workspace the table asks for.
+    `eps` is Muon's own (the floor of the Frobenius norm, 1e-7) and lives in the optimizer_args: the train step's Adam eps is unused,
+    and so are betas.  `first` marks a state that has not stepped (torch keeps no state before the first step)."""
+    NAMES = ("buf",)
+    DEFAULTS = dict(momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        dev = store.pflat.device
+        self.layout = ops.muon_table([(off, p.shape) for _, p, off, _ in store.entries], args["adjust_lr_fn"], device=dev)
+        self.buf = torch.zeros_like(store.pflat)
+        self.ws = torch.empty(self.layout.ws_bytes // 2, dtype=torch.bfloat16, device=dev) if self.layout.ws_bytes else None
+        self.first = True
+
+    @classmethod
+    def layout_key(cls, store, args):
+        return super().layout_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries), args["adjust_lr_fn"])
+
+    @staticmethod
+    def validate(args):
+        """torch.optim.Muon's constructor and Newton-Schulz checks, with its messages."""
+        if not 0.0 <= args["momentum"]:
+            raise ValueError(f"momentum should be >= 0 but is: {args['momentum']}")
+        if args["adjust_lr_fn"] not in ops.MUON_ADJUST_LR:
+            raise ValueError(f"Adjust learning rate function {args['adjust_lr_fn']} is not supported")
+        if args["ns_steps"] >= 100:
+            raise ValueError("Number of steps must be less than 100 for computational efficiency")
+        if int(args["ns_steps"]) != args["ns_steps"] or args["ns_steps"] < 0:
+            raise ValueError(f"Invalid ns_steps value: {args['ns_steps']}")
+        if len(args["ns_coefficients"]) != 3:
+            raise ValueError("Coefficients must be a tuple of exactly 3 values")
+        if not float(args["eps"]) > 0.0:
+            raise ValueError(f"Invalid eps value: {args['eps']}")
+        args.update(ns_coefficients=tuple(float(c) for c in args["ns_coefficients"]), eps=float(args["eps"]), ns_steps=int(args["ns_steps"]),
+                    nesterov=bool(args["nesterov"]), momentum=float(args["momentum"]))
+
+    def buffers(self):
+        self.first = False            # listed for a broadcast or a replica check: the state of a run that has stepped
+        return [("buf", self.buf)]
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        self.validate(args)
+        ops.muon_step(store.pflat, store.gflat, self.buf, self.ws, self.layout, lr, weight_decay, args["momentum"], args["nesterov"],
+                      args["ns_coefficients"], args["eps"], args["ns_steps"], gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+        self.first = False
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """torch.optim.Muon's layout: per parameter {"momentum_buffer"} (no state before the first step); the group carries momentum,
+        nesterov, ns_coefficients, eps, ns_steps, adjust_lr_fn next to lr and weight_decay."""
+        group = {n: args[n] for n in cls.DEFAULTS}
+        if state is None or state.first:
+            return group, {}
+        return group, {i: {"momentum_buffer": _out(state.buf, off, k, p.shape)} for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """torch keeps no step count: the train steps' own global_step carries it (0 for a file torch.optim.Muon wrote)."""
+        g = sd["param_groups"][0]
+        for n in cls.DEFAULTS:
+            if n in g:
+                args[n] = g[n]
+        cls.validate(args)
+        if not sd["state"]:
+            return None, 0
+        state = cls(store, args)
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            mb = e["momentum_buffer"]
+            if tuple(mb.shape) != tuple(p.shape):
+                raise ValueError(f"optimizer state of parameter {i}: momentum_buffer has shape {tuple(mb.shape)}, {tuple(p.shape)} expected")
+            state.buf[off:off + k].copy_(mb.reshape(-1).float())
+        state.first = False
+        return state, 0
+
+
 LION = ("lion",) + A8.LION_BLOCKWISE
 
 
@@ -503,7 +583,7 @@ def default_betas(optimizer):
 def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
     state class, weight decay, the family's optimizer_args with defaults filled in)."""
-    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor") + A8.BLOCKWISE + LION:
+    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor", "muon") + A8.BLOCKWISE + LION:
         raise ValueError(f"unknown optimizer {optimizer!r}")
     alias = None
     # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / SGD; Prodigy
@@ -522,10 +602,11 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         weight_decay = 0.0
         alias, optimizer = optimizer, "adamw"
     if weight_decay is None:
-        weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.0
+        weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.1 if optimizer == "muon" else 0.0      # torch.optim.Muon's 0.1
     blockwise = optimizer in A8.BLOCKWISE + A8.LION_BLOCKWISE
     cls = (LionBlockwiseState if optimizer in A8.LION_BLOCKWISE else BlockwiseState) if blockwise else \
-        {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState, "lion": LionState}[optimizer]
+        {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState, "lion": LionState,
+         "muon": MuonState}[optimizer]
     if blockwise:
         args = dict(min_8bit_size=4096, blocksize=256)
     elif optimizer == "lion":
@@ -534,11 +615,13 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         args = dict(SgdState.DEFAULTS)
     elif optimizer == "adafactor":
         args = dict(AdafactorState.DEFAULTS)
+    elif optimizer == "muon":
+        args = dict(MuonState.DEFAULTS)
     else:
         args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                     growth_rate=float("inf"))
     unknown = set(optimizer_args or {}) - set(args)
-    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor") + A8.BLOCKWISE + A8.LION_BLOCKWISE):
+    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor", "muon") + A8.BLOCKWISE + A8.LION_BLOCKWISE):
         raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
     args.update(optimizer_args or {})
     if blockwise:
@@ -549,6 +632,8 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         SgdState.validate(args)
     if optimizer == "adafactor":
         AdafactorState.validate(args)
+    if optimizer == "muon":
+        MuonState.validate(args)
     return alias, optimizer, cls, weight_decay, args
 
 

@@ -68,6 +68,10 @@ class QwenLoraTrainStep:
         moment; weight decay decoupled, before the update, default 0); no optimizer_args; eps unused.  "lion8bit_blockwise":
         bitsandbytes.optim.Lion8bit / PagedLion8bit with the moment in blockwise 8-bit codes and bnb's one-state layout;
         optimizer_args: min_8bit_size (4096), blocksize (256 or 2048).
+        "muon": torch.optim.Muon (per adapter matrix: Nesterov momentum, then five Newton-Schulz iterations in bf16 on the matrix
+        units orthogonalise the update; weight decay decoupled, default the class's 0.1); optimizer_args: momentum (0.95), nesterov
+        (True), ns_coefficients ((3.4445, -4.7750, 2.0315)), ns_steps (5), adjust_lr_fn (None = "original", or "match_rms_adamw") and
+        eps (1e-7: Muon's own, the floor of the update's norm, not this constructor's Adam eps); betas / eps unused.
         betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, (0.9, 0.999) --
         torch.optim.AdamW's, this constructor's default before Lion -- for every other one; betas given explicitly are never
         reinterpreted.
@@ -457,9 +461,11 @@ _OWN_CLASSES = {"qflux_amd.optim.AdamW": ("torch.optim.AdamW", 32), "qflux_amd.o
                 "qflux_amd.optim.Adam8bit": ("bitsandbytes.optim.Adam8bit", 8), "qflux_amd.optim.AdamW8bit": ("bitsandbytes.optim.AdamW8bit", 8),
                 "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0),
                 "qflux_amd.optim.Adafactor": ("transformers.optimization.Adafactor", 0),
+                "qflux_amd.optim.Muon": ("torch.optim.Muon", 0),
                 "qflux_amd.optim.Lion8bit": ("bitsandbytes.optim.Lion8bit", 8),
                 "qflux_amd.optim.PagedLion8bit": ("bitsandbytes.optim.PagedLion8bit", 8)}
 _ADAFACTOR = ("transformers.optimization.Adafactor", "transformers.Adafactor")
+_MUON = ("torch.optim.Muon",)
 _LION = ("lion_pytorch.Lion", "bitsandbytes.optim.Lion", "bitsandbytes.optim.Lion32bit")
 _BNB_LION_8BIT = ("bitsandbytes.optim.Lion8bit", "bitsandbytes.optim.PagedLion8bit")
 _BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
@@ -492,6 +498,9 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     qflux_amd.optim.Lion8bit / PagedLion8bit always map to the blockwise form.  The path qflux_amd.optim.Lion itself is NOT mapped
     here and keeps raising (tests/test_optim_classes_cpu.py pins that refusal): the class exists and steps "lion", a config for the
     fused train step names lion_pytorch.Lion, whose keywords it takes.
+        torch.optim.Muon / qflux_amd.optim.Muon -> optimizer="muon" + optimizer_args (momentum, nesterov, ns_coefficients, eps,
+    ns_steps, adjust_lr_fn); weight decay left out is the class's 0.1; ns_steps >= 100 and an unknown adjust_lr_fn are refused with
+    torch's messages.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -513,6 +522,15 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         if "eps" in out["optimizer_args"]:
             out["optimizer_args"]["eps"] = tuple(float(e) for e in out["optimizer_args"]["eps"])
         OS.AdafactorState.validate(dict(OS.AdafactorState.DEFAULTS, **out["optimizer_args"]), out["lr"])
+    if class_path in _MUON:
+        # eps is Muon's own (the norm's floor), one of the family's optimizer_args next to the Newton-Schulz settings
+        out["optimizer"] = "muon"
+        if "betas" in a:
+            raise NotImplementedError(f"unsupported optimizer init_args for {given}: ['betas']")
+        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in OS.MuonState.DEFAULTS}
+        OS.MuonState.validate(dict(OS.MuonState.DEFAULTS, **out["optimizer_args"]))
+        if "ns_coefficients" in out["optimizer_args"]:
+            out["optimizer_args"]["ns_coefficients"] = tuple(float(c) for c in out["optimizer_args"]["ns_coefficients"])
     for k in ("lr", "eps", "weight_decay"):
         if k in a:
             out[k] = float(a.pop(k))
@@ -550,7 +568,7 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
             raise NotImplementedError(f"{given}: maximize=True is not implemented")
         out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("momentum", "dampening", "nesterov")}
         a.pop("differentiable", None)
-    elif class_path in _ADAFACTOR:
+    elif class_path in _ADAFACTOR + _MUON:
         pass
     elif class_path == "prodigyopt.Prodigy":
         out["optimizer"] = "prodigy"
