@@ -292,6 +292,19 @@ int qfx_mod_gemv(const uint16_t* temb, int32_t B, int32_t K, const uint16_t* con
                  int32_t nmat, int32_t N, int32_t apply_silu, uint16_t* out, void* stream);
 /* W, bias: DEVICE arrays of nmat device pointers. apply_silu=0 gives a plain small-batch Linear
  * (timestep_embedder.linear_1). B <= 8. */
+/* The same launch guarded by a device flag: every block returns before it touches anything when *skip != 0; with skip == NULL or
+ * *skip == 0 it is qfx_mod_gemv bit for bit (one kernel).  The flag is the `hit` cell of qfx_mod_table_fetch. */
+int qfx_mod_gemv_unless(const uint16_t* temb, int32_t B, int32_t K, const uint16_t* const* W, const uint16_t* const* bias,
+                        int32_t nmat, int32_t N, int32_t apply_silu, uint16_t* out, const int32_t* skip, void* stream);
+/* Modulation table of a frozen conditioning head: row i of tbl_mods ([n] rows of [nmat][N], ld_mods elements apart) and of tbl_out
+ * ([n] rows of [N_out], ld_out apart) holds what the qfx_timestep_embed -> qfx_mod_gemv chain writes for the timestep keys[i].
+ * Keys match as fp32 WORDS (NaN never hits, -0.0 is not 0.0).  Iff every one of the B timesteps t[b] is a key, sample b's rows are
+ * copied to mods[mat][b][:] ([nmat][B][N]) and mod_out[b][:] ([B][N_out]) -- the layout of qfx_mod_gemv -- and *hit = 1; otherwise
+ * *hit = 0 and neither destination is written.  Decided on the device: nothing reads the flag on the host.  B <= 8, n >= 1; the
+ * four bf16 bases 16-byte aligned (rows that are not take the element-wise path). */
+int qfx_mod_table_fetch(const float* t, int32_t B, const float* keys, int32_t n, const uint16_t* tbl_mods, int64_t ld_mods,
+                        int32_t nmat, int32_t N, const uint16_t* tbl_out, int64_t ld_out, int32_t N_out, uint16_t* mods,
+                        uint16_t* mod_out, int32_t* hit, void* stream);
 /* Backward of the same frozen linears w.r.t. their (shared) input, needed when the conditioning head carries adapters
  * (target_modules "all-linear", configs/example_with_sampling.yaml:9): out[b, k] (fp32 [B, K], zeroed by the caller) +=
  * sum_mat sum_n dy[mat, b, n] * W_mat[n, k], dy bf16 [nmat, B, N] -- what autograd computes as dy @ W per module and sums.

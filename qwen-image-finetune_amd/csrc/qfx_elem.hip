@@ -407,7 +407,10 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restri
 __global__ __launch_bounds__(256) void mod_gemv_kernel(const bf16_t* __restrict__ temb, int B, int K,
                                                        const bf16_t* const* __restrict__ Ws,
                                                        const bf16_t* const* __restrict__ biases, int N,
-                                                       int apply_silu, bf16_t* __restrict__ out) {
+                                                       int apply_silu, bf16_t* __restrict__ out,
+                                                       const int* __restrict__ skip) {
+  // qfx_mod_gemv_unless: the modulation table served this step (mod_table_fetch_kernel wrote *skip = 1) -- nothing to compute
+  if (skip && *skip) return;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   bf16_t* sT = (bf16_t*)smem_raw;  // [B][K] bf16(silu(temb))
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -459,6 +462,63 @@ __global__ __launch_bounds__(256) void mod_gemv_kernel(const bf16_t* __restrict_
 #pragma unroll
         for (int b = 0; b < 8; ++b)
           if (b < B) out[((int64_t)mat * B + b) * N + n] = f2bf(acc[r][b] + bv);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- modulation table fetch (frozen conditioning head)
+// Without adapters on the conditioning head the modulation vectors are a pure function of the timestep, and training draws it from
+// a fixed list (FlowMatchEulerDiscreteScheduler.timesteps): the model keeps the rows mod_gemv_kernel writes for every key.  When ALL
+// B timesteps are keys (fp32 words compared as bits: NaN never hits, -0.0 is not 0.0), sample b's [nmat][N] row lands in
+// mods[mat][b][:] and its [N_out] row in mod_out[0][b][:] -- the layout mod_gemv_kernel writes -- and *hit = 1; otherwise *hit = 0
+// and neither destination is touched.  Every block repeats the key search (n words, L2-resident) instead of a grid-wide handshake.
+__global__ __launch_bounds__(256) void mod_table_fetch_kernel(const uint32_t* __restrict__ t, int B, const uint32_t* __restrict__ keys,
+                                                              int n, const bf16_t* __restrict__ tbl_mods, int64_t ld_mods, int nmat,
+                                                              int N, const bf16_t* __restrict__ tbl_out, int64_t ld_out, int N_out,
+                                                              bf16_t* __restrict__ mods, bf16_t* __restrict__ mod_out,
+                                                              int* __restrict__ hit) {
+  __shared__ int s_idx[8];
+  const int tid = threadIdx.x;
+  if (tid < 8) s_idx[tid] = n;
+  __syncthreads();
+  uint32_t tb[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b) tb[b] = b < B ? t[b] : 0u;
+  for (int i = tid; i < n; i += 256) {
+    const uint32_t kv = keys[i];
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+      if (b < B && kv == tb[b]) atomicMin(&s_idx[b], i);    // a repeated key: its first row
+  }
+  __syncthreads();
+  bool all = true;
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+    if (b < B) all = all && s_idx[b] < n && (tb[b] & 0x7fffffffu) <= 0x7f800000u;   // a NaN word never hits, whatever the keys hold
+  if (blockIdx.x == 0 && tid == 0) *hit = all ? 1 : 0;
+  if (!all) return;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int part = 0; part < 2; ++part) {
+    const bf16_t* tbl = part ? tbl_out : tbl_mods;
+    bf16_t* dst0 = part ? mod_out : mods;
+    const int64_t ld = part ? ld_out : ld_mods;
+    const int nm = part ? 1 : nmat, len = part ? N_out : N;
+    const int cpr = (len + 7) / 8;                           // 8-element pieces per row, the last one possibly short
+    const int64_t total = (int64_t)B * nm * cpr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < total; i += stride) {
+      const int c = (int)(i % cpr);
+      const int row = (int)(i / cpr);
+      const int mat = row % nm, b = row / nm;
+      const int64_t so = (int64_t)s_idx[b] * ld + (int64_t)mat * len, d_o = ((int64_t)mat * B + b) * len;
+      const bf16_t* src = tbl + so;
+      bf16_t* dst = dst0 + d_o;
+      const int e0 = c * 8;
+      if (e0 + 8 <= len && ((so | d_o) & 7) == 0) {          // 16-byte piece of a 16-byte aligned row pair
+        *(uint4*)(dst + e0) = *(const uint4*)(src + e0);
+      } else {
+        const int e1 = e0 + 8 < len ? e0 + 8 : len;
+        for (int e = e0; e < e1; ++e) dst[e] = src[e];
       }
     }
   }
@@ -1297,7 +1357,34 @@ extern "C" int qfx_mod_gemv(const uint16_t* temb, int32_t B, int32_t K, const ui
   const size_t lds = (size_t)B * K * 2;
   if (lds > 64 * 1024) return QFX_EUNSUPPORTED;
   hipLaunchKernelGGL(mod_gemv_kernel, dim3((N + 15) / 16, nmat), dim3(256), lds, (hipStream_t)stream, temb, B, K, W, bias, N,
-                     apply_silu, out);
+                     apply_silu, out, (const int*)nullptr);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int qfx_mod_gemv_unless(const uint16_t* temb, int32_t B, int32_t K, const uint16_t* const* W, const uint16_t* const* bias,
+                                   int32_t nmat, int32_t N, int32_t apply_silu, uint16_t* out, const int32_t* skip, void* stream) {
+  if (!temb || !W || !out || B <= 0 || B > 8 || K <= 0 || (K % 8) || nmat <= 0 || N <= 0) return QFX_EINVAL;
+  const size_t lds = (size_t)B * K * 2;
+  if (lds > 64 * 1024) return QFX_EUNSUPPORTED;
+  hipLaunchKernelGGL(mod_gemv_kernel, dim3((N + 15) / 16, nmat), dim3(256), lds, (hipStream_t)stream, temb, B, K, W, bias, N,
+                     apply_silu, out, (const int*)skip);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int qfx_mod_table_fetch(const float* t, int32_t B, const float* keys, int32_t n, const uint16_t* tbl_mods, int64_t ld_mods,
+                                   int32_t nmat, int32_t N, const uint16_t* tbl_out, int64_t ld_out, int32_t N_out, uint16_t* mods,
+                                   uint16_t* mod_out, int32_t* hit, void* stream) {
+  if (!t || !keys || !tbl_mods || !tbl_out || !mods || !mod_out || !hit || B <= 0 || B > 8 || n < 1 || nmat <= 0 || N <= 0 ||
+      N_out <= 0 || ld_mods < (int64_t)nmat * N || ld_out < N_out)
+    return QFX_EINVAL;
+  if ((((uintptr_t)tbl_mods | (uintptr_t)tbl_out | (uintptr_t)mods | (uintptr_t)mod_out) & 15) || ((uintptr_t)hit & 3)) return QFX_EINVAL;
+  const int64_t pieces = (int64_t)B * ((int64_t)nmat * ((N + 7) / 8) + (N_out + 7) / 8);
+  int blocks = (int)((pieces + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(mod_table_fetch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)t, B,
+                     (const uint32_t*)keys, n, tbl_mods, ld_mods, nmat, N, tbl_out, ld_out, N_out, mods, mod_out, (int*)hit);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

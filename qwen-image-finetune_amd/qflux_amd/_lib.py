@@ -234,6 +234,8 @@ SYMBOLS = {
     "qfx_rmsnorm_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _f, _vp]),
     "qfx_mod_gemv": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "qfx_mod_gemv_t": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "qfx_mod_gemv_unless": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "qfx_mod_table_fetch": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "qfx_timestep_embed": (C.c_int, [_vp, _i32, _i32, _f, _f, _vp, _vp]),
     "qfx_cond_lora_fwd": (C.c_int, [C.POINTER(CondLoraArgs), _vp]),
     "qfx_cond_lora_bwd": (C.c_int, [C.POINTER(CondLoraArgs), _vp]),

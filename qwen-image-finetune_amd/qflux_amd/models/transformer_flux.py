@@ -103,6 +103,7 @@ class FluxTransformer2DModel(QwenImageTransformer2DModel):
         self._rope_cache = {}
 
     _HEAD_SITES = {"x_embedder": "x_in", "context_embedder": "c_in", "proj_out": "proj_out"}
+    _MOD_TABLE = False    # temb also depends on guidance and the pooled text: no per-timestep modulation table
 
     _COND_SUFFIXES = ("timestep_embedder.linear_1", "timestep_embedder.linear_2", "guidance_embedder.linear_1", "guidance_embedder.linear_2",
                       "text_embedder.linear_1", "text_embedder.linear_2", "norm1.linear", "norm1_context.linear", "norm.linear",

@@ -157,6 +157,8 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._wq_cache = {}        # ... and the quantised copies of the frozen weights, shared by the model's plans
         self._version = 0
         self._adapter_gen = 0      # bumped ONLY by add_adapter / load_lora_adapter / load_state_dict: what a data-parallel resync keys on
+        self._mod_keys = None      # timestep keys of the modulation table (None: the flow-match training timesteps / 1000)
+        self._mod_table = None     # None: not decided; False: decided against; dict(keys, mods, out): see ensure_modulation_table
 
     # ------------------------------------------------------------------ reference-surface methods
     @classmethod
@@ -230,6 +232,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
 
     def _invalidate(self):
         self._prepared = None
+        self._mod_table = None     # rows computed from the prepared frozen weights
         self._lora_prep = None
         self._plans = PlanCache()
         self._wq_cache = {}
@@ -381,6 +384,93 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._plans = PlanCache()
         self._version += 1
         return self
+
+    # ------------------------------------------------------------------ modulation table (frozen conditioning head)
+    _MOD_TABLE = True     # (the FLUX head also depends on guidance and pooled text: no table there)
+
+    @staticmethod
+    def modulation_table_bytes(n_keys: int, num_layers: int, dim: int) -> int:
+        """bf16 rows of one key: [2 * num_layers][6 * dim] modulation vectors + [2 * dim] of norm_out."""
+        return n_keys * (2 * num_layers * 6 * dim + 2 * dim) * 2
+
+    @staticmethod
+    def modulation_table_levers(env=None):
+        """(QFX_MOD_TABLE: on unless "0", QFX_MOD_TABLE_GB: size cap in GB, default 8)."""
+        env = os.environ if env is None else env
+        cap = float(env.get("QFX_MOD_TABLE_GB", "8"))
+        if not cap >= 0:
+            raise ValueError(f"QFX_MOD_TABLE_GB={env.get('QFX_MOD_TABLE_GB')!r}: a non-negative number of GB")
+        return env.get("QFX_MOD_TABLE", "1") != "0", cap
+
+    def _modulation_keys(self):
+        if self._mod_keys is None:
+            from ..trainer.qwen_step import flowmatch_tables
+            return (flowmatch_tables()[0] / 1000).to(F32).contiguous()
+        return self._mod_keys
+
+    def set_modulation_keys(self, keys):
+        """The timesteps (as the forward receives them: sigma-scaled, fp32) the modulation table holds rows for.  Other keys than
+        the current ones drop an existing table."""
+        keys = torch.as_tensor(keys).detach().to("cpu", F32).reshape(-1).contiguous().clone()
+        if keys.numel() < 1:
+            raise ValueError("set_modulation_keys: at least one key")
+        if not torch.equal(keys.view(torch.int32), self._modulation_keys().view(torch.int32)):
+            self.drop_modulation_table()
+        self._mod_keys = keys
+
+    def drop_modulation_table(self):
+        """Free the table; plans that fetch from it are dropped with it.  The next training use builds it again."""
+        if self._mod_table:
+            self._plans = PlanCache()
+            self._version += 1
+        self._mod_table = None
+
+    @property
+    def modulation_table(self):
+        """dict(keys [n] fp32, mods [n, 2L, 6D], out [n, 2D]) when the table exists, else None."""
+        return self._mod_table or None
+
+    def ensure_modulation_table(self) -> bool:
+        """Build the per-timestep table of the AdaLN modulation vectors if it is allowed and missing; True when it exists.
+        The conditioning head (timestep embedding -> linear_1 -> silu -> linear_2 -> silu -> every img_mod / txt_mod, norm_out.linear)
+        is a function of the timestep alone, and without adapters on it its weights never change: the 13.6 GB weight stream of the
+        big qfx_mod_gemv launch is replaced by a row copy (qfx_mod_table_fetch).  Rows come from the same launches the step
+        runs, in batches of 8 keys (a row of qfx_mod_gemv does not depend on the batch it was computed in), so a hit is bit-identical
+        to the computed path.  Training entry points call this; inference never builds a table but uses one that exists."""
+        if self._mod_table is not None:
+            return bool(self._mod_table)
+        self._mod_table = False
+        if not self._MOD_TABLE or self.device.type != "cuda" or self.cond_lora:
+            return False
+        on, cap_gb = self.modulation_table_levers()
+        keys = self._modulation_keys()
+        Lyr, D = self.config.num_layers, self.inner_dim
+        if not on or self.modulation_table_bytes(keys.numel(), Lyr, D) > cap_gb * 1e9:
+            return False
+        P = self._prepare()
+        dev, n = self.device, keys.numel()
+        kd = keys.to(dev)
+        mods_t = torch.empty(n, 2 * Lyr, 6 * D, dtype=BF, device=dev)
+        out_t = torch.empty(n, 2 * D, dtype=BF, device=dev)
+        tproj, t1, temb = (torch.empty(8, w, dtype=BF, device=dev) for w in (256, D, D))
+        mods, mo = torch.empty(2 * Lyr * 8 * 6 * D, dtype=BF, device=dev), torch.empty(8 * 2 * D, dtype=BF, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        for i0 in range(0, n, 8):
+            B = min(8, n - i0)
+            for rc in (lib.qfx_timestep_embed(kd[i0:].data_ptr(), B, 256, 1000.0, 1.0, tproj.data_ptr(), st),
+                       lib.qfx_mod_gemv(tproj.data_ptr(), B, 256, P["t1_Wp"].data_ptr(), P["t1_bp"].data_ptr(), 1, D, 0, t1.data_ptr(), st),
+                       lib.qfx_mod_gemv(t1.data_ptr(), B, D, P["t2_Wp"].data_ptr(), P["t2_bp"].data_ptr(), 1, D, 1, temb.data_ptr(), st),
+                       lib.qfx_mod_gemv(temb.data_ptr(), B, D, P["mod_W"].data_ptr(), P["mod_b"].data_ptr(), 2 * Lyr, 6 * D, 1,
+                                        mods.data_ptr(), st),
+                       lib.qfx_mod_gemv(temb.data_ptr(), B, D, P["norm_out_Wp"].data_ptr(), P["norm_out_bp"].data_ptr(), 1, 2 * D, 1,
+                                        mo.data_ptr(), st)):
+                L.check(rc, "modulation table build")
+            mods_t[i0:i0 + B].copy_(mods[:2 * Lyr * B * 6 * D].view(2 * Lyr, B, 6 * D).transpose(0, 1))
+            out_t[i0:i0 + B].copy_(mo[:B * 2 * D].view(B, 2 * D))
+        self._mod_table = dict(keys=kd, mods=mods_t, out=out_t)
+        self._plans = PlanCache()      # plans built before the table existed compute the vectors
+        self._version += 1
+        return True
 
     def lora_parameters(self):
         return [p for n, p in self.named_parameters() if "lora_" in n]
@@ -584,6 +674,8 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         B, S_i, T = hidden_states.shape[0], hidden_states.shape[1], encoder_hidden_states.shape[1]
         batched = isinstance(img_shapes, list) and len(img_shapes) > 0 and isinstance(img_shapes[0], list)
         ragged = batched and not all(sh == img_shapes[0] for sh in img_shapes)
+        if self.training and torch.is_grad_enabled():
+            self.ensure_modulation_table()      # the drop-in module's first training-mode forward builds it
         if attention_mask is not None or ragged:
             if attention_mask is not None:
                 if attention_mask.dim() != 2:

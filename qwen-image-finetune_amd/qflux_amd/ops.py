@@ -182,6 +182,27 @@ def mod_gemv_tables(temb, wt, bt, nmat, N, apply_silu=True):
     return out
 
 
+def mod_gemv_unless(temb, weights, biases, out, skip, apply_silu=True):
+    """qfx_mod_gemv into `out` [nmat, B, N] unless the device int32 cell `skip` (None: no guard) holds a non-zero value."""
+    B, K = temb.shape
+    N = weights[0].shape[0]
+    wt = ptr_table(weights, temb.device)
+    bt = ptr_table(biases, temb.device) if biases is not None else None
+    L.check(lib.qfx_mod_gemv_unless(_p(temb), B, K, _p(wt), _p(bt), len(weights), N, int(apply_silu), _p(out), _p(skip), stream_ptr()),
+            "qfx_mod_gemv_unless")
+    return out
+
+
+def mod_table_fetch(t, keys, tbl_mods, tbl_out, mods, mod_out, hit):
+    """Serve mods [nmat, B, N] / mod_out [B, N_out] from the table rows (tbl_mods [n, nmat, N], tbl_out [n, N_out]) of the fp32
+    timesteps t [B] when every one of them is in keys [n]; the device int32 cell `hit` tells which way it went."""
+    n, nmat, N = tbl_mods.shape
+    L.check(lib.qfx_mod_table_fetch(_p(t), t.shape[0], _p(keys), n, _p(tbl_mods), tbl_mods.stride(0), nmat, N, _p(tbl_out),
+                                    tbl_out.stride(0), tbl_out.shape[1], _p(mods), _p(mod_out), _p(hit), stream_ptr()),
+            "qfx_mod_table_fetch")
+    return hit
+
+
 def mod_gemv_t(dy, weights=None, out=None, table=None):
     """out[b, k] += sum_mat dy[mat, b, :] @ W_mat  (fp32 [B, K]); dy bf16 [nmat, B, N] contiguous; weights: list of [N, K] bf16
     tensors, or table = (prepared device pointer table, K)."""

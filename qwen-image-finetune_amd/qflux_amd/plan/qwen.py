@@ -375,6 +375,20 @@ class _QwenPlan:
         p.c(lib.qfx_timestep_embed, _ptr(A["t"]), B, 256, 1000.0, 1.0, _ptr(A["tproj"]))
         if self.cond:   # adapters on the conditioning head: base GEMVs + the banks' rank-r launches (cond_hip.py)
             self.cond_head.emit_forward(p)
+        elif model.modulation_table is not None:
+            # frozen head + a per-timestep table of its outputs (model.ensure_modulation_table): the fetch serves mods / mod_out when
+            # every sample's timestep is a key and raises the hit cell, on which the four GEMVs return at once; an off-table
+            # timestep leaves the cell at 0 and they run as ever.  Decided on the device: the program stays a static launch list.
+            tb = self.mod_table = model.modulation_table      # (keeps the rows alive as long as this plan)
+            A["mod_hit"] = self.buf(1, dtype=torch.int32, zero=True)
+            hit = _ptr(A["mod_hit"])
+            p.c(lib.qfx_mod_table_fetch, _ptr(A["t"]), B, _ptr(tb["keys"]), tb["keys"].numel(), _ptr(tb["mods"]), tb["mods"].stride(0),
+                2 * Lyr, 6 * D, _ptr(tb["out"]), tb["out"].stride(0), 2 * D, _ptr(A["mods"]), _ptr(A["mod_out"]), hit)
+            p.c(lib.qfx_mod_gemv_unless, _ptr(A["tproj"]), B, 256, _ptr(P["t1_Wp"]), _ptr(P["t1_bp"]), 1, D, 0, _ptr(A["t1"]), hit)
+            p.c(lib.qfx_mod_gemv_unless, _ptr(A["t1"]), B, D, _ptr(P["t2_Wp"]), _ptr(P["t2_bp"]), 1, D, 1, _ptr(A["temb"]), hit)
+            p.c(lib.qfx_mod_gemv_unless, _ptr(A["temb"]), B, D, _ptr(P["mod_W"]), _ptr(P["mod_b"]), 2 * Lyr, 6 * D, 1, _ptr(A["mods"]), hit)
+            p.c(lib.qfx_mod_gemv_unless, _ptr(A["temb"]), B, D, _ptr(P["norm_out_Wp"]), _ptr(P["norm_out_bp"]), 1, 2 * D, 1,
+                _ptr(A["mod_out"]), hit)
         else:
             p.c(lib.qfx_mod_gemv, _ptr(A["tproj"]), B, 256, _ptr(P["t1_Wp"]), _ptr(P["t1_bp"]), 1, D, 0, _ptr(A["t1"]))
             p.c(lib.qfx_mod_gemv, _ptr(A["t1"]), B, D, _ptr(P["t2_Wp"]), _ptr(P["t2_bp"]), 1, D, 1, _ptr(A["temb"]))

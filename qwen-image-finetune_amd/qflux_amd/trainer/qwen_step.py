@@ -94,6 +94,11 @@ class QwenLoraTrainStep:
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         self.timesteps_tbl, self.sigmas_tbl = flowmatch_tables()
+        # frozen conditioning head: the AdaLN modulation vectors of every training timestep, computed once here so that no step pays
+        # for it (dit.ensure_modulation_table; QFX_MOD_TABLE=0 / QFX_MOD_TABLE_GB; nothing happens with adapters on the head)
+        if getattr(dit, "_MOD_TABLE", False):
+            dit.set_modulation_keys(self.timesteps_tbl / 1000)
+            dit.ensure_modulation_table()
         self.global_step = 0
         self._gnorm = self._gparts = None
         # data-parallel exchange overlapped with the backward: the flat gradient is all-reduced in buckets of whole DiT
@@ -150,6 +155,12 @@ class QwenLoraTrainStep:
         t_in = (timesteps / 1000).to(dev, non_blocking=True)
         return packed, target, pe, t_in, x0.shape[1]
 
+    def _ensure_mod_table(self):
+        """The modulation table again after the model dropped it (load_state_dict, merge / unmerge, a move): one attribute test when
+        it is in place or decided against."""
+        if getattr(self.dit, "_MOD_TABLE", False):
+            self.dit.ensure_modulation_table()
+
     # ------------------------------------------------------------------ drop-in (autograd) path
     def compute_loss(self, embeddings, noise=None, u=None):
         packed, target, pe, t_in, S_t = self._prepare(embeddings, noise, u)
@@ -175,6 +186,7 @@ class QwenLoraTrainStep:
         sync=False = accelerator.accumulate()/no_sync micro-step (base_trainer.py:518): no gradient exchange is started; pass
         sync=True on the last micro-step of the window (the buckets then carry the accumulated sums)."""
         packed, target, pe, t_in, S_t = self._prepare(embeddings, noise, u)
+        self._ensure_mod_table()
         plan = self.dit.get_plan(packed.shape[0], packed.shape[1], pe.shape[1], embeddings["img_shapes"], None)
         return self._fused_pass(plan, packed, pe, t_in, target, S_t, grad_scale, sync, embeddings)
 
@@ -210,6 +222,7 @@ class QwenLoraTrainStep:
             raise NotImplementedError("capture_graph: the mask_edit criterion takes per-step token weights; use train_step")
         dit = self.dit
         packed, target, pe, t_in, S_t = self._prepare(embeddings)
+        self._ensure_mod_table()
         plan = dit.get_plan(packed.shape[0], packed.shape[1], pe.shape[1], embeddings["img_shapes"], None)
         dit.lora_store
         self._ensure_synced()      # outside the capture: a job driven only by the captured step still starts from rank 0's state
