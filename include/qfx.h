@@ -653,6 +653,36 @@ typedef struct qfx_lion8bit_args {
 } qfx_lion8bit_args;
 int qfx_lion8bit_step(const qfx_lion8bit_args* a, void* stream);
 
+/* ---- Schedule-Free AdamW (Defazio et al., "The Road Less Scheduled", 2024; third party schedulefree.AdamWScheduleFree, the method
+ * made for the constant learning rate the reference's configs run (lr_scheduler.scheduler_type: constant / constant_with_warmup);
+ * in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909, stepped at :531 after
+ * clip_gradients :449-455).  The parameters exist in two forms: y, where the gradient is taken (the parameter buffer in train
+ * mode), and the averaged x that is sampled from and saved (the parameter buffer in eval mode); z is the base sequence.
+ * qfx_sfadamw_step: ONE launch over the flat LoRA buffers.  The caller forms the group's scalars in double as the package does
+ * (k counts steps from 0): lr_t = lr * min(1, (k + 1) / warmup_steps), bias_corr2 = 1 - beta2^(k + 1), lr_max = max(lr_t, lr_max),
+ * weight = (k + 1)^r * lr_max^weight_lr_power, weight_sum += weight, ckp1 = weight / weight_sum (0 when weight_sum == 0).  Per
+ * element, with g' = g * clip (clip exactly as qfx_adamw_step computes it from gnorm_sq / max_norm / grad_scale), everything in
+ * fp32, every operation rounded on its own (never contracted into an FMA), 1 - beta2 and 1 - ckp1 formed in fp32, and
+ * ylr = lr_t (beta1 (1 - ckp1) - 1) formed in double from the arguments and rounded once:
+ *   v  = v beta2 + ((1 - beta2) g') g'
+ *   gn = g' / (sqrt(v / bias_corr2) + eps)
+ *   gn = gn + weight_decay y                  (only when weight_decay != 0)
+ *   y  = lerp(y, z, ckp1)                      (torch.lerp: y + ckp1 (z - y) for |ckp1| < 0.5, else z - (z - y)(1 - ckp1))
+ *   y  = y + ylr gn
+ *   z  = z - lr_t gn
+ * `first` != 0 on the step that creates the state: the kernel takes z = y (as it was before the step) and v = 0 instead of reading
+ * them (their contents are then ignored), like qfx_sgd_step's `first`.  There is no non-finite guard: the package has none.
+ * 16-byte accesses when p, g, z and v are 16-byte aligned, scalar ones otherwise and for the n % 4 tail.
+ * qfx_sf_swap: p = lerp(p, z, weight), the same formula with both branches; weight = 1 - 1 / beta1 turns y into x (eval),
+ * weight = 1 - beta1 turns x back into y (train).  The caller refuses beta1 == 0 (the first weight would divide by zero).
+ * No atomics: same inputs -> same bits.  Rejected with QFX_EINVAL before any launch: a NULL p, g, z or v, n <= 0, a negative lr_t, a
+ * beta outside [0, 1), a negative weight_decay or eps, bias_corr2 <= 0, ckp1 outside [0, 1]; for the swap a NULL p or z, n <= 0 or
+ * a weight that is not finite. ---- */
+int qfx_sfadamw_step(float* p, const float* g, float* z, float* v, int64_t n, float lr_t, float beta1, float beta2, float eps,
+                     float weight_decay, float bias_corr2, float ckp1, int32_t first, const float* gnorm_sq /* may be NULL */,
+                     float max_norm, float grad_scale, void* stream);
+int qfx_sf_swap(float* p, const float* z, int64_t n, float weight, void* stream);
+
 /* ---- Muon (Jordan et al., "Muon: An optimizer for hidden layers in neural networks", 2024; torch.optim.Muon, the one mainstream
  * optimizer defined per MATRIX; in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909,
  * stepped at :531 after clip_gradients :449-455).  ONE launch, one workgroup per adapter matrix, driven by a device table.  Per

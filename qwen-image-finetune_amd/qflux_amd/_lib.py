@@ -265,6 +265,8 @@ SYMBOLS = {
     "qfx_adafactor_step": (C.c_int, [C.POINTER(AdafactorArgs), _vp]),
     "qfx_lion_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _f, _f, _vp]),
     "qfx_lion8bit_step": (C.c_int, [C.POINTER(Lion8bitArgs), _vp]),
+    "qfx_sfadamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i32, _vp, _f, _f, _vp]),
+    "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
     "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),
     "qfx_muon_step": (C.c_int, [C.POINTER(MuonArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),

@@ -457,6 +457,42 @@ def lion8bit_step(p, g, q1, absmax1, m32, layout, qmap1, lr, betas, weight_decay
     L.check(lib.qfx_lion8bit_step(a, stream_ptr()), "qfx_lion8bit_step")
 
 
+def sfadamw_schedule(k, lr, beta2, warmup_steps, r, weight_lr_power, lr_max, weight_sum):
+    """The group scalars of Schedule-Free AdamW's step k (counted from 0), in Python doubles as schedulefree.AdamWScheduleFree forms
+    them: (lr_t, bias_corr2, ckp1, lr_max, weight_sum) with the two running values updated."""
+    sched = (k + 1) / warmup_steps if k < warmup_steps else 1.0
+    bc2 = 1 - beta2 ** (k + 1)
+    lr_t = lr * sched
+    lr_max = max(lr_t, lr_max)
+    weight = ((k + 1) ** r) * (lr_max ** weight_lr_power)
+    weight_sum = weight_sum + weight
+    ckp1 = weight / weight_sum if weight_sum != 0 else 0.0
+    return lr_t, bc2, ckp1, lr_max, weight_sum
+
+
+def _sf_check(what, p, others):
+    for name, t in (("p", p),) + others:
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < p.numel() or t.device != p.device:
+            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor on {p.device} with >= {p.numel()} elements")
+
+
+def sfadamw_step(p, g, z, v, lr_t, beta1, beta2, eps, weight_decay, bias_corr2, ckp1, first=False, gnorm_sq=None, max_norm=0.0,
+                 grad_scale=1.0):
+    """One Schedule-Free AdamW step (schedulefree.AdamWScheduleFree) over the flat fp32 buffers: p holds y, z the base sequence, v
+    exp_avg_sq; lr_t, bias_corr2 and ckp1 from sfadamw_schedule; first: z = y and v = 0 are taken, not read; see qfx.h."""
+    _sf_check("sfadamw_step", p, (("g", g), ("z", z), ("v", v)))
+    L.check(lib.qfx_sfadamw_step(_p(p), _p(g), _p(z), _p(v), p.numel(), lr_t, beta1, beta2, eps, weight_decay, bias_corr2, ckp1,
+                                 int(bool(first)), _p(gnorm_sq), max_norm, grad_scale, stream_ptr()), "qfx_sfadamw_step")
+
+
+def sf_swap(p, z, beta1, to_eval):
+    """Schedule-free mode swap in place: y -> x = lerp(y, z, 1 - 1 / beta1) (to_eval) or x -> y = lerp(x, z, 1 - beta1); see qfx.h."""
+    if not 0.0 < beta1 < 1.0:
+        raise ValueError(f"sf_swap: beta1 must lie in (0, 1) for the train / eval swap, not {beta1!r}")
+    _sf_check("sf_swap", p, (("z", z),))
+    L.check(lib.qfx_sf_swap(_p(p), _p(z), p.numel(), 1.0 - 1.0 / beta1 if to_eval else 1.0 - beta1, stream_ptr()), "qfx_sf_swap")
+
+
 MUON_ADJUST_LR = (None, "original", "match_rms_adamw")
 MUON_MAX_SHORT_SIDE = 96
 

@@ -1,7 +1,7 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, Lion, Lion8bit, PagedLion8bit, Muon) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
@@ -18,7 +18,7 @@ import torch
 from .trainer import optim_state as OS
 from .trainer.qwen_step import optimizer_kwargs_from_config
 
-__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon"]
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree"]
 
 
 def _find_store(param_groups):
@@ -72,16 +72,22 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 self._args[n] = g[n]
         return g
 
+    def _ensure_state(self, st):
+        if self._opt_state is None or self._opt_state.key != self._cls.layout_key(st, self._args):
+            self._opt_state = self._cls(st, self._args)      # zeroed state of the current layout
+        return self._opt_state
+
     @torch.no_grad()
     def step(self, closure=None):
+        if self._opt_state is not None and not self._opt_state.train_mode:
+            raise RuntimeError(self._opt_state.EVAL_STEP)
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         g, st = self._group(), self._store()
         st.ensure_grads()
-        if self._opt_state is None or self._opt_state.key != self._cls.layout_key(st, self._args):
-            self._opt_state = self._cls(st, self._args)      # zeroed state of the current layout
+        self._ensure_state(st)
         self._step_count_fused += 1
         self._opt_state.step(st, g["lr"], g["betas"], g["eps"], g["weight_decay"], self._step_count_fused, None, 0.0, 1.0, self._args)
         return loss
@@ -220,3 +226,29 @@ class Muon(_FlatOptimizer):
             raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
         super().__init__(params, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, ns_coefficients=ns_coefficients,
                          eps=eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn)
+
+
+class AdamWScheduleFree(_FlatOptimizer):
+    """schedulefree.AdamWScheduleFree (no first moment, no schedule: the adapter weights are the gradient point y in train mode and
+    the averaged x in eval mode).  As with the package, call .train() before training and .eval() before validating or saving the
+    weights; step() in eval mode raises.  foreach only says how the package loops over its tensors."""
+    _PATH = "qflux_amd.optim.AdamWScheduleFree"
+
+    def __init__(self, params, lr=0.0025, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, warmup_steps=0, r=0.0, weight_lr_power=2.0,
+                 foreach=True):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, warmup_steps=warmup_steps, r=r,
+                         weight_lr_power=weight_lr_power, foreach=foreach)
+
+    def _swap(self, train):
+        g, st = self._group(), self._store()
+        self._ensure_state(st).swap(st, g["betas"][0], train)
+
+    @torch.no_grad()
+    def eval(self):
+        """y -> x in place (one launch over the flat buffer); nothing happens in eval mode already."""
+        self._swap(False)
+
+    @torch.no_grad()
+    def train(self):
+        """x -> y in place; nothing happens in train mode already."""
+        self._swap(True)

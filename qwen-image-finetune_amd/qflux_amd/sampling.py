@@ -93,10 +93,17 @@ class QwenSampler:
         self.schedule = schedule
 
     @torch.inference_mode()
-    def sample(self, embeddings: dict) -> torch.Tensor:
+    def sample(self, embeddings: dict, train_step=None) -> torch.Tensor:
         """embeddings: control_latents [B,S_c,64], prompt_embeds [B,T,J], prompt_embeds_mask, img_shapes, num_inference_steps,
         true_cfg_scale, latents [B,S_t,64] (initial noise, packed) and, for true CFG, negative_prompt_embeds(+_mask).
+        train_step: the train step that is training this model -- the loop then runs under train_step.eval_mode(), which a
+        schedule-free optimizer needs (its adapter weights are the gradient point y while training, the averaged x is what is
+        sampled from); nothing changes for the other families or without the argument.
         Returns the final packed latents [B,S_t,64]."""
+        with (train_step.eval_mode() if train_step is not None else contextlib.nullcontext()):
+            return self._sample(embeddings)
+
+    def _sample(self, embeddings):
         dit, dev, dt = self.dit, self.dit.device, self.weight_dtype
         steps = int(embeddings["num_inference_steps"])
         cfg = float(embeddings.get("true_cfg_scale", 1.0))
@@ -152,11 +159,16 @@ class FluxSampler:
         self.schedule = schedule
 
     @torch.inference_mode()
-    def sample(self, embeddings: dict) -> torch.Tensor:
+    def sample(self, embeddings: dict, train_step=None) -> torch.Tensor:
         """embeddings: latents [B,S_t,64] + latent_ids [S_t,3] (initial noise, packed), control_latents [B,S_c,64], control_ids
         [S_c,3], pooled_prompt_embeds [B,P], prompt_embeds [B,T,J], text_ids [T,3], guidance, num_inference_steps,
         true_cfg_scale and, for true CFG, negative_pooled_prompt_embeds / negative_prompt_embeds / negative_text_ids.
+        train_step: as QwenSampler.sample -- the loop runs under train_step.eval_mode().
         Returns the final packed latents [B,S_t,64]."""
+        with (train_step.eval_mode() if train_step is not None else contextlib.nullcontext()):
+            return self._sample(embeddings)
+
+    def _sample(self, embeddings):
         dit, dev, dt = self.dit, self.dit.device, self.weight_dtype
         steps = int(embeddings["num_inference_steps"])
         cfg = float(embeddings.get("true_cfg_scale", 1.0))

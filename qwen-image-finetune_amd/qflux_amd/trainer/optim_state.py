@@ -1,14 +1,16 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
 file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
 AdafactorState (transformers.optimization.Adafactor's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
-Lion8bit) and MuonState (torch.optim.Muon's).
+Lion8bit), MuonState (torch.optim.Muon's) and ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
   cls.names(args) / buffers()    fixed, ordered (name, tensor) list that broadcast_state sends and check_replicas sums
   step(store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args)   the family's one step launch
   cls.save(state, entries, step, args) -> (extra param-group fields, per-parameter state); state may be None (no step yet)
-  cls.load(store, sd, args) -> (state or None, highest per-parameter step the family reads, else 0)"""
+  cls.load(store, sd, args) -> (state or None, highest per-parameter step the family reads, else 0)
+  sync_host()                    after the buffers were received from another rank: host-side copies of device scalars follow them
+  swap(store, beta1, train)      the parameter buffer between its train and eval form; a no-op for every family but the schedule-free"""
 from __future__ import annotations
 
 import torch
@@ -41,6 +43,14 @@ class FlatState:
 
     def buffers(self):
         return [(n, getattr(self, n)) for n in self.NAMES]
+
+    def sync_host(self):
+        pass
+
+    train_mode = True
+
+    def swap(self, store, beta1, train):
+        pass
 
 
 class AdamWState(FlatState):
@@ -571,19 +581,114 @@ class MuonState(FlatState):
         return state, 0
 
 
+class ScheduleFreeAdamWState(FlatState):
+    """schedulefree.AdamWScheduleFree: the base sequence z and exp_avg_sq (v) in fp32, indexed like pflat.  The parameter buffer
+    itself holds y (train mode: where the gradient is taken) or the averaged x (eval mode: what is sampled from and saved); swap()
+    moves it between the two.  The group's running scalars k, weight_sum, lr_max, train_mode and scheduled_lr are host values, as in
+    the package (no step reads them back from the device); `sched` is their fp64 device image, written by buffers() for a broadcast
+    or a replica check and read back by sync_host() on the ranks that received it.  k == 0 marks a state that has not stepped: its
+    first step takes z = y and v = 0 in the kernel (the package creates both there), and a swap before it moves nothing."""
+    NAMES = ("z", "v", "sched")
+    DEFAULTS = dict(warmup_steps=0, r=0.0, weight_lr_power=2.0)
+    SCHED = ("k", "weight_sum", "lr_max", "train_mode", "scheduled_lr")
+    EVAL_STEP = ("optimizer step in eval mode: the parameters hold the averaged point x, not the point y the gradient belongs to; "
+                 "call train() first")
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.z = torch.zeros_like(store.pflat)
+        self.v = torch.zeros_like(store.pflat)
+        self.sched = None
+        self.k, self.weight_sum, self.lr_max, self.train_mode, self.scheduled_lr = 0, 0.0, -1.0, True, 0.0
+
+    @staticmethod
+    def validate(args):
+        if int(args["warmup_steps"]) != args["warmup_steps"] or args["warmup_steps"] < 0:
+            raise ValueError(f"Invalid warmup_steps value: {args['warmup_steps']}")
+        args.update(warmup_steps=int(args["warmup_steps"]), r=float(args["r"]), weight_lr_power=float(args["weight_lr_power"]))
+
+    def buffers(self):
+        self.sched = torch.tensor([float(getattr(self, n)) for n in self.SCHED], dtype=torch.float64, device=self.z.device)
+        return super().buffers()
+
+    def sync_host(self):
+        k, self.weight_sum, self.lr_max, tm, self.scheduled_lr = self.sched.cpu().tolist()
+        self.k, self.train_mode = int(k), bool(tm)
+
+    def swap(self, store, beta1, train):
+        """y -> x (train=False) or x -> y (train=True) in place; nothing happens in the mode asked for."""
+        if self.train_mode == bool(train):
+            return
+        if self.k > 0:
+            ops.sf_swap(store.pflat, self.z, beta1, to_eval=not train)
+        self.train_mode = bool(train)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        if not self.train_mode:
+            raise RuntimeError(self.EVAL_STEP)
+        lr_t, bc2, ckp1, self.lr_max, self.weight_sum = ops.sfadamw_schedule(self.k, lr, betas[1], args["warmup_steps"], args["r"],
+                                                                             args["weight_lr_power"], self.lr_max, self.weight_sum)
+        self.scheduled_lr = lr_t
+        ops.sfadamw_step(store.pflat, store.gflat, self.z, self.v, lr_t, betas[0], betas[1], eps, weight_decay, bc2, ckp1,
+                         first=self.k == 0, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+        self.k += 1
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """The package's layout: per parameter {"z", "exp_avg_sq"} (no state before the first step); the group carries warmup_steps, r,
+        weight_lr_power, k, train_mode, weight_sum, lr_max, scheduled_lr and foreach next to lr, betas, eps and weight_decay."""
+        group = dict(args, k=0, train_mode=True, weight_sum=0.0, lr_max=-1.0, scheduled_lr=0.0, foreach=True)
+        if state is None:
+            return group, {}
+        group.update({n: getattr(state, n) for n in cls.SCHED})
+        if state.k == 0:
+            return group, {}
+        return group, {i: {"z": _out(state.z, off, k, p.shape), "exp_avg_sq": _out(state.v, off, k, p.shape)}
+                       for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """The step count is the group's k (as Prodigy's).  A file without per-parameter state has not stepped: no state object, and
+        its train_mode says nothing about the values (a swap before the first step moves none)."""
+        g = sd["param_groups"][0]
+        for n in cls.DEFAULTS:
+            if n in g:
+                args[n] = g[n]
+        cls.validate(args)
+        if not sd["state"]:
+            return None, 0
+        state = cls(store, args)
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is None:
+                continue
+            for n, buf in (("z", state.z), ("exp_avg_sq", state.v)):
+                if n not in e:
+                    raise ValueError(f"optimizer state of parameter {i} (shape {tuple(p.shape)}) has no {n!r}: {sorted(e)}")
+                if e[n].numel() != k:
+                    raise ValueError(f"optimizer state of parameter {i}: {n} has {e[n].numel()} elements, {k} expected")
+                buf[off:off + k].copy_(e[n].reshape(-1).float())
+        state.k, state.weight_sum, state.lr_max = int(g["k"]), float(g["weight_sum"]), float(g["lr_max"])
+        state.train_mode, state.scheduled_lr = bool(g.get("train_mode", True)), float(g.get("scheduled_lr", 0.0))
+        if state.k <= 0:
+            raise ValueError(f"optimizer state with per-parameter z but a step count k = {g['k']}")
+        return state, 0
+
+
 LION = ("lion",) + A8.LION_BLOCKWISE
 
 
 def default_betas(optimizer):
     """The betas a train step uses when its caller gives none: the optimizer class's own default -- (0.9, 0.99) for Lion (both
-    packages), (0.9, 0.999) for every other family (torch.optim.AdamW's, the train steps' default so far)."""
+    packages), (0.9, 0.999) for every other family (torch.optim.AdamW's and schedulefree.AdamWScheduleFree's, the train steps' default
+    so far)."""
     return (0.9, 0.99) if optimizer in LION else (0.9, 0.999)
 
 
 def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
     state class, weight decay, the family's optimizer_args with defaults filled in)."""
-    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor", "muon") + A8.BLOCKWISE + LION:
+    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor", "muon", "adamw_schedulefree") + A8.BLOCKWISE + LION:
         raise ValueError(f"unknown optimizer {optimizer!r}")
     alias = None
     # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / SGD; Prodigy
@@ -606,7 +711,7 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     blockwise = optimizer in A8.BLOCKWISE + A8.LION_BLOCKWISE
     cls = (LionBlockwiseState if optimizer in A8.LION_BLOCKWISE else BlockwiseState) if blockwise else \
         {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState, "lion": LionState,
-         "muon": MuonState}[optimizer]
+         "muon": MuonState, "adamw_schedulefree": ScheduleFreeAdamWState}[optimizer]
     if blockwise:
         args = dict(min_8bit_size=4096, blocksize=256)
     elif optimizer == "lion":
@@ -617,11 +722,14 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         args = dict(AdafactorState.DEFAULTS)
     elif optimizer == "muon":
         args = dict(MuonState.DEFAULTS)
+    elif optimizer == "adamw_schedulefree":
+        args = dict(ScheduleFreeAdamWState.DEFAULTS)
     else:
         args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                     growth_rate=float("inf"))
     unknown = set(optimizer_args or {}) - set(args)
-    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor", "muon") + A8.BLOCKWISE + A8.LION_BLOCKWISE):
+    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor", "muon", "adamw_schedulefree") + A8.BLOCKWISE +
+                   A8.LION_BLOCKWISE):
         raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
     args.update(optimizer_args or {})
     if blockwise:
@@ -634,6 +742,8 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
         AdafactorState.validate(args)
     if optimizer == "muon":
         MuonState.validate(args)
+    if optimizer == "adamw_schedulefree":
+        ScheduleFreeAdamWState.validate(args)
     return alias, optimizer, cls, weight_decay, args
 
 

@@ -15,6 +15,7 @@ Two ways to drive it:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -72,6 +73,12 @@ class QwenLoraTrainStep:
         units orthogonalise the update; weight decay decoupled, default the class's 0.1); optimizer_args: momentum (0.95), nesterov
         (True), ns_coefficients ((3.4445, -4.7750, 2.0315)), ns_steps (5), adjust_lr_fn (None = "original", or "match_rms_adamw") and
         eps (1e-7: Muon's own, the floor of the update's norm, not this constructor's Adam eps); betas / eps unused.
+        "adamw_schedulefree": schedulefree.AdamWScheduleFree (Defazio et al. 2024: Adam's second moment, no first moment and no
+        schedule -- the gradient is taken at y, an interpolation between the base sequence z and the running average x; made for a
+        constant lr; weight decay in the L2 form on y, default 0; the package's lr is 0.0025); optimizer_args: warmup_steps (0: the
+        optimizer's own linear warm-up), r (0.0) and weight_lr_power (2.0): the averaging weight of step k is (k + 1)^r lr_max^power.
+        The adapter weights hold y while training: eval() / train() / eval_mode() swap them to x and back, save_checkpoint writes x,
+        and the samplers take train_step= to sample from x.
         betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, (0.9, 0.999) --
         torch.optim.AdamW's, this constructor's default before Lion -- for every other one; betas given explicitly are never
         reinterpreted.
@@ -327,10 +334,49 @@ class QwenLoraTrainStep:
             return 1.0 / self.world
         return 1.0
 
-    def optimizer_step(self, grad_scale=1.0):
+    def _ensure_opt_state(self):
         st = self.dit.lora_store
         if self.opt_state is None or self.opt_state.key != self._opt_cls.layout_key(st, self.optimizer_args):
             self.opt_state = self._opt_cls(st, self.optimizer_args)      # zeroed state of the current layout
+        return st
+
+    # ------------------------------------------------------------------ train / eval form of the adapter weights
+    @property
+    def train_mode(self):
+        """False while the adapter weights hold the averaged point x of a schedule-free optimizer (eval()); True otherwise, always
+        for every other family."""
+        return self.opt_state is None or self.opt_state.train_mode
+
+    def _swap(self, train):
+        if self.optimizer == "adamw_schedulefree":
+            self._ensure_opt_state()
+            self.opt_state.swap(self.dit.lora_store, self.betas[0], train)
+
+    def eval(self):
+        """optimizer="adamw_schedulefree": the adapter weights (lora_store.pflat, which every plan reads its LoRA operands from at
+        each pass: no plan is rebuilt) go from y to the averaged x that is sampled from and saved -- the package's optimizer.eval().
+        Nothing happens in eval mode already, and for every other family."""
+        self._swap(False)
+
+    def train(self):
+        """Back from x to y (the package's optimizer.train()); nothing happens in train mode already, and for every other family."""
+        self._swap(True)
+
+    @contextlib.contextmanager
+    def eval_mode(self):
+        """`with step.eval_mode():` -- eval() on entry, train() on exit if the step was in train mode before."""
+        was = self.train_mode
+        self.eval()
+        try:
+            yield self
+        finally:
+            if was:
+                self.train()
+
+    def optimizer_step(self, grad_scale=1.0):
+        if not self.train_mode:
+            raise RuntimeError(self.opt_state.EVAL_STEP)
+        st = self._ensure_opt_state()
         self.global_step += 1
         if self._gnorm is None or self._gnorm.device != st.pflat.device:
             self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
@@ -373,20 +419,32 @@ class QwenLoraTrainStep:
 
     def save_checkpoint(self, save_dir, extra_state=None):
         """checkpoint-<e>-<step> folder of the reference (base_trainer.py:827-875): pytorch_lora_weights.safetensors (diffusers
-        key style) + optimizer.bin + state.json."""
+        key style) + optimizer.bin + state.json.  With a schedule-free optimizer the weights file holds the averaged x (what an
+        inference pipeline must load): the weights are swapped to eval for it and back, and optimizer.bin is written after that, in
+        the mode the step was in.  The round trip y -> x -> y rounds (the package's own does); the run goes on from the
+        swapped-back y, and so does a run resumed from the folder."""
         import json
         os.makedirs(save_dir, exist_ok=True)
-        self.dit.save_lora_weights(save_dir)
+        with self.eval_mode():
+            self.dit.save_lora_weights(save_dir)
         torch.save(self.state_dict(), os.path.join(save_dir, "optimizer.bin"))
         with open(os.path.join(save_dir, "state.json"), "w") as f:
             json.dump(dict({"global_step": self.global_step, "lr": self.lr}, **(extra_state or {})), f, indent=2)
 
     def load_checkpoint(self, save_dir, adapter_name=None):
-        """adapter_name: inject/overwrite that adapter from the saved weights first (None = the adapter is already in place)."""
+        """adapter_name: inject/overwrite that adapter from the saved weights first (None = the adapter is already in place).
+        Schedule-free: the step ends in train mode.  Weights read from the folder are the averaged x whatever optimizer.bin says
+        (save_checkpoint writes them in eval mode); weights already in place are x when the file says train_mode=False.  Either
+        way y is reconstructed from x and the file's z with train()'s lerp -- the same launch on the same bits as the swap back in
+        save_checkpoint, so the resumed run continues like the run that wrote the folder."""
         import json
         if adapter_name is not None:
             self.dit.load_lora_adapter(save_dir, adapter_name=adapter_name)
         self.load_state_dict(torch.load(os.path.join(save_dir, "optimizer.bin"), map_location="cpu", weights_only=False))
+        if self.optimizer == "adamw_schedulefree" and self.opt_state is not None:
+            if adapter_name is not None:
+                self.opt_state.train_mode = False
+            self.train()
         self.broadcast_state()       # every replica continues from rank 0's copy of the checkpoint
         with open(os.path.join(save_dir, "state.json")) as f:
             return json.load(f)
@@ -423,6 +481,8 @@ class QwenLoraTrainStep:
         for _, t in self._state_buffers():
             if t is not None:
                 dist.broadcast(t, src=src, group=self.group)
+        if self.opt_state is not None:
+            self.opt_state.sync_host()
 
     def check_replicas(self, what: str = "adapter weights"):
         """Raises if the adapter weights (and optimizer buffers) differ between ranks: two order-sensitive fp64 checksums per
@@ -475,10 +535,12 @@ _OWN_CLASSES = {"qflux_amd.optim.AdamW": ("torch.optim.AdamW", 32), "qflux_amd.o
                 "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0),
                 "qflux_amd.optim.Adafactor": ("transformers.optimization.Adafactor", 0),
                 "qflux_amd.optim.Muon": ("torch.optim.Muon", 0),
+                "qflux_amd.optim.AdamWScheduleFree": ("schedulefree.AdamWScheduleFree", 0),
                 "qflux_amd.optim.Lion8bit": ("bitsandbytes.optim.Lion8bit", 8),
                 "qflux_amd.optim.PagedLion8bit": ("bitsandbytes.optim.PagedLion8bit", 8)}
 _ADAFACTOR = ("transformers.optimization.Adafactor", "transformers.Adafactor")
 _MUON = ("torch.optim.Muon",)
+_SCHEDULEFREE = ("schedulefree.AdamWScheduleFree",)
 _LION = ("lion_pytorch.Lion", "bitsandbytes.optim.Lion", "bitsandbytes.optim.Lion32bit")
 _BNB_LION_8BIT = ("bitsandbytes.optim.Lion8bit", "bitsandbytes.optim.PagedLion8bit")
 _BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
@@ -514,6 +576,9 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         torch.optim.Muon / qflux_amd.optim.Muon -> optimizer="muon" + optimizer_args (momentum, nesterov, ns_coefficients, eps,
     ns_steps, adjust_lr_fn); weight decay left out is the class's 0.1; ns_steps >= 100 and an unknown adjust_lr_fn are refused with
     torch's messages.
+        schedulefree.AdamWScheduleFree / qflux_amd.optim.AdamWScheduleFree -> optimizer="adamw_schedulefree" + optimizer_args
+    (warmup_steps, r, weight_lr_power); lr and weight decay left out are the class's 0.0025 and 0; foreach is dropped.  Keep the
+    reference's lr_scheduler at `constant`: the warm-up is the optimizer's own warmup_steps.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -583,6 +648,12 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         a.pop("differentiable", None)
     elif class_path in _ADAFACTOR + _MUON:
         pass
+    elif class_path in _SCHEDULEFREE:
+        out["optimizer"] = "adamw_schedulefree"
+        out.setdefault("lr", 0.0025)
+        out.setdefault("weight_decay", 0.0)
+        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in OS.ScheduleFreeAdamWState.DEFAULTS}
+        OS.ScheduleFreeAdamWState.validate(dict(OS.ScheduleFreeAdamWState.DEFAULTS, **out["optimizer_args"]))
     elif class_path == "prodigyopt.Prodigy":
         out["optimizer"] = "prodigy"
         out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("beta3", "decouple", "use_bias_correction", "safeguard_warmup", "d0",

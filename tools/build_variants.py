@@ -12,9 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "qwen-image-finetune_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "_ab")
 SOURCES = ["qfx_gemm.hip", "qfx_gemm_fp8.hip", "qfx_skinny.hip", "qfx_elem.hip", "qfx_attn.hip", "qfx_attn64.hip", "qfx_attn_bwd1.hip", "qfx_cond.hip",
-           "qfx_adafactor.hip", "qfx_lion.hip", "qfx_muon.hip"]
+           "qfx_adafactor.hip", "qfx_lion.hip", "qfx_muon.hip", "qfx_schedulefree.hip"]
 EXTRA_FLAGS = {"qfx_attn64.hip": ["-fno-slp-vectorize"], "qfx_attn_bwd1.hip": ["-fno-slp-vectorize"], "qfx_lion.hip": ["-ffp-contract=off"],
-               "qfx_muon.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+               "qfx_muon.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "qfx_schedulefree.hip": ["-ffp-contract=off"]}
 
 
 def main():
