@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void adafactor_kernel(const qfx_adafactor_args
   __shared__ float part[NT];
   const int tid = threadIdx.x;
   float clip = a.grad_scale;
-  if (a.gnorm_sq != nullptr && a.max_norm > 0.f) {      // = adamw_kernel's prologue
+  if (a.gnorm_sq != nullptr && a.max_norm > 0.f) {      // = opt_clip (qfx_optim.h), written out: inlined, it compiles to other code here
     const float nrm = sqrtf(*a.gnorm_sq) * a.grad_scale;
     const float c = a.max_norm / (nrm + 1e-6f);
     clip *= c < 1.0f ? c : 1.0f;

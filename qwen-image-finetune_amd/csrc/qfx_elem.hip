@@ -1,5 +1,5 @@
 // qfx_elem.hip -- the HBM-bound row kernels of the DiT block: LayerNorm+modulate (fwd/bwd),
-// RMSNorm, modulation GEMV, QK-RMSNorm+RoPE (fwd/bwd), head transposes, criterion, clip+AdamW.
+// RMSNorm, modulation GEMV, QK-RMSNorm+RoPE (fwd/bwd), head transposes, criterion.  (The optimizers: qfx_optim.hip and the files beside it.)
 // All bf16 traffic is 16 bytes per lane; one wave owns one row so reductions are shuffle-only.
 // Rounding points replicate the reference's bf16 eager graph (every torch op rounds its output).
 #include "qfx_common.h"
@@ -804,335 +804,6 @@ __global__ __launch_bounds__(256) void mse_tw_kernel(const bf16_t* __restrict__ 
   if (threadIdx.x == 0) unsafeAtomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv_denom);
 }
 
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) acc += g[i] * g[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) unsafeAtomicAdd(out, red[0] + red[1] + red[2] + red[3]);
-}
-
-// Deterministic form: per-block partial sums in a fixed slot each, folded by ONE block in a fixed order.  Data-parallel replicas
-// hold bit-identical gradients after the all-reduce; with the atomic form above the clip coefficient differed in its last bits
-// from rank to rank (fp32 atomics commute only approximately) and the replicas drifted apart by ~1e-10 per step.
-__global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) acc += g[i] * g[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-__global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict__ part, int nb, float* __restrict__ out) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) acc += part[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
-                                                    float wd, float bc1, float bc2, const float* __restrict__ gnorm_sq,
-                                                    float max_norm, float grad_scale) {
-  float clip = grad_scale;
-  if (gnorm_sq != nullptr && max_norm > 0.f) {
-    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
-    const float c = max_norm / (nrm + 1e-6f);
-    clip *= c < 1.0f ? c : 1.0f;
-  }
-  const float step = lr / bc1;
-  const float rs2 = 1.0f / sqrtf(bc2);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * clip;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    pi -= step * mi / (sqrtf(vi) * rs2 + eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
-// torch.optim.SGD over the flat LoRA buffers after adamw_kernel's clip prologue (include/qfx.h).  buf is never touched when mom == 0.
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  int64_t n, float lr, float mom, float damp, float wd, int nesterov, int first,
-                                                  const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
-  float clip = grad_scale;
-  if (gnorm_sq != nullptr && max_norm > 0.f) {
-    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
-    const float c = max_norm / (nrm + 1e-6f);
-    clip *= c < 1.0f ? c : 1.0f;
-  }
-  const float keep = 1.0f - damp;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float pi = p[i];
-    float gi = g[i] * clip;
-    if (wd != 0.f) gi += wd * pi;
-    if (mom != 0.f) {
-      const float bi = first ? gi : mom * buf[i] + keep * gi;
-      buf[i] = bi;
-      gi = nesterov ? gi + mom * bi : bi;
-    }
-    p[i] = pi - lr * gi;
-  }
-}
-
-// ---- Prodigy (prodigyopt 1.x, Adam variant) over the flat LoRA buffers: see include/qfx.h.  Host scalars of the package (Python
-// float64: d, d_max, d_numerator, d_denom, k) live in a device double[QFX_PRODIGY_STATE] so the step never synchronises.
-enum { PS_D = 0, PS_DMAX, PS_NUM, PS_DEN, PS_DHAT, PS_K, PS_ACC_NUM, PS_ACC_DEN, PS_DLR, PS_SKIP };
-
-__global__ void prodigy_begin_kernel(double* __restrict__ st, double lr, double b1, double b2, int use_bc) {
-  const double k = st[PS_K];
-  const double bc = use_bc ? sqrt(1.0 - pow(b2, k + 1.0)) / (1.0 - pow(b1, k + 1.0)) : 1.0;
-  st[PS_DLR] = st[PS_D] * lr * bc;
-  st[PS_ACC_NUM] = 0.0;
-  st[PS_ACC_DEN] = 0.0;
-  st[PS_SKIP] = 0.0;
-}
-
-__global__ __launch_bounds__(256) void prodigy_ema_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, float* __restrict__ sv, const float* __restrict__ p0,
-                                                          int64_t n, double* __restrict__ st, float b1, float b2, float b3, double d0,
-                                                          int safeguard, const float* __restrict__ gnorm_sq, float max_norm,
-                                                          float grad_scale) {
-  __shared__ float red[8];
-  float clip = grad_scale;
-  if (gnorm_sq != nullptr && max_norm > 0.f) {
-    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
-    const float c = max_norm / (nrm + 1e-6f);
-    clip *= c < 1.0f ? c : 1.0f;
-  }
-  const double d = st[PS_D], dlr = st[PS_DLR];
-  const float am = (float)(d * (1.0 - (double)b1)), av = (float)(d * d * (1.0 - (double)b2));
-  const float as = (float)(safeguard ? (d / d0) * d : (d / d0) * dlr);
-  float num = 0.f, den = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * clip;
-    num += gi * (p0[i] - p[i]);
-    m[i] = m[i] * b1 + gi * am;
-    v[i] = v[i] * b2 + (av * gi) * gi;
-    const float si = sv[i] * b3 + gi * as;
-    sv[i] = si;
-    den += fabsf(si);
-  }
-  num = wave_sum(num); den = wave_sum(den);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = num; red[4 + (threadIdx.x >> 6)] = den; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(&st[PS_ACC_NUM], (double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]);
-    atomicAdd(&st[PS_ACC_DEN], (double)red[4] + (double)red[5] + (double)red[6] + (double)red[7]);
-  }
-}
-
-__global__ void prodigy_d_kernel(double* __restrict__ st, double b3, double d0, double d_coef, double growth) {
-  const double den = st[PS_ACC_DEN];
-  if (den == 0.0) { st[PS_SKIP] = 1.0; return; }   // no progress: the package returns before storing anything
-  double d = st[PS_D];
-  const double num = st[PS_NUM] * b3 + (d / d0) * st[PS_DLR] * st[PS_ACC_NUM];
-  const double d_hat = d_coef * num / den;
-  if (d == d0) d = d > d_hat ? d : d_hat;
-  double d_max = st[PS_DMAX];
-  d_max = d_max > d_hat ? d_max : d_hat;
-  const double dg = d * growth;
-  d = d_max < dg ? d_max : dg;
-  st[PS_NUM] = num; st[PS_DEN] = den; st[PS_D] = d; st[PS_DMAX] = d_max; st[PS_DHAT] = d_hat;
-  st[PS_K] += 1.0;
-}
-
-__global__ __launch_bounds__(256) void prodigy_apply_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
-                                                            int64_t n, const double* __restrict__ st, float eps, float wd) {
-  if (st[PS_SKIP] != 0.0) return;
-  const double dlr = st[PS_DLR];
-  const float deps = (float)(st[PS_D] * (double)eps);
-  const float adec = (float)(-(double)wd * dlr), astep = (float)(-dlr);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float pi = p[i];
-    if (wd != 0.f) pi = pi + pi * adec;
-    p[i] = pi + astep * (m[i] / (sqrtf(v[i]) + deps));
-  }
-}
-
-// ---- blockwise 8-bit Adam with bitsandbytes' state layout: see include/qfx.h.  The moment / parameter arithmetic is written out
-// operation by operation with contraction off, so every rounding point is the one of the restatement in tests/bnb8_ref.py.
-// blocksize 256: one wave per table entry, 4 elements per lane (one dwordx4 of p and of g, one dword of four codes per moment), the
-// block maximum a cross-lane reduction.  blocksize 2048: one 256-thread workgroup per entry, 8 elements per lane, maximum through LDS.
-struct A8Const { float b1, b2, omb1, omb2, step_size, eps_hat, decay, clip; int wd; };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// number of midpoints below x (mid[255] = +inf): the nearest code, a tie (x == midpoint) going to the lower one
-__device__ __forceinline__ int a8_code(const float* mid, float x) {
-  int c = 0;
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) c += (x > mid[c + s - 1]) ? s : 0;
-  return c;
-}
-
-// one element: moments in (decoded or fp32), out updated; p updated.  bnb's two kernels associate the g'^2 term differently.
-template <bool FP32_FORM>
-__device__ __forceinline__ void a8_elem(float& p, float g, float& m, float& v, const A8Const& k) {
-#pragma clang fp contract(off)
-  const float gs = g * k.clip;
-  if (!__builtin_isfinite(gs)) return;
-  m = m * k.b1 + k.omb1 * gs;
-  v = FP32_FORM ? v * k.b2 + k.omb2 * (gs * gs) : v * k.b2 + (k.omb2 * gs) * gs;
-  p = p + k.step_size * (m / (sqrtf(v) + k.eps_hat));
-  if (k.wd) p = p * k.decay;
-}
-
-// E elements of one lane starting at element `base` of p / g / codes, n of them valid (n may be < E or <= 0)
-template <int E>
-__device__ __forceinline__ void a8_load(const float* __restrict__ src, int64_t base, int n, float (&x)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {
-      const f32x4 t = *(const f32x4*)(src + base + j);
-      x[j] = t[0]; x[j + 1] = t[1]; x[j + 2] = t[2]; x[j + 3] = t[3];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) x[j + i] = (j + i < n) ? src[base + j + i] : 0.f;
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void a8_store(float* __restrict__ dst, int64_t base, int n, const float (&x)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {
-      f32x4 t; t[0] = x[j]; t[1] = x[j + 1]; t[2] = x[j + 2]; t[3] = x[j + 3];
-      *(f32x4*)(dst + base + j) = t;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (j + i < n) dst[base + j + i] = x[j + i];
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void a8_load_codes(const uint8_t* __restrict__ src, int64_t base, int n, int (&c)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {
-      const uint32_t w = *(const uint32_t*)(src + base + j);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) c[j + i] = (w >> (8 * i)) & 0xff;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) c[j + i] = (j + i < n) ? src[base + j + i] : 0;
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void a8_store_codes(uint8_t* __restrict__ dst, int64_t base, int n, const int (&c)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {     // packed 32-bit vector store
-      *(uint32_t*)(dst + base + j) = (uint32_t)c[j] | ((uint32_t)c[j + 1] << 8) | ((uint32_t)c[j + 2] << 16) | ((uint32_t)c[j + 3] << 24);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (j + i < n) dst[base + j + i] = (uint8_t)c[j + i];
-    }
-  }
-}
-
-// BS = 256: E = 4, a wave per entry (4 entries per workgroup and iteration); BS = 2048: E = 8, the workgroup per entry
-template <int BS>
-__global__ __launch_bounds__(256) void adam8bit_kernel(const qfx_adam8bit_args a, float step_size, float eps_hat) {
-#pragma clang fp contract(off)
-  constexpr bool WG = BS > 256;
-  constexpr int E = WG ? 8 : 4;
-  constexpr int LANES = WG ? 256 : 64;
-  static_assert(E * LANES == BS, "tile");
-  __shared__ float q1s[256], q2s[256], mid1[256], mid2[256];
-  __shared__ float red[2][2][4];
-  const int t = threadIdx.x;
-  q1s[t] = a.qmap1[t];
-  q2s[t] = a.qmap2[t];
-  mid1[t] = t < 255 ? (a.qmap1[t] + a.qmap1[t + 1]) / 2.0f : INFINITY;
-  mid2[t] = t < 255 ? (a.qmap2[t] + a.qmap2[t + 1]) / 2.0f : INFINITY;
-  A8Const k;
-  k.clip = a.grad_scale;
-  if (a.gnorm_sq != nullptr && a.max_norm > 0.f) {      // = adamw_kernel's prologue
-    const float nrm = sqrtf(*a.gnorm_sq) * a.grad_scale;
-    const float c = a.max_norm / (nrm + 1e-6f);
-    k.clip *= c < 1.0f ? c : 1.0f;
-  }
-  k.b1 = a.beta1; k.b2 = a.beta2; k.omb1 = 1.0f - a.beta1; k.omb2 = 1.0f - a.beta2;
-  k.step_size = step_size; k.eps_hat = eps_hat;
-  k.wd = a.weight_decay > 0.f; k.decay = 1.0f - a.lr * a.weight_decay;
-  __syncthreads();
-  const int lane = WG ? t : (t & 63);
-  const int64_t first = WG ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + (t >> 6);
-  const int64_t stride = WG ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
-  int parity = 0;
-  for (int64_t bi = first; bi < a.n_blocks; bi += stride) {
-    const qfx_adam8bit_block e = a.table[bi];
-    const int64_t base = e.off + (int64_t)lane * E;
-    const int n = e.len - lane * E;
-    float p[E], g[E], m[E], v[E];
-    a8_load<E>(a.p, base, n, p);
-    a8_load<E>(a.g, base, n, g);
-    if (e.mode == QFX_ADAM8BIT_FP32) {
-      const int64_t sb = e.state + (int64_t)lane * E;
-      a8_load<E>(a.m32, sb, n, m);
-      a8_load<E>(a.v32, sb, n, v);
-#pragma unroll
-      for (int j = 0; j < E; ++j) a8_elem<true>(p[j], g[j], m[j], v[j], k);
-      a8_store<E>(a.p, base, n, p);
-      a8_store<E>(a.m32, sb, n, m);
-      a8_store<E>(a.v32, sb, n, v);
-      continue;
-    }
-    int c1[E], c2[E];
-    a8_load_codes<E>(a.q1, base, n, c1);
-    a8_load_codes<E>(a.q2, base, n, c2);
-    const float am1 = a.absmax1[e.state], am2 = a.absmax2[e.state];
-    float mx1 = 0.f, mx2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < E; ++j) {
-      m[j] = q1s[c1[j]] * am1;
-      v[j] = q2s[c2[j]] * am2;
-      if (j < n) {
-        a8_elem<false>(p[j], g[j], m[j], v[j], k);
-        mx1 = fmaxf(mx1, fabsf(m[j]));
-        mx2 = fmaxf(mx2, fabsf(v[j]));
-      }
-    }
-    mx1 = wave_max(mx1);
-    mx2 = wave_max(mx2);
-    if (WG) {
-      if ((t & 63) == 0) { red[parity][0][t >> 6] = mx1; red[parity][1][t >> 6] = mx2; }
-      __syncthreads();
-      mx1 = fmaxf(fmaxf(red[parity][0][0], red[parity][0][1]), fmaxf(red[parity][0][2], red[parity][0][3]));
-      mx2 = fmaxf(fmaxf(red[parity][1][0], red[parity][1][1]), fmaxf(red[parity][1][2], red[parity][1][3]));
-      parity ^= 1;
-    }
-    a8_store<E>(a.p, base, n, p);
-#pragma unroll
-    for (int j = 0; j < E; ++j) {
-      const float x1 = mx1 > 0.f ? m[j] / mx1 : 0.f;
-      int c = a8_code(mid1, x1);
-      if (mx1 > 0.f && (__builtin_signbit(q1s[c]) != 0) != (__builtin_signbit(m[j]) != 0)) {      // state1 keeps its sign
-        c += m[j] > 0.f ? 1 : -1;
-        c = c < 0 ? 0 : (c > 255 ? 255 : c);
-      }
-      c1[j] = c;
-      c2[j] = a8_code(mid2, mx2 > 0.f ? v[j] / mx2 : 0.f);
-    }
-    a8_store_codes<E>(a.q1, base, n, c1);
-    a8_store_codes<E>(a.q2, base, n, c2);
-    if (lane == 0) { a.absmax1[e.state] = mx1; a.absmax2[e.state] = mx2; }
-  }
-}
-
 // ---- runtime helpers: CU-masked side stream + a probe of where blocks run --------------------------------------------------
 __global__ void where_kernel(uint32_t* __restrict__ out) {
   if (threadIdx.x == 0) {
@@ -1487,105 +1158,6 @@ extern "C" int qfx_mse_token_weighted_fwd_bwd(const uint16_t* pred, const uint16
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(mse_tw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, target, token_w, loss, dpred, B, S_all,
                      S_t, C, inv_denom, gscale);
-  QFX_CHECK_LAUNCH();
-  return QFX_OK;
-}
-
-extern "C" int qfx_sumsq(const float* g, int64_t n, float* out, void* stream) {
-  if (!g || !out || n <= 0) return QFX_EINVAL;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, out);
-  QFX_CHECK_LAUNCH();
-  return QFX_OK;
-}
-
-extern "C" int qfx_sumsq_det(const float* g, int64_t n, float* out, float* partials, int32_t nslots, void* stream) {
-  if (!g || !out || !partials || n <= 0 || nslots <= 0) return QFX_EINVAL;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > nslots) blocks = nslots;
-  hipLaunchKernelGGL(sumsq_part_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, partials);
-  hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)blocks, out);
-  QFX_CHECK_LAUNCH();
-  return QFX_OK;
-}
-
-extern "C" int qfx_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                              float eps, float weight_decay, float bias_corr1, float bias_corr2, const float* gnorm_sq,
-                              float max_norm, float grad_scale, void* stream) {
-  if (!p || !g || !m || !v || n <= 0) return QFX_EINVAL;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
-                     weight_decay, bias_corr1, bias_corr2, gnorm_sq, max_norm, grad_scale);
-  QFX_CHECK_LAUNCH();
-  return QFX_OK;
-}
-
-extern "C" int qfx_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float dampening,
-                            float weight_decay, int32_t nesterov, int32_t first, const float* gnorm_sq, float max_norm,
-                            float grad_scale, void* stream) {
-  if (!p || !g || n <= 0) return QFX_EINVAL;
-  if (!buf && momentum != 0.f) return QFX_EINVAL;
-  if (nesterov && (!(momentum > 0.f) || dampening != 0.f)) return QFX_EINVAL;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, momentum, dampening,
-                     weight_decay, nesterov, first, gnorm_sq, max_norm, grad_scale);
-  QFX_CHECK_LAUNCH();
-  return QFX_OK;
-}
-
-extern "C" int qfx_prodigy_init_state(double* state, double d0, void* stream) {
-  if (!state || !(d0 > 0.0)) return QFX_EINVAL;
-  double h[QFX_PRODIGY_STATE] = {0};
-  h[PS_D] = d0; h[PS_DMAX] = d0; h[PS_DHAT] = d0;
-  if (hipMemcpyAsync(state, h, sizeof(h), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return QFX_EINVAL;
-  return hipStreamSynchronize((hipStream_t)stream) == hipSuccess ? QFX_OK : QFX_EINVAL;   // h is a stack buffer
-}
-
-extern "C" int qfx_prodigy_step(const qfx_prodigy_args* a, void* stream) {
-  if (!a || !a->p || !a->g || !a->exp_avg || !a->exp_avg_sq || !a->s || !a->p0 || !a->state || a->n <= 0) return QFX_EINVAL;
-  if (!(a->beta1 > 0.f) || !(a->d0 > 0.f) || a->lr < 0.f) return QFX_EINVAL;
-  if (a->weight_decay != 0.f && !a->decouple) return QFX_EUNSUPPORTED;   // coupled decay: not used by any reference config
-  if (a->lr == 0.f) return QFX_OK;   // warm-up step 0: the package creates its state and returns; k does not advance
-  hipStream_t s = (hipStream_t)stream;
-  const double b3 = a->beta3 > 0.f ? (double)a->beta3 : sqrt((double)a->beta2);
-  int blocks = (int)((a->n + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(prodigy_begin_kernel, dim3(1), dim3(1), 0, s, a->state, (double)a->lr, (double)a->beta1, (double)a->beta2,
-                     a->use_bias_correction);
-  hipLaunchKernelGGL(prodigy_ema_kernel, dim3(blocks), dim3(256), 0, s, a->p, a->g, a->exp_avg, a->exp_avg_sq, a->s, a->p0, a->n,
-                     a->state, a->beta1, a->beta2, (float)b3, (double)a->d0, a->safeguard_warmup, a->gnorm_sq, a->max_norm,
-                     a->grad_scale);
-  hipLaunchKernelGGL(prodigy_d_kernel, dim3(1), dim3(1), 0, s, a->state, b3, (double)a->d0, (double)a->d_coef,
-                     (double)a->growth_rate);
-  hipLaunchKernelGGL(prodigy_apply_kernel, dim3(blocks), dim3(256), 0, s, a->p, a->exp_avg, a->exp_avg_sq, a->n, a->state, a->eps,
-                     a->weight_decay);
-  QFX_CHECK_LAUNCH();
-  return QFX_OK;
-}
-
-extern "C" int qfx_adam8bit_step(const qfx_adam8bit_args* a, void* stream) {
-  if (!a || !a->p || !a->g || !a->q1 || !a->q2 || !a->absmax1 || !a->absmax2 || !a->m32 || !a->v32 || !a->table || !a->qmap1 ||
-      !a->qmap2)
-    return QFX_EINVAL;
-  if ((a->blocksize != 256 && a->blocksize != 2048) || a->n_blocks <= 0 || a->step < 1 || !(a->lr >= 0.f)) return QFX_EINVAL;
-  if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) return QFX_EINVAL;
-  // bnb's correction1 / correction2 / step_size, formed once in double here (the same value on every lane and every replica)
-  const double c1 = 1.0 - pow((double)a->beta1, (double)a->step);
-  const double c2 = sqrt(1.0 - pow((double)a->beta2, (double)a->step));
-  const float step_size = (float)(-(double)a->lr * c2 / c1);
-  const float eps_hat = (float)((double)a->eps * c2);
-  hipStream_t s = (hipStream_t)stream;
-  if (a->blocksize == 256) {
-    int64_t wgs = ((int64_t)a->n_blocks + 3) / 4;
-    if (wgs > 2048) wgs = 2048;
-    hipLaunchKernelGGL(adam8bit_kernel<256>, dim3((unsigned)wgs), dim3(256), 0, s, *a, step_size, eps_hat);
-  } else {
-    int64_t wgs = a->n_blocks < 2048 ? a->n_blocks : 2048;
-    hipLaunchKernelGGL(adam8bit_kernel<2048>, dim3((unsigned)wgs), dim3(256), 0, s, *a, step_size, eps_hat);
-  }
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

@@ -7,23 +7,13 @@
 // gets the restatement's sign.  Plain * and + only: the __fmul_rn / __fadd_rn wrappers are inlined from a header compiled WITH
 // contraction and fuse again.
 #include "qfx_common.h"
+#include "qfx_optim.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 struct LionConst { float b1, b2, omb1, omb2, lr, decay, clip; int wd; };
-
-// = adamw_kernel's prologue
-__device__ __forceinline__ float lion_clip(const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
-  float clip = grad_scale;
-  if (gnorm_sq != nullptr && max_norm > 0.f) {
-    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
-    const float c = max_norm / (nrm + 1e-6f);
-    clip *= c < 1.0f ? c : 1.0f;
-  }
-  return clip;
-}
 
 __device__ __forceinline__ LionConst lion_const(float lr, float b1, float b2, float wd, float clip) {
   LionConst k;
@@ -48,7 +38,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n,
                                                    float lr, float b1, float b2, float wd, const float* __restrict__ gnorm_sq,
                                                    float max_norm, float grad_scale) {
-  const LionConst k = lion_const(lr, b1, b2, wd, lion_clip(gnorm_sq, max_norm, grad_scale));
+  const LionConst k = lion_const(lr, b1, b2, wd, opt_clip(gnorm_sq, max_norm, grad_scale));
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = VEC ? n / 4 : 0;
   for (int64_t i = tid; i < nv; i += nt) {
@@ -71,75 +61,7 @@ __global__ __launch_bounds__(256) void lion_kernel(float* __restrict__ p, const 
   }
 }
 
-// ---- blockwise 8-bit state.  The tile helpers restate those of adam8bit_kernel (qfx_elem.hip), which stay where they are so that
-// kernel's code does not move: E elements of one lane starting at element `base`, n of them valid (n may be < E or <= 0).
-__device__ __forceinline__ float lion_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// number of midpoints below x (mid[255] = +inf): the nearest code, a tie (x == midpoint) going to the lower one
-__device__ __forceinline__ int lion_code(const float* mid, float x) {
-  int c = 0;
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) c += (x > mid[c + s - 1]) ? s : 0;
-  return c;
-}
-
-template <int E>
-__device__ __forceinline__ void tile_load(const float* __restrict__ src, int64_t base, int n, float (&x)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {
-      const f32x4 t = *(const f32x4*)(src + base + j);
-      x[j] = t[0]; x[j + 1] = t[1]; x[j + 2] = t[2]; x[j + 3] = t[3];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) x[j + i] = (j + i < n) ? src[base + j + i] : 0.f;
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void tile_store(float* __restrict__ dst, int64_t base, int n, const float (&x)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {
-      f32x4 t; t[0] = x[j]; t[1] = x[j + 1]; t[2] = x[j + 2]; t[3] = x[j + 3];
-      *(f32x4*)(dst + base + j) = t;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (j + i < n) dst[base + j + i] = x[j + i];
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void tile_load_codes(const uint8_t* __restrict__ src, int64_t base, int n, int (&c)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {
-      const uint32_t w = *(const uint32_t*)(src + base + j);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) c[j + i] = (w >> (8 * i)) & 0xff;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) c[j + i] = (j + i < n) ? src[base + j + i] : 0;
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void tile_store_codes(uint8_t* __restrict__ dst, int64_t base, int n, const int (&c)[E]) {
-#pragma unroll
-  for (int j = 0; j < E; j += 4) {
-    if (n >= j + 4) {     // packed 32-bit vector store
-      *(uint32_t*)(dst + base + j) = (uint32_t)c[j] | ((uint32_t)c[j + 1] << 8) | ((uint32_t)c[j + 2] << 16) | ((uint32_t)c[j + 3] << 24);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (j + i < n) dst[base + j + i] = (uint8_t)c[j + i];
-    }
-  }
-}
-
+// ---- blockwise 8-bit state (the tile helpers of qfx_optim.h, shared with adam8bit_kernel).
 // BS = 256: E = 4, a wave per entry (4 entries per workgroup and iteration), the block maximum a cross-lane reduction;
 // BS = 2048: E = 8, the workgroup per entry, the maximum through LDS
 template <int BS>
@@ -153,7 +75,7 @@ __global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a
   const int t = threadIdx.x;
   q1s[t] = a.qmap1[t];
   mid1[t] = t < 255 ? (a.qmap1[t] + a.qmap1[t + 1]) / 2.0f : INFINITY;
-  const LionConst k = lion_const(a.lr, a.beta1, a.beta2, a.weight_decay, lion_clip(a.gnorm_sq, a.max_norm, a.grad_scale));
+  const LionConst k = lion_const(a.lr, a.beta1, a.beta2, a.weight_decay, opt_clip(a.gnorm_sq, a.max_norm, a.grad_scale));
   __syncthreads();
   const int lane = WG ? t : (t & 63);
   const int64_t first = WG ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + (t >> 6);
@@ -187,7 +109,7 @@ __global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a
         mx1 = fmaxf(mx1, fabsf(m[j]));
       }
     }
-    mx1 = lion_wave_max(mx1);
+    mx1 = wave_max(mx1);
     if (WG) {
       if ((t & 63) == 0) red[parity][t >> 6] = mx1;
       __syncthreads();
@@ -198,7 +120,7 @@ __global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       const float x1 = mx1 > 0.f ? m[j] / mx1 : 0.f;
-      int c = lion_code(mid1, x1);
+      int c = nearest_code(mid1, x1);
       if (mx1 > 0.f && (__builtin_signbit(q1s[c]) != 0) != (__builtin_signbit(m[j]) != 0)) {      // state1 keeps its sign
         c += m[j] > 0.f ? 1 : -1;
         c = c < 0 ? 0 : (c > 255 ? 255 : c);
@@ -220,8 +142,7 @@ extern "C" int qfx_lion_step(float* p, const float* g, float* m, int64_t n, floa
                              const float* gnorm_sq, float max_norm, float grad_scale, void* stream) {
   if (!p || !g || !m || n <= 0 || !lion_scalars_ok(lr, beta1, beta2, weight_decay)) return QFX_EINVAL;
   const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0;
-  const int64_t work = vec ? (n + 3) / 4 : n;
-  int blocks = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);      // adamw_kernel's grid policy
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, 4096);      // adamw_kernel's grid policy
   if (vec)
     hipLaunchKernelGGL(lion_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, n, lr, beta1, beta2, weight_decay,
                        gnorm_sq, max_norm, grad_scale);
@@ -236,15 +157,11 @@ extern "C" int qfx_lion8bit_step(const qfx_lion8bit_args* a, void* stream) {
   if (!a || !a->p || !a->g || !a->q1 || !a->absmax1 || !a->m32 || !a->table || !a->qmap1) return QFX_EINVAL;
   if ((a->blocksize != 256 && a->blocksize != 2048) || a->n_blocks <= 0) return QFX_EINVAL;
   if (!lion_scalars_ok(a->lr, a->beta1, a->beta2, a->weight_decay)) return QFX_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (a->blocksize == 256) {
-    int64_t wgs = ((int64_t)a->n_blocks + 3) / 4;
-    if (wgs > 2048) wgs = 2048;
-    hipLaunchKernelGGL(lion8bit_kernel<256>, dim3((unsigned)wgs), dim3(256), 0, s, *a);
-  } else {
-    const int64_t wgs = a->n_blocks < 2048 ? a->n_blocks : 2048;
-    hipLaunchKernelGGL(lion8bit_kernel<2048>, dim3((unsigned)wgs), dim3(256), 0, s, *a);
-  }
+  const dim3 grid(blockwise_grid(a->n_blocks, a->blocksize));
+  if (a->blocksize == 256)
+    hipLaunchKernelGGL(lion8bit_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  else
+    hipLaunchKernelGGL(lion8bit_kernel<2048>, grid, dim3(256), 0, (hipStream_t)stream, *a);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void muon_kernel(const qfx_muon_args a, const 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, lhi = lane >> 4;
   float clip = a.grad_scale;
-  if (a.gnorm_sq != nullptr && a.max_norm > 0.f) {      // = adamw_kernel's prologue
+  if (a.gnorm_sq != nullptr && a.max_norm > 0.f) {      // = opt_clip (qfx_optim.h), written out: inlined, it compiles to other code here
     const float nrm = sqrtf(*a.gnorm_sq) * a.grad_scale;
     const float c = a.max_norm / (nrm + 1e-6f);
     clip *= c < 1.0f ? c : 1.0f;

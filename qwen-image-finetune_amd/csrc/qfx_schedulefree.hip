@@ -6,6 +6,7 @@
 // is compiled without FMA contraction (the pragma below and -ffp-contract=off in the build), so every product and sum is rounded
 // where tests/schedulefree_ref.py rounds it.  Plain operators only, as in qfx_lion.hip.
 #include "qfx_common.h"
+#include "qfx_optim.h"
 
 #pragma clang fp contract(off)
 
@@ -14,17 +15,6 @@ namespace {
 // b2 .. eps as passed; ylr = lr_t (beta1 (1 - ckp1) - 1), formed in double on the host as the package forms it; w / omw: the lerp weight
 // ckp1 and 1 - ckp1 in fp32
 struct SfConst { float b2, omb2, bc2, eps, wd, w, omw, ylr, lr, clip; int wdon, first; };
-
-// = adamw_kernel's prologue
-__device__ __forceinline__ float sf_clip(const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
-  float clip = grad_scale;
-  if (gnorm_sq != nullptr && max_norm > 0.f) {
-    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
-    const float c = max_norm / (nrm + 1e-6f);
-    clip *= c < 1.0f ? c : 1.0f;
-  }
-  return clip;
-}
 
 // torch.lerp's formula, w uniform over the launch
 __device__ __forceinline__ float sf_lerp(float a, float b, float w, float omw) {
@@ -50,7 +40,7 @@ template <bool VEC, bool FIRST>
 __global__ __launch_bounds__(256) void sfadamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ z,
                                                       float* __restrict__ v, int64_t n, SfConst k, const float* __restrict__ gnorm_sq,
                                                       float max_norm, float grad_scale) {
-  k.clip = sf_clip(gnorm_sq, max_norm, grad_scale);
+  k.clip = opt_clip(gnorm_sq, max_norm, grad_scale);
   k.first = FIRST;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = VEC ? n / 4 : 0;
@@ -90,12 +80,6 @@ __global__ __launch_bounds__(256) void sf_swap_kernel(float* __restrict__ p, con
   for (int64_t i = 4 * nv + tid; i < n; i += nt) p[i] = sf_lerp(p[i], z[i], w, omw);
 }
 
-// a bandwidth kernel's grid: one 16-byte (or one scalar) access per lane and pass, at most 256 CUs x 8 workgroups, the rest by stride
-int sf_blocks(int64_t work) {
-  const int64_t b = (work + 255) / 256;
-  return (int)(b < 2048 ? b : 2048);
-}
-
 }  // namespace
 
 extern "C" int qfx_sfadamw_step(float* p, const float* g, float* z, float* v, int64_t n, float lr_t, float beta1, float beta2, float eps,
@@ -110,7 +94,8 @@ extern "C" int qfx_sfadamw_step(float* p, const float* g, float* z, float* v, in
   k.w = ckp1; k.omw = 1.0f - ckp1; k.lr = lr_t; k.clip = 1.0f; k.first = 0;
   k.ylr = (float)((double)lr_t * ((double)beta1 * (1.0 - (double)ckp1) - 1.0));
   const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)z | (uintptr_t)v) & 15) == 0;
-  const int blocks = sf_blocks(vec ? (n + 3) / 4 : n);
+  // one 16-byte (or one scalar) access per lane and pass, at most 256 CUs x 8 workgroups, the rest by stride
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, 2048);
   hipStream_t s = (hipStream_t)stream;
 #define SF_LAUNCH(VEC, FIRST) \
   hipLaunchKernelGGL((sfadamw_kernel<VEC, FIRST>), dim3(blocks), dim3(256), 0, s, p, g, z, v, n, k, gnorm_sq, max_norm, grad_scale)
@@ -124,7 +109,7 @@ extern "C" int qfx_sfadamw_step(float* p, const float* g, float* z, float* v, in
 extern "C" int qfx_sf_swap(float* p, const float* z, int64_t n, float weight, void* stream) {
   if (!p || !z || n <= 0 || !__builtin_isfinite(weight)) return QFX_EINVAL;
   const bool vec = (((uintptr_t)p | (uintptr_t)z) & 15) == 0;
-  const int blocks = sf_blocks(vec ? (n + 3) / 4 : n);
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, 2048);
   if (vec)
     hipLaunchKernelGGL(sf_swap_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, z, n, weight, 1.0f - weight);
   else

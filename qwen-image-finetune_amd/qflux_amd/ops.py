@@ -411,18 +411,24 @@ def adam8bit_block_table(entries, blocksize=256, min_8bit_size=4096, device=None
     return Adam8bitLayout(table, tensors, blocksize, min_8bit_size, n_abs, n_fp32, extent)
 
 
+def _check_tensors(what, p, specs):
+    """specs: (name, tensor, dtype, need[, word]) -- every tensor contiguous, of that dtype, on p's device, with at least `need`
+    elements; word: how the message names the dtype (the flat fp32 steps have always said "float32")."""
+    for name, t, dt, need, *word in specs:
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
+            raise ValueError(f"{what}: {name} must be a contiguous {word[0] if word else dt} tensor on {p.device} with >= {need} elements")
+
+
 def adam8bit_step(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2, lr, betas, eps, weight_decay, step, gnorm_sq=None,
                   max_norm=0.0, grad_scale=1.0):
     """One blockwise 8-bit Adam step (bitsandbytes' Adam8bit / AdamW8bit state layout) over the flat buffers p / g; see qfx.h.
     q1 / q2: uint8 codes indexed like p; absmax1 / absmax2: fp32[>= layout.n_absmax]; m32 / v32: fp32[>= layout.n_fp32] (one element
     when unused); qmap1 / qmap2: fp32[256] ascending."""
     f32, u8 = torch.float32, torch.uint8
-    for name, t, dt, need in (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
-                              ("q2", q2, u8, layout.extent), ("absmax1", absmax1, f32, max(1, layout.n_absmax)),
-                              ("absmax2", absmax2, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
-                              ("v32", v32, f32, max(1, layout.n_fp32)), ("qmap1", qmap1, f32, 256), ("qmap2", qmap2, f32, 256)):
-        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
-            raise ValueError(f"adam8bit_step: {name} must be a contiguous {dt} tensor on {p.device} with >= {need} elements")
+    _check_tensors("adam8bit_step", p, (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
+                                        ("q2", q2, u8, layout.extent), ("absmax1", absmax1, f32, max(1, layout.n_absmax)),
+                                        ("absmax2", absmax2, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
+                                        ("v32", v32, f32, max(1, layout.n_fp32)), ("qmap1", qmap1, f32, 256), ("qmap2", qmap2, f32, 256)))
     if layout.table.device != p.device:
         raise ValueError("adam8bit_step: the block table lives on another device")
     a = L.Adam8bitArgs(_p(p), _p(g), _p(q1), _p(q2), _p(absmax1), _p(absmax2), _p(m32), _p(v32), _p(layout.table), layout.n_blocks,
@@ -433,9 +439,7 @@ def adam8bit_step(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2
 
 def lion_step(p, g, m, lr, beta1, beta2, weight_decay=0.0, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
     """One Lion step (lion_pytorch.Lion / bitsandbytes.optim.Lion) over the flat fp32 buffers p / g with the one moment m; see qfx.h."""
-    for name, t in (("p", p), ("g", g), ("m", m)):
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < p.numel() or t.device != p.device:
-            raise ValueError(f"lion_step: {name} must be a contiguous float32 tensor on {p.device} with >= {p.numel()} elements")
+    _check_tensors("lion_step", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p),) + (("g", g), ("m", m))])
     L.check(lib.qfx_lion_step(_p(p), _p(g), _p(m), p.numel(), lr, beta1, beta2, weight_decay, _p(gnorm_sq), max_norm, grad_scale,
                               stream_ptr()), "qfx_lion_step")
 
@@ -445,11 +449,9 @@ def lion8bit_step(p, g, q1, absmax1, m32, layout, qmap1, lr, betas, weight_decay
     adam8bit_block_table; q1: uint8 codes indexed like p; absmax1: fp32[>= layout.n_absmax]; m32: fp32[>= layout.n_fp32] (one element
     when unused); qmap1: fp32[256] ascending."""
     f32, u8 = torch.float32, torch.uint8
-    for name, t, dt, need in (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
-                              ("absmax1", absmax1, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
-                              ("qmap1", qmap1, f32, 256)):
-        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
-            raise ValueError(f"lion8bit_step: {name} must be a contiguous {dt} tensor on {p.device} with >= {need} elements")
+    _check_tensors("lion8bit_step", p, (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
+                                        ("absmax1", absmax1, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
+                                        ("qmap1", qmap1, f32, 256)))
     if layout.table.device != p.device:
         raise ValueError("lion8bit_step: the block table lives on another device")
     a = L.Lion8bitArgs(_p(p), _p(g), _p(q1), _p(absmax1), _p(m32), _p(layout.table), layout.n_blocks, layout.blocksize, _p(qmap1),
@@ -470,17 +472,11 @@ def sfadamw_schedule(k, lr, beta2, warmup_steps, r, weight_lr_power, lr_max, wei
     return lr_t, bc2, ckp1, lr_max, weight_sum
 
 
-def _sf_check(what, p, others):
-    for name, t in (("p", p),) + others:
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < p.numel() or t.device != p.device:
-            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor on {p.device} with >= {p.numel()} elements")
-
-
 def sfadamw_step(p, g, z, v, lr_t, beta1, beta2, eps, weight_decay, bias_corr2, ckp1, first=False, gnorm_sq=None, max_norm=0.0,
                  grad_scale=1.0):
     """One Schedule-Free AdamW step (schedulefree.AdamWScheduleFree) over the flat fp32 buffers: p holds y, z the base sequence, v
     exp_avg_sq; lr_t, bias_corr2 and ckp1 from sfadamw_schedule; first: z = y and v = 0 are taken, not read; see qfx.h."""
-    _sf_check("sfadamw_step", p, (("g", g), ("z", z), ("v", v)))
+    _check_tensors("sfadamw_step", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p),) + (("g", g), ("z", z), ("v", v))])
     L.check(lib.qfx_sfadamw_step(_p(p), _p(g), _p(z), _p(v), p.numel(), lr_t, beta1, beta2, eps, weight_decay, bias_corr2, ckp1,
                                  int(bool(first)), _p(gnorm_sq), max_norm, grad_scale, stream_ptr()), "qfx_sfadamw_step")
 
@@ -489,7 +485,7 @@ def sf_swap(p, z, beta1, to_eval):
     """Schedule-free mode swap in place: y -> x = lerp(y, z, 1 - 1 / beta1) (to_eval) or x -> y = lerp(x, z, 1 - beta1); see qfx.h."""
     if not 0.0 < beta1 < 1.0:
         raise ValueError(f"sf_swap: beta1 must lie in (0, 1) for the train / eval swap, not {beta1!r}")
-    _sf_check("sf_swap", p, (("z", z),))
+    _check_tensors("sf_swap", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p),) + (("z", z),)])
     L.check(lib.qfx_sf_swap(_p(p), _p(z), p.numel(), 1.0 - 1.0 / beta1 if to_eval else 1.0 - beta1, stream_ptr()), "qfx_sf_swap")
 
 

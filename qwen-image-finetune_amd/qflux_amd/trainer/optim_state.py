@@ -28,9 +28,43 @@ def _out(t, off, k, shape=None):
 
 class FlatState:
     LAYOUT_ARGS = ()
+    DEFAULTS = {}               # the family's optimizer_args and their defaults; empty: the family takes none
 
     def __init__(self, store, args):
         self.key = self.layout_key(store, args)
+
+    @staticmethod
+    def validate(args):
+        pass
+
+    @classmethod
+    def group_args(cls, sd, args):
+        """The file's group; its fields named in DEFAULTS are copied into args, which are then validated."""
+        g = sd["param_groups"][0]
+        for n in cls.DEFAULTS:
+            if n in g:
+                args[n] = g[n]
+        cls.validate(args)
+        return g
+
+    @staticmethod
+    def file_entries(store, sd):
+        """(i, p, off, k, e) for every entry of the store the file has per-parameter state e for."""
+        for i, (_, p, off, k) in enumerate(store.entries):
+            e = sd["state"].get(i)
+            if e is not None:
+                yield i, p, off, k, e
+
+    @staticmethod
+    def field(i, p, e, n, numel=None, shape=None):
+        """e[n], which must exist and have `numel` elements or the shape `shape`."""
+        if n not in e:
+            raise ValueError(f"optimizer state of parameter {i} (shape {tuple(p.shape)}) has no {n!r}: {sorted(e)}")
+        if numel is not None and e[n].numel() != numel:
+            raise ValueError(f"optimizer state of parameter {i}: {n} has {e[n].numel()} elements, {numel} expected")
+        if shape is not None and tuple(e[n].shape) != tuple(shape):
+            raise ValueError(f"optimizer state of parameter {i}: {n} has shape {tuple(e[n].shape)}, {tuple(shape)} expected")
+        return e[n]
 
     @classmethod
     def layout_key(cls, store, args):
@@ -77,10 +111,7 @@ class AdamWState(FlatState):
     @classmethod
     def load(cls, store, sd, args):
         state, step = cls(store, args), 0
-        for i, (_, p, off, k) in enumerate(store.entries):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
+        for i, p, off, k, e in cls.file_entries(store, sd):
             # a bitsandbytes-layout file (state1 / state2 / absmax / qmap) resumes with its moments dequantised
             ea, es = (e["exp_avg"], e["exp_avg_sq"]) if "exp_avg" in e else A8.bnb_moments(e)
             state.m[off:off + k].copy_(ea.reshape(-1).to(state.m.device))
@@ -93,6 +124,8 @@ class ProdigyState(AdamWState):
     """AdamW's two moments plus s, p0 and the fp64 device scalars d, d_max, d_numerator, d_denom, d_hat, k (pstate)."""
     NAMES = ("m", "v", "ps", "p0", "pstate")
     GROUP = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k")
+    DEFAULTS = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
+                    growth_rate=float("inf"))
 
     def __init__(self, store, args):
         super().__init__(store, args)
@@ -132,10 +165,7 @@ class ProdigyState(AdamWState):
     @classmethod
     def load(cls, store, sd, args):
         """The step count is the group's k (QwenLoraTrainStep reads it), not the per-parameter one."""
-        g = sd["param_groups"][0]
-        for n in args:
-            if n in g:
-                args[n] = g[n]
+        g = cls.group_args(sd, args)
         if not sd["state"]:
             return None, 0
         state = cls(store, args)
@@ -150,58 +180,68 @@ class ProdigyState(AdamWState):
         return state, 0
 
 
-class BlockwiseState(FlatState):
-    """bitsandbytes' blockwise 8-bit Adam / AdamW (adam8bit.py): codes indexed like pflat, absmax per 8-bit block, fp32 moments of the
-    tensors below min_8bit_size, the two code books, and the block table of the layout."""
+class _BlockwiseBase(FlatState):
+    """bitsandbytes' blockwise 8-bit state of MOMENTS moments (adam8bit.py): per moment j the codes qj indexed like pflat, absmaxj per
+    8-bit block and the code book qmapj (signed for the first moment), an fp32 moment (m32, v32) for the tensors below min_8bit_size,
+    and the block table of the layout.  In a file the moments are state1 / state2."""
     LAYOUT_ARGS = ("blocksize", "min_8bit_size")
-    NAMES = ("q1", "q2", "absmax1", "absmax2", "m32", "v32", "qmap1", "qmap2")
+    DEFAULTS = dict(min_8bit_size=4096, blocksize=256)
+    MOMENTS = 0
+    F32 = ("m32", "v32")
+
+    @staticmethod
+    def validate(args, optimizer="blockwise 8-bit state"):
+        if args["blocksize"] not in A8.BLOCKSIZES or int(args["min_8bit_size"]) < 1:
+            raise ValueError(f"{optimizer}: blocksize must be one of {A8.BLOCKSIZES} and min_8bit_size >= 1 ({args})")
+        args["min_8bit_size"] = int(args["min_8bit_size"])
+
+    def __init_subclass__(cls):
+        r = range(1, cls.MOMENTS + 1)
+        cls.F32 = _BlockwiseBase.F32[:cls.MOMENTS]
+        cls.NAMES = tuple([f"q{j}" for j in r] + [f"absmax{j}" for j in r] + list(cls.F32) + [f"qmap{j}" for j in r])
 
     def __init__(self, store, args):
         super().__init__(store, args)
         dev = store.pflat.device
         self.layout = ops.adam8bit_block_table([(off, k) for _, _, off, k in store.entries], args["blocksize"], args["min_8bit_size"],
                                                device=dev)
-        n = store.pflat.numel()
-        self.q1 = torch.zeros(n, dtype=torch.uint8, device=dev)     # bnb's initial state: codes 0, absmax 0 (decodes to 0)
-        self.q2 = torch.zeros(n, dtype=torch.uint8, device=dev)
-        self.absmax1 = torch.zeros(max(1, self.layout.n_absmax), dtype=torch.float32, device=dev)
-        self.absmax2 = torch.zeros_like(self.absmax1)
-        self.m32 = torch.zeros(max(1, self.layout.n_fp32), dtype=torch.float32, device=dev)
-        self.v32 = torch.zeros_like(self.m32)
-        self.qmap1 = A8.dynamic_map(True).to(dev)
-        self.qmap2 = A8.dynamic_map(False).to(dev)
-
-    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
-        ops.adam8bit_step(store.pflat, store.gflat, self.q1, self.q2, self.absmax1, self.absmax2, self.m32, self.v32, self.layout,
-                          self.qmap1, self.qmap2, lr, betas, eps, weight_decay, step, gnorm_sq=gnorm_sq, max_norm=max_norm,
-                          grad_scale=grad_scale)
+        for j, f32 in enumerate(self.F32, 1):
+            setattr(self, f"q{j}", torch.zeros(store.pflat.numel(), dtype=torch.uint8, device=dev))     # bnb's initial state: codes 0,
+            setattr(self, f"absmax{j}", torch.zeros(max(1, self.layout.n_absmax), dtype=torch.float32, device=dev))     # absmax 0 (decodes to 0)
+            setattr(self, f32, torch.zeros(max(1, self.layout.n_fp32), dtype=torch.float32, device=dev))
+            setattr(self, f"qmap{j}", A8.dynamic_map(j == 1).to(dev))
 
     def param_state(self, i, shape, step):
         """bnb's per-parameter state of entry i (CPU tensors)."""
         off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        r = range(1, self.MOMENTS + 1)
         if not eight:
-            return {"step": step, "state1": _out(self.m32, s0, k, shape), "state2": _out(self.v32, s0, k, shape)}
-        return {"step": step, "state1": _out(self.q1, off, k, shape), "state2": _out(self.q2, off, k, shape),
-                "qmap1": self.qmap1.cpu().clone(), "qmap2": self.qmap2.cpu().clone(),
-                "absmax1": _out(self.absmax1, a0, nb), "absmax2": _out(self.absmax2, a0, nb)}
+            return dict({"step": step}, **{f"state{j}": _out(getattr(self, self.F32[j - 1]), s0, k, shape) for j in r})
+        e = dict({"step": step}, **{f"state{j}": _out(getattr(self, f"q{j}"), off, k, shape) for j in r})
+        e.update({f"qmap{j}": getattr(self, f"qmap{j}").cpu().clone() for j in r})
+        e.update({f"absmax{j}": _out(getattr(self, f"absmax{j}"), a0, nb) for j in r})
+        return e
 
     def load_param_state(self, i, e):
         off, k, eight, a0, nb, s0 = self.layout.tensors[i]
         if (e["state1"].dtype == torch.uint8) != eight:
             raise ValueError(f"optimizer state of parameter {i} ({k} elements) is {'8-bit' if not eight else 'fp32'} in the file: it was "
                              f"saved with another min_8bit_size than {self.layout.min_8bit_size}")
+        r = range(1, self.MOMENTS + 1)
         if not eight:
-            self.m32[s0:s0 + k].copy_(e["state1"].reshape(-1)); self.v32[s0:s0 + k].copy_(e["state2"].reshape(-1))
+            for j in r:
+                getattr(self, self.F32[j - 1])[s0:s0 + k].copy_(e[f"state{j}"].reshape(-1))
             return
-        if e["absmax1"].numel() != nb or e["absmax2"].numel() != nb:
+        if any(e[f"absmax{j}"].numel() != nb for j in r):
             raise ValueError(f"optimizer state of parameter {i}: {e['absmax1'].numel()} absmax blocks, {nb} expected")
-        self.q1[off:off + k].copy_(e["state1"].reshape(-1)); self.q2[off:off + k].copy_(e["state2"].reshape(-1))
-        self.absmax1[a0:a0 + nb].copy_(e["absmax1"].reshape(-1)); self.absmax2[a0:a0 + nb].copy_(e["absmax2"].reshape(-1))
+        for j in r:
+            getattr(self, f"q{j}")[off:off + k].copy_(e[f"state{j}"].reshape(-1))
+            getattr(self, f"absmax{j}")[a0:a0 + nb].copy_(e[f"absmax{j}"].reshape(-1))
 
     @classmethod
     def save(cls, state, entries, step, args):
-        """bnb's Optimizer2State layout: per parameter {"step", "state1", "state2", "qmap1", "qmap2", "absmax1", "absmax2"} (8-bit) or
-        {"step", "state1", "state2"} (fp32 moments, numel < min_8bit_size); no group fields of its own."""
+        """bnb's Optimizer2State / Optimizer1State layout: per parameter {"step", "stateJ", "qmapJ", "absmaxJ"} (8-bit) or {"step",
+        "stateJ"} (fp32 moments, numel < min_8bit_size); no group fields of its own."""
         if state is None or step == 0:
             return {}, {}
         return {}, {i: state.param_state(i, p.shape, step) for i, (_, p, _, _) in enumerate(entries)}
@@ -209,19 +249,27 @@ class BlockwiseState(FlatState):
     @classmethod
     def load(cls, store, sd, args):
         """The block size is inferred from the file's absmax sizes, the code books are the file's."""
-        bs, q1, q2 = A8.file_layout(sd["state"], store.entries)
+        bs, *qmaps = A8.file_layout(sd["state"], store.entries)
         if bs is not None:
             args["blocksize"] = bs
         state, step = cls(store, args), 0
-        if q1 is not None:
-            state.qmap1.copy_(q1); state.qmap2.copy_(q2)
-        for i in range(len(store.entries)):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
+        if qmaps[0] is not None:
+            for j in range(1, cls.MOMENTS + 1):
+                getattr(state, f"qmap{j}").copy_(qmaps[j - 1])
+        for i, p, off, k, e in cls.file_entries(store, sd):
             state.load_param_state(i, e)
             step = max(step, int(float(e["step"])))
         return state, step
+
+
+class BlockwiseState(_BlockwiseBase):
+    """bitsandbytes' blockwise 8-bit Adam / AdamW: two moments (q1, q2, absmax1, absmax2, m32, v32, qmap1, qmap2)."""
+    MOMENTS = 2
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        ops.adam8bit_step(store.pflat, store.gflat, self.q1, self.q2, self.absmax1, self.absmax2, self.m32, self.v32, self.layout,
+                          self.qmap1, self.qmap2, lr, betas, eps, weight_decay, step, gnorm_sq=gnorm_sq, max_norm=max_norm,
+                          grad_scale=grad_scale)
 
 
 class SgdState(FlatState):
@@ -271,19 +319,14 @@ class SgdState(FlatState):
 
     @classmethod
     def load(cls, store, sd, args):
-        g = sd["param_groups"][0]
-        if g.get("maximize", False):
+        if sd["param_groups"][0].get("maximize", False):
             raise NotImplementedError("SGD with maximize=True")
-        for n in cls.DEFAULTS:
-            if n in g:
-                args[n] = g[n]
-        cls.validate(args)
+        cls.group_args(sd, args)
         if not sd["state"] or args["momentum"] == 0:
             return None, 0
         state = cls(store, args)
-        for i, (_, p, off, k) in enumerate(store.entries):
-            e = sd["state"].get(i)
-            if e is not None and e.get("momentum_buffer") is not None:
+        for i, p, off, k, e in cls.file_entries(store, sd):
+            if e.get("momentum_buffer") is not None:
                 state.buf[off:off + k].copy_(e["momentum_buffer"].reshape(-1))
         state.first = False
         return state, 0
@@ -363,27 +406,17 @@ class AdafactorState(FlatState):
     @classmethod
     def load(cls, store, sd, args):
         """Every statistic must have the shape the parameter implies; a file written without beta1 cannot resume a run with it."""
-        g = sd["param_groups"][0]
-        for n in cls.DEFAULTS:
-            if n in g:
-                args[n] = g[n]
-        cls.validate(args)
+        cls.group_args(sd, args)
         if not sd["state"]:
             return None, 0
         state, step, rms = cls(store, args), 0, [0.0] * len(store.entries)
-        for i, (_, p, off, k) in enumerate(store.entries):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
+        for i, p, off, k, e in cls.file_entries(store, sd):
             _, rows, cols, factored, r0, c0, v0 = state.layout.tensors[i]
             want = {"exp_avg_sq_row": (rows,), "exp_avg_sq_col": (cols,)} if factored else {"exp_avg_sq": tuple(p.shape)}
             if state.m is not None:
                 want["exp_avg"] = tuple(p.shape)
             for n, shape in want.items():
-                if n not in e:
-                    raise ValueError(f"optimizer state of parameter {i} (shape {tuple(p.shape)}) has no {n!r}: {sorted(e)}")
-                if tuple(e[n].shape) != shape:
-                    raise ValueError(f"optimizer state of parameter {i}: {n} has shape {tuple(e[n].shape)}, {shape} expected")
+                cls.field(i, p, e, n, shape=shape)
             if factored:
                 state.row[r0:r0 + rows].copy_(e["exp_avg_sq_row"]); state.col[c0:c0 + cols].copy_(e["exp_avg_sq_col"])
             else:
@@ -422,10 +455,7 @@ class LionState(FlatState):
         if not sd["state"]:
             return None, 0
         state, step = cls(store, args), 0
-        for i, (_, p, off, k) in enumerate(store.entries):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
+        for i, p, off, k, e in cls.file_entries(store, sd):
             ea = e["exp_avg"] if "exp_avg" in e else A8.bnb_moment1(e)
             if ea.numel() != k:
                 raise ValueError(f"optimizer state of parameter {i}: {ea.numel()} elements, {k} expected")
@@ -434,71 +464,13 @@ class LionState(FlatState):
         return state, step
 
 
-class LionBlockwiseState(FlatState):
-    """bitsandbytes.optim.Lion8bit / PagedLion8bit: BlockwiseState with ONE moment -- codes indexed like pflat, absmax per 8-bit block,
-    the fp32 moment of the tensors below min_8bit_size, the signed code book, and the same block table."""
-    LAYOUT_ARGS = ("blocksize", "min_8bit_size")
-    NAMES = ("q1", "absmax1", "m32", "qmap1")
-
-    def __init__(self, store, args):
-        super().__init__(store, args)
-        dev = store.pflat.device
-        self.layout = ops.adam8bit_block_table([(off, k) for _, _, off, k in store.entries], args["blocksize"], args["min_8bit_size"],
-                                               device=dev)
-        self.q1 = torch.zeros(store.pflat.numel(), dtype=torch.uint8, device=dev)     # bnb's initial state: codes 0, absmax 0
-        self.absmax1 = torch.zeros(max(1, self.layout.n_absmax), dtype=torch.float32, device=dev)
-        self.m32 = torch.zeros(max(1, self.layout.n_fp32), dtype=torch.float32, device=dev)
-        self.qmap1 = A8.dynamic_map(True).to(dev)
+class LionBlockwiseState(_BlockwiseBase):
+    """bitsandbytes.optim.Lion8bit / PagedLion8bit: ONE moment (q1, absmax1, m32, qmap1) over the same block table."""
+    MOMENTS = 1
 
     def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
         ops.lion8bit_step(store.pflat, store.gflat, self.q1, self.absmax1, self.m32, self.layout, self.qmap1, lr, betas, weight_decay,
                           gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
-
-    def param_state(self, i, shape, step):
-        """bnb's per-parameter state of entry i (CPU tensors)."""
-        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
-        if not eight:
-            return {"step": step, "state1": _out(self.m32, s0, k, shape)}
-        return {"step": step, "state1": _out(self.q1, off, k, shape), "qmap1": self.qmap1.cpu().clone(),
-                "absmax1": _out(self.absmax1, a0, nb)}
-
-    def load_param_state(self, i, e):
-        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
-        if (e["state1"].dtype == torch.uint8) != eight:
-            raise ValueError(f"optimizer state of parameter {i} ({k} elements) is {'8-bit' if not eight else 'fp32'} in the file: it was "
-                             f"saved with another min_8bit_size than {self.layout.min_8bit_size}")
-        if not eight:
-            self.m32[s0:s0 + k].copy_(e["state1"].reshape(-1))
-            return
-        if e["absmax1"].numel() != nb:
-            raise ValueError(f"optimizer state of parameter {i}: {e['absmax1'].numel()} absmax blocks, {nb} expected")
-        self.q1[off:off + k].copy_(e["state1"].reshape(-1))
-        self.absmax1[a0:a0 + nb].copy_(e["absmax1"].reshape(-1))
-
-    @classmethod
-    def save(cls, state, entries, step, args):
-        """bnb's Optimizer1State layout: per parameter {"step", "state1", "qmap1", "absmax1"} (8-bit) or {"step", "state1"} (fp32
-        moment, numel < min_8bit_size); no group fields of its own."""
-        if state is None or step == 0:
-            return {}, {}
-        return {}, {i: state.param_state(i, p.shape, step) for i, (_, p, _, _) in enumerate(entries)}
-
-    @classmethod
-    def load(cls, store, sd, args):
-        """The block size is inferred from the file's absmax sizes, the code book is the file's."""
-        bs, q1, _ = A8.file_layout(sd["state"], store.entries)
-        if bs is not None:
-            args["blocksize"] = bs
-        state, step = cls(store, args), 0
-        if q1 is not None:
-            state.qmap1.copy_(q1)
-        for i in range(len(store.entries)):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
-            state.load_param_state(i, e)
-            step = max(step, int(float(e["step"])))
-        return state, step
 
 
 class MuonState(FlatState):
@@ -561,18 +533,11 @@ class MuonState(FlatState):
     @classmethod
     def load(cls, store, sd, args):
         """torch keeps no step count: the train steps' own global_step carries it (0 for a file torch.optim.Muon wrote)."""
-        g = sd["param_groups"][0]
-        for n in cls.DEFAULTS:
-            if n in g:
-                args[n] = g[n]
-        cls.validate(args)
+        cls.group_args(sd, args)
         if not sd["state"]:
             return None, 0
         state = cls(store, args)
-        for i, (_, p, off, k) in enumerate(store.entries):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
+        for i, p, off, k, e in cls.file_entries(store, sd):
             mb = e["momentum_buffer"]
             if tuple(mb.shape) != tuple(p.shape):
                 raise ValueError(f"optimizer state of parameter {i}: momentum_buffer has shape {tuple(mb.shape)}, {tuple(p.shape)} expected")
@@ -650,24 +615,13 @@ class ScheduleFreeAdamWState(FlatState):
     def load(cls, store, sd, args):
         """The step count is the group's k (as Prodigy's).  A file without per-parameter state has not stepped: no state object, and
         its train_mode says nothing about the values (a swap before the first step moves none)."""
-        g = sd["param_groups"][0]
-        for n in cls.DEFAULTS:
-            if n in g:
-                args[n] = g[n]
-        cls.validate(args)
+        g = cls.group_args(sd, args)
         if not sd["state"]:
             return None, 0
         state = cls(store, args)
-        for i, (_, p, off, k) in enumerate(store.entries):
-            e = sd["state"].get(i)
-            if e is None:
-                continue
+        for i, p, off, k, e in cls.file_entries(store, sd):
             for n, buf in (("z", state.z), ("exp_avg_sq", state.v)):
-                if n not in e:
-                    raise ValueError(f"optimizer state of parameter {i} (shape {tuple(p.shape)}) has no {n!r}: {sorted(e)}")
-                if e[n].numel() != k:
-                    raise ValueError(f"optimizer state of parameter {i}: {n} has {e[n].numel()} elements, {k} expected")
-                buf[off:off + k].copy_(e[n].reshape(-1).float())
+                buf[off:off + k].copy_(cls.field(i, p, e, n, numel=k).reshape(-1).float())
         state.k, state.weight_sum, state.lr_max = int(g["k"]), float(g["weight_sum"]), float(g["lr_max"])
         state.train_mode, state.scheduled_lr = bool(g.get("train_mode", True)), float(g.get("scheduled_lr", 0.0))
         if state.k <= 0:
@@ -676,6 +630,11 @@ class ScheduleFreeAdamWState(FlatState):
 
 
 LION = ("lion",) + A8.LION_BLOCKWISE
+# optimizer= name -> (state class, the weight decay that weight_decay=None stands for: the stood-in optimizer class's own default)
+FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": (SgdState, 0.0), "adafactor": (AdafactorState, 0.0),
+            "lion": (LionState, 0.0), "muon": (MuonState, 0.1), "adamw_schedulefree": (ScheduleFreeAdamWState, 0.0),
+            "adam8bit_blockwise": (BlockwiseState, 0.0), "adamw8bit_blockwise": (BlockwiseState, 0.01),
+            "lion8bit_blockwise": (LionBlockwiseState, 0.0)}
 
 
 def default_betas(optimizer):
@@ -688,7 +647,7 @@ def default_betas(optimizer):
 def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
     state class, weight decay, the family's optimizer_args with defaults filled in)."""
-    if optimizer not in ("adamw", "adam", "adam8bit", "prodigy", "sgd", "adafactor", "muon", "adamw_schedulefree") + A8.BLOCKWISE + LION:
+    if optimizer not in ("adam", "adam8bit") and optimizer not in FAMILIES:
         raise ValueError(f"unknown optimizer {optimizer!r}")
     alias = None
     # weight_decay=None = "the optimizer class's own default": 0.01 for AdamW (torch.optim.AdamW), 0 for Adam / Adam8bit / SGD; Prodigy
@@ -706,44 +665,16 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
                                       "kernel implements AdamW's decoupled form only; the reference's configs use none)")
         weight_decay = 0.0
         alias, optimizer = optimizer, "adamw"
+    cls, default_wd = FAMILIES[optimizer]
     if weight_decay is None:
-        weight_decay = 0.01 if optimizer in ("adamw", "adamw8bit_blockwise") else 0.1 if optimizer == "muon" else 0.0      # torch.optim.Muon's 0.1
-    blockwise = optimizer in A8.BLOCKWISE + A8.LION_BLOCKWISE
-    cls = (LionBlockwiseState if optimizer in A8.LION_BLOCKWISE else BlockwiseState) if blockwise else \
-        {"adamw": AdamWState, "prodigy": ProdigyState, "sgd": SgdState, "adafactor": AdafactorState, "lion": LionState,
-         "muon": MuonState, "adamw_schedulefree": ScheduleFreeAdamWState}[optimizer]
-    if blockwise:
-        args = dict(min_8bit_size=4096, blocksize=256)
-    elif optimizer == "lion":
-        args = {}
-    elif optimizer == "sgd":
-        args = dict(SgdState.DEFAULTS)
-    elif optimizer == "adafactor":
-        args = dict(AdafactorState.DEFAULTS)
-    elif optimizer == "muon":
-        args = dict(MuonState.DEFAULTS)
-    elif optimizer == "adamw_schedulefree":
-        args = dict(ScheduleFreeAdamWState.DEFAULTS)
-    else:
-        args = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
-                    growth_rate=float("inf"))
+        weight_decay = default_wd
+    # "adamw" has always returned Prodigy's defaults (nothing reads them) while taking no optimizer_args
+    args = dict(ProdigyState.DEFAULTS if cls is AdamWState else cls.DEFAULTS)
     unknown = set(optimizer_args or {}) - set(args)
-    if unknown or (optimizer_args and optimizer not in ("prodigy", "sgd", "adafactor", "muon", "adamw_schedulefree") + A8.BLOCKWISE +
-                   A8.LION_BLOCKWISE):
+    if unknown or (optimizer_args and not cls.DEFAULTS):
         raise ValueError(f"unsupported optimizer_args for {optimizer}: {sorted(unknown) or sorted(optimizer_args)}")
     args.update(optimizer_args or {})
-    if blockwise:
-        if args["blocksize"] not in A8.BLOCKSIZES or int(args["min_8bit_size"]) < 1:
-            raise ValueError(f"{optimizer}: blocksize must be one of {A8.BLOCKSIZES} and min_8bit_size >= 1 ({args})")
-        args["min_8bit_size"] = int(args["min_8bit_size"])
-    if optimizer == "sgd":
-        SgdState.validate(args)
-    if optimizer == "adafactor":
-        AdafactorState.validate(args)
-    if optimizer == "muon":
-        MuonState.validate(args)
-    if optimizer == "adamw_schedulefree":
-        ScheduleFreeAdamWState.validate(args)
+    cls.validate(args, optimizer) if issubclass(cls, _BlockwiseBase) else cls.validate(args)      # its message names the optimizer
     return alias, optimizer, cls, weight_decay, args
 
 

@@ -44,10 +44,10 @@ def _grads(sizes, it, bs):
 class _Dev:
     """The device buffers of one step, loaded from / compared with the restatement's state."""
 
-    def __init__(self, sizes, bs, params):
+    def __init__(self, sizes, bs, params, min8=4096):
         from qflux_amd import ops
         self.offs, n = _flat(sizes)
-        self.lay = ops.adam8bit_block_table(list(zip(self.offs, sizes)), bs, 4096, device=DEV)
+        self.lay = ops.adam8bit_block_table(list(zip(self.offs, sizes)), bs, min8, device=DEV)
         self.p = torch.zeros(n, device=DEV)
         self.g = torch.zeros(n, device=DEV)
         self.q1 = torch.zeros(n, dtype=torch.uint8, device=DEV)
@@ -119,6 +119,45 @@ def test_kernel_matches_restatement(bs):
         stats.append(same / tot)
         assert same >= 0.999 * tot, (it, same / tot)
     print(f"adam8bit bs={bs}: identical codes per step {stats}")
+
+
+@pytest.mark.parametrize("bs", [256, 2048])
+def test_kernel_clip_active_on_short_block_one_block_and_fp32_tensors(bs):
+    """min_8bit_size 256 and three tensors: 259 elements (8-bit, the last block short), exactly one block, and 5 elements (fp32
+    moments); the clip is active at every step.  Compared as test_kernel_matches_restatement compares."""
+    sizes, min8 = [256 + 3, bs, 5], 256
+    torch.manual_seed(3)
+    params = [torch.randn(k) * 0.1 for k in sizes]
+    kw = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_norm=1.0, grad_scale=0.5)
+    opt = R.Adam8bitRef([p.clone() for p in params], lr=kw["lr"], betas=kw["betas"], eps=kw["eps"], weight_decay=kw["weight_decay"],
+                        min_8bit_size=min8, blocksize=bs)
+    d = _Dev(sizes, bs, params, min8)
+    assert [t[2] for t in d.lay.tensors] == [True, True, False] and d.lay.tensors[1][4] == 1
+    for it in range(3):
+        grads = _grads(sizes, it, bs)
+        gsq = float(sum(g.double().pow(2).sum() for g in grads))
+        assert gsq * kw["grad_scale"] ** 2 > 4.0                        # the clip is active
+        d.load(opt)                                                      # re-synchronised: one step at a time is compared
+        d.step(grads, it + 1, gsq, **kw)
+        opt.step([g.clone() for g in grads], gnorm_sq=gsq, max_norm=kw["max_norm"], grad_scale=kw["grad_scale"])
+        torch.cuda.synchronize()
+        same = tot = 0
+        for (off, k, eight, a0, nb, s0), p, st in zip(d.lay.tensors, opt.params, opt.state):
+            pk = d.p[off:off + k].cpu()
+            assert torch.isfinite(pk).all()
+            assert ((pk - p).abs() / p.abs().max()).max().item() <= 1e-6, (it, k)
+            if not eight:
+                assert torch.allclose(d.m32[s0:s0 + k].cpu(), st["state1"], rtol=1e-6, atol=0)
+                assert torch.allclose(d.v32[s0:s0 + k].cpu(), st["state2"], rtol=1e-6, atol=0)
+                continue
+            a1k, a2k = d.a1[a0:a0 + nb].cpu(), d.a2[a0:a0 + nb].cpu()
+            assert torch.allclose(a1k, st["absmax1"], rtol=1e-6, atol=0) and torch.allclose(a2k, st["absmax2"], rtol=1e-6, atol=0)
+            for q, key in ((d.q1, "state1"), (d.q2, "state2")):
+                ck, cr = q[off:off + k].cpu().long(), st[key].reshape(-1).long()
+                assert (ck - cr).abs().max().item() <= 1, (it, k, key)          # decoded moments within one code step
+                same += int((ck == cr).sum()); tot += k
+        print(f"adam8bit clipped bs={bs} step {it}: {same} of {tot} codes identical")
+        assert same >= 0.999 * tot, (it, same / tot)
 
 
 def test_kernel_is_deterministic():

@@ -80,13 +80,45 @@ def test_fp32_kernel_unaligned_and_odd_lengths():
     assert torch.equal(outs[0][1], mr) and torch.equal(outs[0][0][~und], pr[~und])      # no clip: the same fp32 operations, the same bits
 
 
+def test_fp32_kernel_clip_active_aligned_and_offset_view():
+    """The clip at work (coefficient ~ 1/16) at the smallest length with a 16-byte body and a scalar tail, on an aligned buffer and on
+    a view one element in (the scalar instantiation): both runs give the same bits, and those are the restatement's, as in the clip-free case
+    above (the coefficient is formed on the host there, on the device here, by the same fp32 operations)."""
+    from qflux_amd import ops
+    g0 = torch.Generator().manual_seed(7)
+    n = 4 * 256 + 3
+    vals = [torch.randn(n, generator=g0) * s for s in (0.1, 1.0, 0.01)]
+    gsq = float(vals[1].double().pow(2).sum())
+    clip = R.clip_coef(gsq, R.KW["max_norm"], R.KW["grad_scale"])
+    assert clip < 0.1 * R.KW["grad_scale"]                                 # the clip is active
+    outs = []
+    for shift in (0, 1):
+        bufs = [torch.zeros(n + 8, device=DEV) for _ in range(3)]
+        p, g, m = (b[shift:shift + n] for b in bufs)
+        for t, v in zip((p, g, m), vals):
+            t.copy_(v.to(DEV))
+        ops.lion_step(p, g, m, 1e-3, 0.9, 0.99, 0.01, gnorm_sq=torch.tensor(gsq, dtype=torch.float32, device=DEV),
+                      max_norm=R.KW["max_norm"], grad_scale=R.KW["grad_scale"])
+        torch.cuda.synchronize()
+        outs.append((p.cpu(), m.cpu()))
+        assert not bufs[0][shift + n:].any() and not bufs[2][shift + n:].any() and not bufs[0][:shift].any()      # nothing past the end
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    pr, mr, und = R.update(vals[0], vals[1] * torch.tensor(clip), vals[2], R.step_scalars(1e-3, 0.9, 0.99, 0.01))
+    n_und = _check_params(outs[0][0], pr, und, n)
+    print(f"lion fp32 clipped n={n}: {n_und} undecided")
+    # bnb8_ref.clip_coef restates the prologue's fp32 operations one by one (correctly rounded sqrt and division on both sides): the
+    # same coefficient, so the same bits as the clip-free case above asks for
+    assert torch.equal(outs[0][1], mr) and torch.equal(outs[0][0][~und], pr[~und])
+    assert n_und <= R.UNDECIDED_CAP * sum(SIZES)
+
+
 class _Dev8:
     """The device buffers of the 8-bit step, loaded from / compared with the restatement's state."""
 
-    def __init__(self, sizes, bs):
+    def __init__(self, sizes, bs, min8=4096):
         from qflux_amd import ops
         self.offs, n = R.flat_offsets(sizes)
-        self.lay = ops.adam8bit_block_table(list(zip(self.offs, sizes)), bs, 4096, device=DEV)
+        self.lay = ops.adam8bit_block_table(list(zip(self.offs, sizes)), bs, min8, device=DEV)
         self.p = torch.zeros(n, device=DEV)
         self.g = torch.zeros(n, device=DEV)
         self.q1 = torch.zeros(n, dtype=torch.uint8, device=DEV)
@@ -141,6 +173,37 @@ def test_8bit_kernel_matches_restatement(bs):
         assert same >= 0.999 * tot, (it, same / tot)
         assert n_und <= R.UNDECIDED_CAP * sum(SIZES), (it, n_und)
     print(f"lion8bit bs={bs}: identical codes per step {stats}")
+
+
+@pytest.mark.parametrize("bs", [256, 2048])
+def test_8bit_kernel_clip_active_on_short_block_one_block_and_fp32_tensors(bs):
+    """min_8bit_size 256 and three tensors: 259 elements (8-bit, the last block short), exactly one block, and 5 elements (fp32
+    moment); the clip is active at every step.  Compared as test_8bit_kernel_matches_restatement compares."""
+    sizes, min8, wd = [256 + 3, bs, 5], 256, 0.01
+    opt = R.LionRef(R.make_params(sizes, seed=3), lr=R.KW["lr"], betas=R.KW["betas"], weight_decay=wd, min_8bit_size=min8, blocksize=bs)
+    d = _Dev8(sizes, bs, min8)
+    assert [t[2] for t in d.lay.tensors] == [True, True, False] and d.lay.tensors[1][4] == 1
+    for it in range(3):
+        grads = R.make_grads(sizes, it, bs)
+        gsq = R.gnorm_sq(grads)
+        assert gsq * R.KW["grad_scale"] ** 2 > 4.0                        # the clip is active
+        d.load([p.clone() for p in opt.params], opt.state)                # re-synchronised: one step at a time is compared
+        d.step(grads, gsq, wd, **R.KW)
+        opt.step([g.clone() for g in grads], gnorm_sq=gsq, max_norm=R.KW["max_norm"], grad_scale=R.KW["grad_scale"])
+        torch.cuda.synchronize()
+        same = tot = n_und = 0
+        for i, ((off, k, eight, a0, nb, s0), pt, st) in enumerate(zip(d.lay.tensors, opt.params, opt.state)):
+            n_und += _check_params(d.p[off:off + k].cpu(), pt, opt.undecided[i], (it, k))
+            if not eight:
+                assert torch.allclose(d.m32[s0:s0 + k].cpu(), st["state1"], rtol=1e-6, atol=0), (it, k)
+                continue
+            assert torch.allclose(d.a1[a0:a0 + nb].cpu(), st["absmax1"], rtol=1e-6, atol=0), (it, k)
+            ck, cr = d.q1[off:off + k].cpu().long(), st["state1"].reshape(-1).long()
+            assert (ck - cr).abs().max().item() <= 1, (it, k)            # decoded moments within one code step
+            same += int((ck == cr).sum()); tot += k
+        print(f"lion8bit clipped bs={bs} step {it}: {same} of {tot} codes identical, {n_und} undecided")
+        assert same >= 0.999 * tot, (it, same / tot)
+        assert n_und <= R.UNDECIDED_CAP * sum(SIZES), (it, n_und)
 
 
 def test_kernels_are_deterministic():

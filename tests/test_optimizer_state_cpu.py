@@ -108,3 +108,90 @@ def test_state_dict_before_the_first_step(lib, optimizer, extra):
     group = dict(lr=1e-4, betas=(0.9, 0.999), eps=1e-8, **extra, params=list(range(n)))
     assert sd == {"state": {}, "param_groups": [group], "global_step": 0}
     assert list(sd) == ["state", "param_groups", "global_step"] and list(sd["param_groups"][0]) == list(group)
+
+
+_SGD_ARGS = dict(momentum=0.0, dampening=0.0, nesterov=False)
+_ADAFACTOR_ARGS = dict(eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, scale_parameter=True, relative_step=True,
+                       warmup_init=False)
+_MUON_ARGS = dict(momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None)
+_SF_ARGS = dict(warmup_steps=0, r=0.0, weight_lr_power=2.0)
+_BLOCK_ARGS = dict(min_8bit_size=4096, blocksize=256)
+# optimizer= name -> (alias, family, state class, weight decay, optimizer_args) as resolve_family returned them before the families
+# shared one table ("adamw" and its aliases have always carried Prodigy's defaults, which nothing reads)
+_FAMILIES = {
+    "adamw": (None, "adamw", "AdamWState", 0.01, _PRODIGY_ARGS),
+    "adam": ("adam", "adamw", "AdamWState", 0.0, _PRODIGY_ARGS),
+    "adam8bit": ("adam8bit", "adamw", "AdamWState", 0.0, _PRODIGY_ARGS),
+    "prodigy": (None, "prodigy", "ProdigyState", 0.0, _PRODIGY_ARGS),
+    "sgd": (None, "sgd", "SgdState", 0.0, _SGD_ARGS),
+    "adafactor": (None, "adafactor", "AdafactorState", 0.0, _ADAFACTOR_ARGS),
+    "muon": (None, "muon", "MuonState", 0.1, _MUON_ARGS),
+    "adamw_schedulefree": (None, "adamw_schedulefree", "ScheduleFreeAdamWState", 0.0, _SF_ARGS),
+    "adam8bit_blockwise": (None, "adam8bit_blockwise", "BlockwiseState", 0.0, _BLOCK_ARGS),
+    "adamw8bit_blockwise": (None, "adamw8bit_blockwise", "BlockwiseState", 0.01, _BLOCK_ARGS),
+    "lion": (None, "lion", "LionState", 0.0, {}),
+    "lion8bit_blockwise": (None, "lion8bit_blockwise", "LionBlockwiseState", 0.0, _BLOCK_ARGS),
+}
+
+
+@pytest.mark.parametrize("optimizer", sorted(_FAMILIES))
+def test_resolve_family_table(lib, optimizer):
+    """Every accepted name resolves to what it always has; an unknown optimizer_args key, and any key for a family that takes none,
+    is refused with the same exception."""
+    from qflux_amd.trainer import optim_state as OS
+    alias, family, cls, wd, args = OS.resolve_family(optimizer)
+    want = _FAMILIES[optimizer]
+    assert (alias, family, cls.__name__, wd, args) == want and list(args) == list(want[4])
+    assert type(wd) is float and cls is getattr(OS, want[2])
+    with pytest.raises(ValueError) as ei:
+        OS.resolve_family(optimizer, None, {"bogus": 1})
+    assert str(ei.value) == f"unsupported optimizer_args for {family}: ['bogus']"
+    if family in ("adamw", "lion"):      # no optimizer_args at all, not even a name another family knows
+        with pytest.raises(ValueError) as ei:
+            OS.resolve_family(optimizer, None, {"d0": 1e-6})
+        assert str(ei.value) == f"unsupported optimizer_args for {family}: ['d0']"
+
+
+def test_resolve_family_unknown_name(lib):
+    from qflux_amd.trainer import optim_state as OS
+    with pytest.raises(ValueError) as ei:
+        OS.resolve_family("adagrad")
+    assert str(ei.value) == "unknown optimizer 'adagrad'"
+    with pytest.raises(NotImplementedError, match="adam8bit with L2 weight decay 0.01"):
+        OS.resolve_family("adam8bit", 0.01)
+
+
+@pytest.mark.parametrize("name", ["BlockwiseState", "LionBlockwiseState"])
+@pytest.mark.parametrize("blocksize", [256, 2048])
+def test_blockwise_state_save_load_round_trip(lib, name, blocksize):
+    """One 8-bit tensor (a short last block) and one fp32-moment tensor: every buffer comes back from save -> load bit for bit, the
+    block size from the file."""
+    import types
+    from qflux_amd.trainer import optim_state as OS
+    cls = getattr(OS, name)
+    ps = [torch.zeros(3, blocksize + 1), torch.zeros(5)]
+    entries, off = [], 0
+    for i, p in enumerate(ps):
+        entries.append((f"p{i}", p, off, p.numel()))
+        off += (p.numel() + 3) // 4 * 4                                     # the flat buffer's 16-byte alignment
+    store = types.SimpleNamespace(entries=entries, pflat=torch.zeros(off))
+    args = dict(min_8bit_size=64, blocksize=blocksize)
+    state = cls(store, args)
+    assert [e[2] for e in state.layout.tensors] == [True, False]
+    g = torch.Generator().manual_seed(11)
+    (o8, k8, _, a0, nb, _), (_, k32, _, _, _, s0) = state.layout.tensors
+    for n, t in state.buffers():          # random values in the elements a parameter owns (the rest is never saved)
+        lo, k = (o8, k8) if n[0] == "q" else (a0, nb) if n.startswith("absmax") else (s0, k32)
+        if not n.startswith("qmap"):
+            t[lo:lo + k] = torch.randint(0, 256, (k,), generator=g).to(t.dtype) if t.dtype == torch.uint8 else torch.randn(k, generator=g)
+    state.qmap1[3] += 1e-3                                                  # the file's code book, not the default one, comes back
+    extra, per = cls.save(state, entries, 7, args)
+    assert extra == {} and sorted(per) == [0, 1]
+    moments = 2 if name == "BlockwiseState" else 1
+    assert sorted(per[1]) == ["state1", "state2"][:moments] + ["step"]
+    args2 = dict(min_8bit_size=64, blocksize=256)
+    loaded, step = cls.load(store, {"state": per, "param_groups": [{}]}, args2)
+    assert step == 7 and args2["blocksize"] == blocksize
+    assert [n for n, _ in loaded.buffers()] == list(cls.NAMES) and len(cls.NAMES) == 4 * moments
+    for (n, a), (_, b) in zip(state.buffers(), loaded.buffers()):
+        assert a.dtype == b.dtype and torch.equal(a, b), n

@@ -78,6 +78,21 @@ def test_lengths_and_alignment(n, shift):
         assert bool((b[:shift] == GUARD).all()) and bool((b[shift + n:] == GUARD).all()), (n, shift)
 
 
+def test_clip_active_at_every_step_aligned_and_offset_view():
+    """max_norm a quarter of the smallest scaled gradient norm, so the clip acts at both steps, at the smallest length with a 16-byte
+    body and a scalar tail: the aligned run and the view one element in (the scalar instantiation) give the same bits and meet the
+    restatement as every other case does."""
+    n = 4 * 256 + 3
+    y, grads, gsq = R.make_inputs(n, 2)
+    max_norm = 0.25 * min(s ** 0.5 * 0.5 for s in gsq)
+    r64, r32 = (R.run(y, grads, gsq, dt, max_norm=max_norm, **KW) for dt in (torch.float64, torch.float32))
+    runs = [_kernel_run(y, grads, gsq, KW, shift=shift, max_norm=max_norm)[0] for shift in (0, 1)]
+    for it in range(2):
+        for i, name in enumerate(("y", "z", "v")):
+            R.check(name, runs[0][it][i], r32[it][i], r64[it][i], f"n={n} clipped step {it}")
+            assert torch.equal(runs[0][it][i], runs[1][it][i]), (it, name)
+
+
 @pytest.mark.parametrize("beta1", [0.9, 0.4])
 def test_swap_matches_torch_lerp_and_round_trips(beta1):
     """beta1 = 0.9: weights -0.111.. and 0.1, the |w| < 0.5 branch; beta1 = 0.4: -1.5 and 0.6, the other one."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Build kernel-variant libraries for tools/step_ab.py:  python tools/build_variants.py name=-DFLAG1,-DFLAG2 name2=-DX ...
--> tools/_ab/libqfx_<name>.so (the four csrc files with the extra flags; objects of unaffected files are shared via a cache
+-> tools/_ab/libqfx_<name>.so (every csrc file of the build with the extra flags; objects of unaffected files are shared via a cache
 keyed by (file, flags that occur in it))."""
 import hashlib
 import os
@@ -11,10 +11,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "qwen-image-finetune_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "_ab")
-SOURCES = ["qfx_gemm.hip", "qfx_gemm_fp8.hip", "qfx_skinny.hip", "qfx_elem.hip", "qfx_attn.hip", "qfx_attn64.hip", "qfx_attn_bwd1.hip", "qfx_cond.hip",
-           "qfx_adafactor.hip", "qfx_lion.hip", "qfx_muon.hip", "qfx_schedulefree.hip"]
-EXTRA_FLAGS = {"qfx_attn64.hip": ["-fno-slp-vectorize"], "qfx_attn_bwd1.hip": ["-fno-slp-vectorize"], "qfx_lion.hip": ["-ffp-contract=off"],
-               "qfx_muon.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "qfx_schedulefree.hip": ["-ffp-contract=off"]}
+sys.path.insert(0, ROOT)
+from __graft_entry__ import EXTRA_FLAGS, PLAIN_SOURCES, SOURCES  # noqa: E402
 
 
 def main():
@@ -25,8 +23,8 @@ def main():
         name, _, fl = spec.partition("=")
         flags = [f for f in fl.split(",") if f]
         objs = []
-        for src in SOURCES:
-            text = (open(os.path.join(CSRC, src)).read() + open(os.path.join(CSRC, "qfx_common.h")).read() +
+        for src in SOURCES + PLAIN_SOURCES:
+            text = (open(os.path.join(CSRC, src)).read() + open(os.path.join(CSRC, "qfx_common.h")).read() + open(os.path.join(CSRC, "qfx_optim.h")).read() +
                     open(os.path.join(CSRC, "qfx_attn_common.h")).read() + open(os.path.join(ROOT, "include", "qfx.h")).read())
             rel = [f for f in flags if re.sub(r"^-D", "", f).split("=")[0] in text]
             key = hashlib.sha1((src + "|" + " ".join(rel) + "|" + hashlib.sha1(text.encode()).hexdigest()).encode()).hexdigest()[:16]
