@@ -141,7 +141,7 @@ class CondHeadHip:
 
     def emit_backward(self, p):
         """Reads the fp32 gradient buffers of the banks (filled by the blocks' qfx_mod_grad launches); LAST entries of the
-        backward program (data-parallel: these adapters' gradients are final only here, trainer._bucket_hook)."""
+        backward program (data-parallel: these adapters' gradients are final only here, dp.LoraGradSync.hook)."""
         B, D = self.B, self.D
         if self.need_dtemb:
             p.py(self.ds.zero_)

@@ -1,4 +1,7 @@
-"""Data-parallel gradient exchange for the DROP-IN path (the reference's own trainer loop around `dit(...)` / `loss.backward()`).
+"""Data-parallel plumbing over the flat LoRA buffers: the bucketed gradient exchange (LoraGradSync), the process-group set-up
+(init_distributed_from_env) and the replica checksum (check_replicas).
+
+The DROP-IN path (the reference's own trainer loop around `dit(...)` / `loss.backward()`):
 
 The reference wraps its container of LoRA layers in DDP (accelerator.prepare, src/qflux/trainer/base_trainer.py:384-393) and DDP
 reduces a gradient when autograd ACCUMULATES it into the parameter.  Here the whole DiT is one autograd node whose kernels write
@@ -11,12 +14,13 @@ therefore exchanges its gradients itself:
                              # averaged (DDP semantics) before backward() returns
     with dit.no_sync(): ...  # gradient-accumulation micro-steps (accelerate's `accumulate(self.dit)` finds this method by name)
 
-The fused step (QwenLoraTrainStep.train_step) has its own copy of the same exchange with the 1/world factor folded into the
-optimizer kernel.
+The fused step (QwenLoraTrainStep.train_step) holds a LoraGradSync of its own (step.sync: its group and bucket size may differ),
+drains it with finish(average=False) and folds the 1/world factor into the optimizer kernel.
 """
 from __future__ import annotations
 
 import contextlib
+import os
 
 import torch
 import torch.distributed as dist
@@ -36,8 +40,9 @@ def contiguous_runs(idx, ents):
 
 
 class LoraGradSync:
-    def __init__(self, dit, process_group=None, bucket_mb: float = 24.0):
-        self.dit, self.group = dit, process_group
+    def __init__(self, dit, process_group=None, bucket_mb: float = 24.0, force: bool = False):
+        """force: exchange on a ONE-rank group too (the fused step's QFX_DP_FORCE=1; read by the owner, who decides when to hook)."""
+        self.dit, self.group, self.force = dit, process_group, force
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         self.bucket_bytes = int(bucket_mb * (1 << 20))
         self.enabled = True
@@ -91,6 +96,15 @@ class LoraGradSync:
             self.dit.lora_store.gflat.mul_(1.0 / self.world)
         self.exchanged = True
 
+    @property
+    def armed(self):
+        """A hook() of this object was handed to a backward program and finish() has not drained it yet."""
+        return self._finish is not None
+
+    def disarm(self):
+        """Drop an armed hook without running it (nothing was started through it: a captured graph replays no callback)."""
+        self._finish = None
+
 
 class DataParallelMixin:
     """enable_data_parallel / no_sync for the drop-in DiT modules (see module docstring)."""
@@ -125,3 +139,44 @@ class DataParallelMixin:
             return
         plan.run_backward(grad_out, on_segment=dp.hook())
         dp.finish(average=True)
+
+
+def init_distributed_from_env():
+    """One process per GPU; backend "nccl" is RCCL on ROCm.  Returns (rank, local_rank, world).
+    Test hooks: QFX_DIST_BACKEND=gloo and QFX_SHARE_GPU=1 let several ranks share device 0 (RCCL refuses duplicate devices), so
+    the multi-rank code path can be exercised on a one-GPU box."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if os.environ.get("QFX_SHARE_GPU") == "1":
+        local = 0
+    if torch.cuda.is_available():
+        torch.cuda.set_device(local)   # before the process group: RCCL binds to the current device
+    if (world > 1 or os.environ.get("QFX_BENCH_INIT_PG") == "1") and not dist.is_initialized():     # (one-rank group: tools/rccl_one_rank.py)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        backend = os.environ.get("QFX_DIST_BACKEND", "nccl" if torch.cuda.is_available() else "gloo")
+        dist.init_process_group(backend=backend, rank=rank, world_size=world)
+    return rank, local, world
+
+
+def check_replicas(buffers, world, group=None, what: str = "adapter weights"):
+    """Raises if the named buffers [(name, tensor or None)] differ between ranks: two order-sensitive fp64 checksums per buffer (and
+    whether the rank has it at all), gathered and compared on every rank of the group (`world` of them, more than one).  Cheap: one
+    small all-gather."""
+    dev = buffers[0][1].device
+    sums = []
+    for _, t in buffers:      # fixed layout: a buffer a rank lacks is part of the verdict
+        if t is None:
+            sums += [torch.zeros((), dtype=torch.float64, device=dev)] * 3
+            continue
+        d = t.detach().double().flatten()
+        w = torch.arange(1, d.numel() + 1, device=d.device, dtype=torch.float64) % 8191
+        sums += [torch.ones((), dtype=torch.float64, device=dev), d.sum(), (d * w).sum()]
+    mine = torch.stack(sums)
+    out = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(out, mine, group=group)
+    for r, o in enumerate(out):
+        if not torch.equal(o, out[0]):
+            raise RuntimeError(f"data-parallel replicas diverged ({what}): rank {r} differs from rank 0 "
+                               f"(checksums {o.tolist()} vs {out[0].tolist()}); call broadcast_state() after loading state")
+    return True

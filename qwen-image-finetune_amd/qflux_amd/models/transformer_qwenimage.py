@@ -27,6 +27,7 @@ from ..modules import (LoraConfig, LoraStore, QfxLinear, QfxLoraLinear, QfxRMSNo
 from ..plan.prog import _ceil
 from ..plan.qwen import _QwenDiTFn, _QwenPlan
 from ..rope import QwenEmbedRope, normalize_img_shapes
+from ..schedules import flowmatch_tables
 
 lib = L.lib
 BF = torch.bfloat16
@@ -404,7 +405,6 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
 
     def _modulation_keys(self):
         if self._mod_keys is None:
-            from ..trainer.qwen_step import flowmatch_tables
             return (flowmatch_tables()[0] / 1000).to(F32).contiguous()
         return self._mod_keys
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 import torch
 
 from .trainer import optim_state as OS
-from .trainer.qwen_step import optimizer_kwargs_from_config
+from .trainer.optim_config import optimizer_kwargs_from_config
 
 __all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree"]
 

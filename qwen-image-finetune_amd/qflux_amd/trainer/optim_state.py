@@ -646,7 +646,37 @@ def default_betas(optimizer):
 
 def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     """The `optimizer=` keyword of the train steps (and of the torch.optim classes in qflux_amd.optim) -> (alias or None, family name,
-    state class, weight decay, the family's optimizer_args with defaults filled in)."""
+    state class, weight decay, the family's optimizer_args with defaults filled in).
+    optimizer: "adamw" (torch.optim.AdamW semantics, the train step's lr/betas/eps/weight_decay) or "prodigy" (prodigyopt.Prodigy, the
+    reference's parameter-free choice: configs/face_seg_flux_kontext_fp16_prodigy.yaml:41-47); optimizer_args = the extra
+    init_args of that class (use_bias_correction, safeguard_warmup, beta3, decouple, d0, d_coef, growth_rate).  With Prodigy
+    `lr` is the schedule multiplier the reference sets to 1.0.
+    "adam8bit_blockwise" / "adamw8bit_blockwise": bitsandbytes.optim.Adam8bit / AdamW8bit with their blockwise 8-bit moments and
+    state layout (trainer/adam8bit.py; weight decay decoupled, defaults 0 / 1e-2); optimizer_args: min_8bit_size (4096), blocksize
+    (256 or 2048).
+    "sgd": torch.optim.SGD, the fourth optimizer the reference documents (docs/guide/training.md:768-826: momentum 0.9, weight_decay
+    1e-4; weight decay in the L2 form, default 0); optimizer_args: momentum (0), dampening (0), nesterov (False); betas / eps unused.
+    "adafactor": transformers.optimization.Adafactor (factored second moments per adapter matrix, update clipping; weight decay
+    scaled by the step's learning rate, default 0); optimizer_args: eps ((1e-30, 1e-3)), clip_threshold (1.0), decay_rate (-0.8),
+    beta1 (None), scale_parameter (True), relative_step (True), warmup_init (False).  lr must be None with relative_step (the
+    default) and a float without it; betas / eps unused.
+    "lion": lion_pytorch.Lion / bitsandbytes.optim.Lion (one fp32 moment, the update is lr times the sign of the interpolated
+    moment; weight decay decoupled, before the update, default 0); no optimizer_args; eps unused.  "lion8bit_blockwise":
+    bitsandbytes.optim.Lion8bit / PagedLion8bit with the moment in blockwise 8-bit codes and bnb's one-state layout;
+    optimizer_args: min_8bit_size (4096), blocksize (256 or 2048).
+    "muon": torch.optim.Muon (per adapter matrix: Nesterov momentum, then five Newton-Schulz iterations in bf16 on the matrix
+    units orthogonalise the update; weight decay decoupled, default the class's 0.1); optimizer_args: momentum (0.95), nesterov
+    (True), ns_coefficients ((3.4445, -4.7750, 2.0315)), ns_steps (5), adjust_lr_fn (None = "original", or "match_rms_adamw") and
+    eps (1e-7: Muon's own, the floor of the update's norm, not the train step constructor's Adam eps); betas / eps unused.
+    "adamw_schedulefree": schedulefree.AdamWScheduleFree (Defazio et al. 2024: Adam's second moment, no first moment and no
+    schedule -- the gradient is taken at y, an interpolation between the base sequence z and the running average x; made for a
+    constant lr; weight decay in the L2 form on y, default 0; the package's lr is 0.0025); optimizer_args: warmup_steps (0: the
+    optimizer's own linear warm-up), r (0.0) and weight_lr_power (2.0): the averaging weight of step k is (k + 1)^r lr_max^power.
+    The adapter weights hold y while training: eval() / train() / eval_mode() swap them to x and back, save_checkpoint writes x,
+    and the samplers take train_step= to sample from x.
+    betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, (0.9, 0.999) --
+    torch.optim.AdamW's, the train step constructor's default before Lion -- for every other one; betas given explicitly are never
+    reinterpreted."""
     if optimizer not in ("adam", "adam8bit") and optimizer not in FAMILIES:
         raise ValueError(f"unknown optimizer {optimizer!r}")
     alias = None

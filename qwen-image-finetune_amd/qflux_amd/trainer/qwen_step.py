@@ -12,6 +12,9 @@ Two ways to drive it:
   * fused (bench / production): `step.train_step(embeddings)` = prepare -> DiT forward program -> criterion
     kernel (loss + dpred) -> DiT backward program -> all-reduce -> fused clip+AdamW; no autograd graph, no
     host synchronisation anywhere in the step.
+
+Beside the step: the bucketed gradient exchange is dp.LoraGradSync (step.sync), the YAML -> keyword mapping is
+trainer/optim_config.py, the timestep tables and lr schedules are qflux_amd/schedules.py.
 """
 from __future__ import annotations
 
@@ -22,20 +25,13 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
+from ..dp import LoraGradSync, check_replicas, init_distributed_from_env  # noqa: F401  (the last: bench.py and tools/ import it from here)
+from ..schedules import flowmatch_tables
 from . import adam8bit as A8
 from . import optim_state as OS
 from .optim_state import resolve_family
 
 BF = torch.bfloat16
-
-
-def flowmatch_tables(num_train_timesteps: int = 1000, shift: float = 1.0):
-    """FlowMatchEulerDiscreteScheduler.timesteps / .sigmas as built at construction (third-party lookup
-    tables, qwen_image_edit_trainer.py:807-810,851-861; dynamic shifting => identity shift at init)."""
-    ts = torch.linspace(1, num_train_timesteps, num_train_timesteps).flip(0)
-    sig = ts / num_train_timesteps
-    sig = shift * sig / (1 + (shift - 1) * sig)
-    return sig * num_train_timesteps, sig
 
 
 def map_mask_to_latent(image_mask: torch.Tensor) -> torch.Tensor:
@@ -52,36 +48,10 @@ class QwenLoraTrainStep:
     def __init__(self, dit, lr=1e-4, betas=None, eps=1e-8, weight_decay=None, max_grad_norm=1.0,
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
                  bucket_mb=24.0, optimizer="adamw", optimizer_args=None):
-        """optimizer: "adamw" (torch.optim.AdamW semantics, lr/betas/eps/weight_decay above) or "prodigy" (prodigyopt.Prodigy, the
-        reference's parameter-free choice: configs/face_seg_flux_kontext_fp16_prodigy.yaml:41-47); optimizer_args = the extra
-        init_args of that class (use_bias_correction, safeguard_warmup, beta3, decouple, d0, d_coef, growth_rate).  With Prodigy
-        `lr` is the schedule multiplier the reference sets to 1.0.
-        "adam8bit_blockwise" / "adamw8bit_blockwise": bitsandbytes.optim.Adam8bit / AdamW8bit with their blockwise 8-bit moments and
-        state layout (trainer/adam8bit.py; weight decay decoupled, defaults 0 / 1e-2); optimizer_args: min_8bit_size (4096), blocksize
-        (256 or 2048).
-        "sgd": torch.optim.SGD, the fourth optimizer the reference documents (docs/guide/training.md:768-826: momentum 0.9, weight_decay
-        1e-4; weight decay in the L2 form, default 0); optimizer_args: momentum (0), dampening (0), nesterov (False); betas / eps unused.
-        "adafactor": transformers.optimization.Adafactor (factored second moments per adapter matrix, update clipping; weight decay
-        scaled by the step's learning rate, default 0); optimizer_args: eps ((1e-30, 1e-3)), clip_threshold (1.0), decay_rate (-0.8),
-        beta1 (None), scale_parameter (True), relative_step (True), warmup_init (False).  lr must be None with relative_step (the
-        default) and a float without it; betas / eps unused.
-        "lion": lion_pytorch.Lion / bitsandbytes.optim.Lion (one fp32 moment, the update is lr times the sign of the interpolated
-        moment; weight decay decoupled, before the update, default 0); no optimizer_args; eps unused.  "lion8bit_blockwise":
-        bitsandbytes.optim.Lion8bit / PagedLion8bit with the moment in blockwise 8-bit codes and bnb's one-state layout;
-        optimizer_args: min_8bit_size (4096), blocksize (256 or 2048).
-        "muon": torch.optim.Muon (per adapter matrix: Nesterov momentum, then five Newton-Schulz iterations in bf16 on the matrix
-        units orthogonalise the update; weight decay decoupled, default the class's 0.1); optimizer_args: momentum (0.95), nesterov
-        (True), ns_coefficients ((3.4445, -4.7750, 2.0315)), ns_steps (5), adjust_lr_fn (None = "original", or "match_rms_adamw") and
-        eps (1e-7: Muon's own, the floor of the update's norm, not this constructor's Adam eps); betas / eps unused.
-        "adamw_schedulefree": schedulefree.AdamWScheduleFree (Defazio et al. 2024: Adam's second moment, no first moment and no
-        schedule -- the gradient is taken at y, an interpolation between the base sequence z and the running average x; made for a
-        constant lr; weight decay in the L2 form on y, default 0; the package's lr is 0.0025); optimizer_args: warmup_steps (0: the
-        optimizer's own linear warm-up), r (0.0) and weight_lr_power (2.0): the averaging weight of step k is (k + 1)^r lr_max^power.
-        The adapter weights hold y while training: eval() / train() / eval_mode() swap them to x and back, save_checkpoint writes x,
-        and the samplers take train_step= to sample from x.
-        betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, (0.9, 0.999) --
-        torch.optim.AdamW's, this constructor's default before Lion -- for every other one; betas given explicitly are never
-        reinterpreted.
+        """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
+        that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
+        schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
+        without it.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
@@ -109,17 +79,20 @@ class QwenLoraTrainStep:
         self.global_step = 0
         self._gnorm = self._gparts = None
         # data-parallel exchange overlapped with the backward: the flat gradient is all-reduced in buckets of whole DiT
-        # blocks as soon as their backward segment has been enqueued (the gradient of block i is final when its segment ends)
-        self.bucket_bytes = int(bucket_mb * (1 << 20))
-        self._pending = []
-        self._finish_buckets = None
-        self._reduced = False
-        self._synced = False      # rank 0's adapter / optimizer state is broadcast before the first step (broadcast_state)
-        self._synced_version = None
+        # blocks as soon as their backward segment has been enqueued (the gradient of block i is final when its segment ends).
+        # An exchange object of this step's own, apart from dit._dp (the drop-in path's: group and bucket size may differ).
         # QFX_DP_FORCE=1: run the bucketed exchange on a ONE-rank process group too (the collectives are then identities) -- lets a
         # one-GPU box execute the real RCCL code path: communicator, RCCL's stream, async handles, ordering against the main and
         # the side gradient stream (tests/test_dp_gpu.py)
-        self._force_dp = os.environ.get("QFX_DP_FORCE", "0") == "1" and dist.is_available() and dist.is_initialized()
+        self.sync = LoraGradSync(dit, process_group, bucket_mb,
+                                 force=os.environ.get("QFX_DP_FORCE", "0") == "1" and dist.is_available() and dist.is_initialized())
+        self._synced = False      # rank 0's adapter / optimizer state is broadcast before the first step (broadcast_state)
+        self._synced_version = None
+
+    @property
+    def bucket_bytes(self):
+        """The exchange's bucket size (bench.py reports it)."""
+        return self.sync.bucket_bytes
 
     def _ensure_synced(self):
         """Rank 0's adapter + optimizer state reaches every rank before the first step AND again whenever the model's adapter set
@@ -212,7 +185,7 @@ class QwenLoraTrainStep:
         else:
             loss, dpred = ops.mse_token_weighted_fwd_bwd(pred, target, tok_w, n_tok, inv_denom, gscale=grad_scale)
         self._mark_unexchanged()       # local gradients are added below: whatever exchange a drop-in backward did before is stale
-        plan.run_backward(dpred, on_segment=self._bucket_hook() if ((self.world > 1 or self._force_dp) and sync) else None)
+        plan.run_backward(dpred, on_segment=self.sync.hook() if ((self.world > 1 or self.sync.force) and sync) else None)
         return loss
 
     # ------------------------------------------------------------------ hipGraph replay of the DiT part of the step
@@ -268,7 +241,7 @@ class QwenLoraTrainStep:
             self._ensure_synced()
             self._mark_unexchanged()
             graph.replay()
-            self._finish_buckets = None
+            self.sync.disarm()
             self.optimizer_step(grad_scale=self.allreduce_grads())
             self.zero_grad()
             return loss_static.clone()      # the graph overwrites loss_static on every replay
@@ -276,53 +249,12 @@ class QwenLoraTrainStep:
         step.graph = graph
         return step
 
-    # ------------------------------------------------------------------ bucketed all-reduce behind the backward
-    def _bucket_hook(self):
-        st = self.dit.lora_store
-        ents = st.entries
-        todo = set(range(len(ents)))
-        acc = []          # entry indices final but not yet reduced
-        self._pending, self._reduced = [], False
-
-        def flush(force=False):
-            nbytes = sum(((ents[i][3] + 63) // 64 * 64) * 4 for i in acc)
-            if not acc or (not force and nbytes < self.bucket_bytes):
-                return
-            for lo, hi in _contiguous_runs(sorted(acc), ents):
-                self._pending.append(dist.all_reduce(st.gflat[lo:hi], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
-            acc.clear()
-
-        # adapters of the conditioning head (AdaLN modulation linears img_mod.1 / txt_mod.1, FLUX norm*.linear, the embedders) live
-        # under the block prefixes too, but their gradients are written by the LAST call of the backward program (the head's own
-        # backward, fed by the d(modulation) column sums of every block): they are never final at a block mark and go out with
-        # finish(), after the whole program
-        cond_sfx = tuple(getattr(self.dit, "_COND_SUFFIXES", ()))
-        late = {i for i in todo if cond_sfx and ents[i][0].split(".lora_")[0].endswith(cond_sfx)}
-
-        def hook(prefix):
-            done = [i for i in todo if i not in late and ents[i][0].startswith(prefix)]
-            todo.difference_update(done)
-            acc.extend(done)
-            flush()
-
-        def finish():
-            acc.extend(sorted(todo))   # adapters outside the marked blocks, if any
-            todo.clear()
-            flush(force=True)
-
-        self._finish_buckets = finish
-        return hook
-
+    # ------------------------------------------------------------------ gradient exchange (the buckets: dp.LoraGradSync)
     def allreduce_grads(self):
         """Returns the factor the optimizer applies to the summed gradient (1/world)."""
-        if self.world > 1 or self._force_dp:
-            fin = self._finish_buckets
-            if fin is not None:
-                fin()
-                self._finish_buckets = None
-                for w in self._pending:
-                    w.wait()
-                self._pending = []
+        if self.world > 1 or self.sync.force:
+            if self.sync.armed:
+                self.sync.finish(average=False)
             else:   # no bucketed backward of THIS object ran (drop-in autograd path, or the hipGraph replay)
                 dp = getattr(self.dit, "_dp", None)
                 if dp is not None and dp.exchanged:
@@ -487,25 +419,7 @@ class QwenLoraTrainStep:
     def check_replicas(self, what: str = "adapter weights"):
         """Raises if the adapter weights (and optimizer buffers) differ between ranks: two order-sensitive fp64 checksums per
         buffer, gathered and compared on every rank.  Cheap (one small all-gather); call it after loading state and periodically."""
-        if self.world <= 1:
-            return True
-        dev = self.dit.lora_store.pflat.device
-        sums = []
-        for _, t in self._state_buffers():      # fixed layout: a buffer a rank lacks is part of the verdict
-            if t is None:
-                sums += [torch.zeros((), dtype=torch.float64, device=dev)] * 3
-                continue
-            d = t.detach().double().flatten()
-            w = torch.arange(1, d.numel() + 1, device=d.device, dtype=torch.float64) % 8191
-            sums += [torch.ones((), dtype=torch.float64, device=dev), d.sum(), (d * w).sum()]
-        mine = torch.stack(sums)
-        out = [torch.zeros_like(mine) for _ in range(self.world)]
-        dist.all_gather(out, mine, group=self.group)
-        for r, o in enumerate(out):
-            if not torch.equal(o, out[0]):
-                raise RuntimeError(f"data-parallel replicas diverged ({what}): rank {r} differs from rank 0 "
-                                   f"(checksums {o.tolist()} vs {out[0].tolist()}); call broadcast_state() after loading state")
-        return True
+        return self.world <= 1 or check_replicas(self._state_buffers(), self.world, self.group, what)
 
     def train_step(self, embeddings, noise=None, u=None, micro_batches=None):
         """One full optimisation step; returns the (device) loss.  micro_batches: optional list of further embedding dicts
@@ -527,198 +441,3 @@ class QwenLoraTrainStep:
             dist.all_gather(out, loss, group=self.group)
             return torch.stack(out).mean()
         return loss
-
-
-# qflux_amd.optim class -> (the class it stands in for, the state_bits it implies)
-_OWN_CLASSES = {"qflux_amd.optim.AdamW": ("torch.optim.AdamW", 32), "qflux_amd.optim.Adam": ("torch.optim.Adam", 32),
-                "qflux_amd.optim.Adam8bit": ("bitsandbytes.optim.Adam8bit", 8), "qflux_amd.optim.AdamW8bit": ("bitsandbytes.optim.AdamW8bit", 8),
-                "qflux_amd.optim.Prodigy": ("prodigyopt.Prodigy", 0), "qflux_amd.optim.SGD": ("qflux_amd.optim.SGD", 0),
-                "qflux_amd.optim.Adafactor": ("transformers.optimization.Adafactor", 0),
-                "qflux_amd.optim.Muon": ("torch.optim.Muon", 0),
-                "qflux_amd.optim.AdamWScheduleFree": ("schedulefree.AdamWScheduleFree", 0),
-                "qflux_amd.optim.Lion8bit": ("bitsandbytes.optim.Lion8bit", 8),
-                "qflux_amd.optim.PagedLion8bit": ("bitsandbytes.optim.PagedLion8bit", 8)}
-_ADAFACTOR = ("transformers.optimization.Adafactor", "transformers.Adafactor")
-_MUON = ("torch.optim.Muon",)
-_SCHEDULEFREE = ("schedulefree.AdamWScheduleFree",)
-_LION = ("lion_pytorch.Lion", "bitsandbytes.optim.Lion", "bitsandbytes.optim.Lion32bit")
-_BNB_LION_8BIT = ("bitsandbytes.optim.Lion8bit", "bitsandbytes.optim.PagedLion8bit")
-_BNB_8BIT = ("bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.PagedAdam8bit", "bitsandbytes.optim.AdamW8bit",
-             "bitsandbytes.optim.PagedAdamW8bit")
-
-
-def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None, state_bits: int = 32) -> dict:
-    """The reference's YAML `optimizer: {class_path, init_args}` (BaseTrainer.configure_optimizers, base_trainer.py:884-909) ->
-    keyword arguments of QwenLoraTrainStep / FluxKontextTrainStep.
-        torch.optim.AdamW                      -> optimizer="adamw"   (lr, betas, eps, weight_decay)
-        bitsandbytes.optim.Adam8bit / Adam     -> optimizer="adam8bit": Adam with FP32 moments (see __init__; 8-bit states buy nothing
-        bitsandbytes.optim.AdamW8bit / AdamW   -> optimizer="adamw"     next to 288 GB of HBM)
-        prodigyopt.Prodigy                     -> optimizer="prodigy" + optimizer_args
-    state_bits=8 maps the four 8-bit bnb classes (Adam8bit, PagedAdam8bit, AdamW8bit, PagedAdamW8bit) to the blockwise 8-bit optimizer
-    with bnb's state layout instead: "adam8bit_blockwise" (weight decay default 0) / "adamw8bit_blockwise" (default 1e-2), min_8bit_size
-    honoured; percentile_clipping != 100, max_unorm != 0, block_wise=False, skip_zeros=True and amsgrad=True are refused; is_paged only
-    moves memory (same math).  state_bits=32 is the mapping above.
-    The torch.optim classes of qflux_amd.optim (the drop-in loop's optimizers) map to the family each of them runs, whatever state_bits
-    says: AdamW -> "adamw", Adam -> "adam", Adam8bit / AdamW8bit -> "adam8bit_blockwise" / "adamw8bit_blockwise" (the class is named for
-    its state), Prodigy -> "prodigy", SGD -> "sgd" + optimizer_args (momentum, dampening, nesterov; maximize is refused).
-    torch.optim.SGD itself is not mapped.
-        transformers.optimization.Adafactor / transformers.Adafactor / qflux_amd.optim.Adafactor -> optimizer="adafactor" + optimizer_args
-    (eps pair, clip_threshold, decay_rate, beta1, scale_parameter, relative_step, warmup_init); lr is None with relative_step (the
-    package's default) and the package's refusals apply: lr with relative_step, warmup_init without it, no lr without it.
-        lion_pytorch.Lion / bitsandbytes.optim.Lion / Lion32bit -> optimizer="lion" (lr, betas, weight_decay;
-    betas left out = the class's (0.9, 0.99), weight decay default 0); lion_pytorch's use_triton and decoupled_weight_decay=False are
-    accepted (where the arithmetic runs; the plain decoupled form), decoupled_weight_decay=True and cautious_factor != 1 are refused.
-        bitsandbytes.optim.Lion8bit / PagedLion8bit -> "lion" (fp32 moment) with state_bits=32, "lion8bit_blockwise" (bnb's one-state
-    8-bit layout, min_8bit_size honoured) with state_bits=8 -- the Adam8bit rule, with the same init_args refused;
-    qflux_amd.optim.Lion8bit / PagedLion8bit always map to the blockwise form.  The path qflux_amd.optim.Lion itself is NOT mapped
-    here and keeps raising (tests/test_optim_classes_cpu.py pins that refusal): the class exists and steps "lion", a config for the
-    fused train step names lion_pytorch.Lion, whose keywords it takes.
-        torch.optim.Muon / qflux_amd.optim.Muon -> optimizer="muon" + optimizer_args (momentum, nesterov, ns_coefficients, eps,
-    ns_steps, adjust_lr_fn); weight decay left out is the class's 0.1; ns_steps >= 100 and an unknown adjust_lr_fn are refused with
-    torch's messages.
-        schedulefree.AdamWScheduleFree / qflux_amd.optim.AdamWScheduleFree -> optimizer="adamw_schedulefree" + optimizer_args
-    (warmup_steps, r, weight_lr_power); lr and weight decay left out are the class's 0.0025 and 0; foreach is dropped.  Keep the
-    reference's lr_scheduler at `constant`: the warm-up is the optimizer's own warmup_steps.
-    Unknown classes raise: silently training with a different optimizer is worse than stopping."""
-    if state_bits not in (8, 32):
-        raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
-    a = dict(init_args or {})
-    name = class_path.rsplit(".", 1)[-1]
-    given = class_path
-    if class_path in _OWN_CLASSES:
-        class_path, bits = _OWN_CLASSES[class_path]
-        state_bits = bits or state_bits
-    out = {}
-    if class_path in _ADAFACTOR:
-        # lr may be None (relative_step) and eps is the package's pair: both are read here, the package's own refusals apply
-        out["optimizer"] = "adafactor"
-        if "betas" in a:
-            raise NotImplementedError(f"unsupported optimizer init_args for {given}: ['betas']")
-        lr = a.pop("lr", None)
-        out["lr"] = None if lr is None else float(lr)
-        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in OS.AdafactorState.DEFAULTS}
-        if "eps" in out["optimizer_args"]:
-            out["optimizer_args"]["eps"] = tuple(float(e) for e in out["optimizer_args"]["eps"])
-        OS.AdafactorState.validate(dict(OS.AdafactorState.DEFAULTS, **out["optimizer_args"]), out["lr"])
-    if class_path in _MUON:
-        # eps is Muon's own (the norm's floor), one of the family's optimizer_args next to the Newton-Schulz settings
-        out["optimizer"] = "muon"
-        if "betas" in a:
-            raise NotImplementedError(f"unsupported optimizer init_args for {given}: ['betas']")
-        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in OS.MuonState.DEFAULTS}
-        OS.MuonState.validate(dict(OS.MuonState.DEFAULTS, **out["optimizer_args"]))
-        if "ns_coefficients" in out["optimizer_args"]:
-            out["optimizer_args"]["ns_coefficients"] = tuple(float(c) for c in out["optimizer_args"]["ns_coefficients"])
-    for k in ("lr", "eps", "weight_decay"):
-        if k in a:
-            out[k] = float(a.pop(k))
-    if "betas" in a:
-        out["betas"] = tuple(float(b) for b in a.pop("betas"))
-    if state_bits == 8 and class_path in _BNB_8BIT + _BNB_LION_8BIT:
-        adamw = "AdamW" in name
-        out["optimizer"] = "lion8bit_blockwise" if class_path in _BNB_LION_8BIT else "adamw8bit_blockwise" if adamw else "adam8bit_blockwise"
-        out.setdefault("weight_decay", 0.01 if adamw else 0.0)
-        refused = {"percentile_clipping": (100, "percentile clipping"), "max_unorm": (0.0, "update-norm clipping (max_unorm)"),
-                   "block_wise": (True, "non-blockwise 8-bit state"), "skip_zeros": (False, "skip_zeros"), "amsgrad": (False, "amsgrad")}
-        for k, (ok, what) in refused.items():
-            if k in a and a.pop(k) != ok:
-                raise NotImplementedError(f"{given}: {what} is not implemented by the blockwise 8-bit step ({k} must be {ok!r})")
-        if "min_8bit_size" in a:
-            out["optimizer_args"] = {"min_8bit_size": int(a.pop("min_8bit_size"))}
-        a.pop("is_paged", None)        # paged memory: where the state lives, not what is computed
-        a.pop("optim_bits", None)      # the 8-bit classes pass 8 whatever this says
-    elif class_path in ("torch.optim.AdamW", "bitsandbytes.optim.AdamW8bit", "bitsandbytes.optim.AdamW", "bitsandbytes.optim.PagedAdamW8bit"):
-        out["optimizer"] = "adamw"
-    elif class_path in ("torch.optim.Adam", "bitsandbytes.optim.Adam8bit", "bitsandbytes.optim.Adam", "bitsandbytes.optim.PagedAdam8bit"):
-        out["optimizer"] = "adam8bit" if "8bit" in name else "adam"
-        out.setdefault("weight_decay", 0.0)
-    elif class_path in _LION + _BNB_LION_8BIT:
-        out["optimizer"] = "lion"
-        out.setdefault("weight_decay", 0.0)
-        if a.pop("decoupled_weight_decay", False):
-            raise NotImplementedError(f"{given}: decoupled_weight_decay=True (weight decay scaled by lr / the initial lr) is not implemented")
-        if float(a.pop("cautious_factor", 1.0)) != 1.0:
-            raise NotImplementedError(f"{given}: the cautious variant (cautious_factor != 1) is not implemented")
-        a.pop("use_triton", None)      # where lion_pytorch runs the same arithmetic
-    elif given == "qflux_amd.optim.SGD":
-        out["optimizer"] = "sgd"
-        if a.pop("maximize", False):
-            raise NotImplementedError(f"{given}: maximize=True is not implemented")
-        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("momentum", "dampening", "nesterov")}
-        a.pop("differentiable", None)
-    elif class_path in _ADAFACTOR + _MUON:
-        pass
-    elif class_path in _SCHEDULEFREE:
-        out["optimizer"] = "adamw_schedulefree"
-        out.setdefault("lr", 0.0025)
-        out.setdefault("weight_decay", 0.0)
-        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in OS.ScheduleFreeAdamWState.DEFAULTS}
-        OS.ScheduleFreeAdamWState.validate(dict(OS.ScheduleFreeAdamWState.DEFAULTS, **out["optimizer_args"]))
-    elif class_path == "prodigyopt.Prodigy":
-        out["optimizer"] = "prodigy"
-        out["optimizer_args"] = {k: a.pop(k) for k in list(a) if k in ("beta3", "decouple", "use_bias_correction", "safeguard_warmup", "d0",
-                                                                       "d_coef", "growth_rate")}
-    else:
-        raise NotImplementedError(f"optimizer {class_path!r} has no fused counterpart (use the drop-in path with the torch optimizer)")
-    for k in ("min_8bit_size", "percentile_clipping", "block_wise", "optim_bits", "is_paged", "amsgrad", "foreach", "fused"):
-        a.pop(k, None)       # knobs of the 8-bit state / torch dispatch: no meaning for the fused fp32 step
-    if a:
-        raise NotImplementedError(f"unsupported optimizer init_args for {given}: {sorted(a)}")
-    return out
-
-
-def get_scheduler(name: str, num_warmup_steps: int = 0, num_training_steps: int | None = None, num_cycles: float = 0.5):
-    """lr multiplier(step) of diffusers.optimization.get_scheduler for the schedules the reference's configs use
-    (base_trainer.py:900-916): constant, constant_with_warmup, linear, cosine.  Use: step.lr = base_lr * f(global_step)."""
-    import math
-
-    def warm(s):
-        return float(s) / float(max(1, num_warmup_steps)) if s < num_warmup_steps else None
-
-    if name == "constant":
-        return lambda s: 1.0
-    if name == "constant_with_warmup":
-        return lambda s: (warm(s) if warm(s) is not None else 1.0)
-    if name == "linear":
-        return lambda s: (warm(s) if warm(s) is not None else
-                          max(0.0, float(num_training_steps - s) / float(max(1, num_training_steps - num_warmup_steps))))
-    if name == "cosine":
-        def f(s):
-            w = warm(s)
-            if w is not None:
-                return w
-            prog = float(s - num_warmup_steps) / float(max(1, num_training_steps - num_warmup_steps))
-            return max(0.0, 0.5 * (1.0 + math.cos(math.pi * float(num_cycles) * 2.0 * prog)))
-        return f
-    raise ValueError(f"unsupported lr scheduler {name!r}")
-
-
-def _contiguous_runs(idx, ents):
-    """Entry indices -> [lo, hi) element ranges of the flat buffer, merged where adjacent (64-element padded slots)."""
-    runs = []
-    for i in idx:
-        lo = ents[i][2]
-        hi = lo + (ents[i][3] + 63) // 64 * 64
-        if runs and runs[-1][1] == lo:
-            runs[-1][1] = hi
-        else:
-            runs.append([lo, hi])
-    return [(a, b) for a, b in runs]
-
-
-def init_distributed_from_env():
-    """One process per GPU; backend "nccl" is RCCL on ROCm.  Returns (rank, local_rank, world).
-    Test hooks: QFX_DIST_BACKEND=gloo and QFX_SHARE_GPU=1 let several ranks share device 0 (RCCL refuses duplicate devices), so
-    the multi-rank code path can be exercised on a one-GPU box."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if os.environ.get("QFX_SHARE_GPU") == "1":
-        local = 0
-    if torch.cuda.is_available():
-        torch.cuda.set_device(local)   # before the process group: RCCL binds to the current device
-    if (world > 1 or os.environ.get("QFX_BENCH_INIT_PG") == "1") and not dist.is_initialized():     # (one-rank group: tools/rccl_one_rank.py)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = os.environ.get("QFX_DIST_BACKEND", "nccl" if torch.cuda.is_available() else "gloo")
-        dist.init_process_group(backend=backend, rank=rank, world_size=world)
-    return rank, local, world

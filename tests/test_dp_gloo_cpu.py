@@ -109,20 +109,20 @@ def _worker_buckets(rank, world, port, q):
     st = toy.lora_store
     # tiny bucket size: every block flushes on its own -> several async all-reduces in flight
     step = QwenLoraTrainStep(toy, bucket_mb=1e-4)
-    hook = step._bucket_hook()
+    hook = step.sync.hook()
     calls = []
     for i in range(4, -1, -1):   # backward order: last block first
         for n, p in toy.named_parameters():
             if n.startswith(f"transformer_blocks.{i}.") and "lora_" in n:
                 p.grad.fill_(float((rank + 1) * (i + 1)))
         hook(f"transformer_blocks.{i}.")
-        calls.append(len(step._pending))
+        calls.append(len(step.sync._pending))
     for n, p in toy.named_parameters():
         if n.startswith("extra.") and "lora_" in n:
             p.grad.fill_(float(10 * (rank + 1)))
     scale = step.allreduce_grads()
     tot = sum(range(1, world + 1))
-    ok = abs(scale - 1.0 / world) < 1e-12 and calls == sorted(calls) and calls[-1] >= 5 and not step._pending
+    ok = abs(scale - 1.0 / world) < 1e-12 and calls == sorted(calls) and calls[-1] >= 5 and not step.sync._pending
     for n, p in toy.named_parameters():
         if "lora_" not in n:
             continue
@@ -152,11 +152,13 @@ def test_bucketed_allreduce_behind_backward_world2():
     assert sorted(res) == [(0, True), (1, True)], res
 
 
-def _toy_model(n_blocks=3, with_cond=True):
+def _toy_model(n_blocks=3, with_cond=True, cond_blocks=None, extra=False):
+    """cond_blocks: the blocks that carry a conditioning-head adapter (None: all of them, with with_cond); extra: one more adapter
+    outside the marked blocks, first in the flat buffer."""
     from qflux_amd.modules import LoraStore, QfxLinear, QfxLoraLinear
 
     class Blk(nn.Module):
-        def __init__(self):
+        def __init__(self, with_cond):
             super().__init__()
             self.to_q = QfxLoraLinear(QfxLinear(8, 8), 4, 8, "ad")
             if with_cond:      # AdaLN modulation linear of the block: name transformer_blocks.<i>.img_mod.1 (index 0 is the SiLU)
@@ -167,7 +169,9 @@ def _toy_model(n_blocks=3, with_cond=True):
 
         def __init__(self):
             super().__init__()
-            self.transformer_blocks = nn.ModuleList([Blk() for _ in range(n_blocks)])
+            if extra:
+                self.extra = QfxLoraLinear(QfxLinear(8, 8), 4, 8, "ad")
+            self.transformer_blocks = nn.ModuleList([Blk(with_cond and (cond_blocks is None or i in cond_blocks)) for i in range(n_blocks)])
             self._store = LoraStore(self)
             self._store.rebuild("cpu")
 
@@ -178,6 +182,64 @@ def _toy_model(n_blocks=3, with_cond=True):
         device = torch.device("cpu")
 
     return Toy()
+
+
+def _worker_one_exchange(rank, world, port, q):
+    """The fused step and the drop-in model drive ONE exchange (dp.LoraGradSync): on the same toy with the same bucket size both hand
+    dist.all_reduce the same sequence of [lo, hi) ranges of the flat gradient -- one per block mark in backward order, then, from
+    finish(), the adapter outside the marked blocks and LAST the conditioning-head adapter of the block that was marked first.  The
+    fused path leaves the sum and returns 1/world for the optimizer kernel; the drop-in path leaves the mean."""
+    sys.path.insert(0, os.path.join(ROOT, "qwen-image-finetune_amd"))
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from qflux_amd.dp import LoraGradSync
+    from qflux_amd.trainer import QwenLoraTrainStep
+    toy = _toy_model(cond_blocks=(2,), extra=True)
+    toy._dp = LoraGradSync(toy, bucket_mb=1e-4)       # what dit.enable_data_parallel(bucket_mb=1e-4) installs
+    step = QwenLoraTrainStep(toy, bucket_mb=1e-4)     # tiny buckets: every block mark flushes
+    st = toy.lora_store
+    seq, real = [], dist.all_reduce
+
+    def recording(t, *args, **kw):
+        lo = t.storage_offset() - st.gflat.storage_offset()
+        seq.append((lo, lo + t.numel()))
+        return real(t, *args, **kw)
+
+    def backward(hook):
+        del seq[:]
+        st.gflat.fill_(float(rank + 1))
+        for i in (2, 1, 0):
+            hook(f"transformer_blocks.{i}.")
+
+    def span(prefix):
+        own = [(off, off + (k + 63) // 64 * 64) for n, _, off, k in st.entries if n.startswith(prefix)]
+        return min(lo for lo, _ in own), max(hi for _, hi in own)
+
+    def grads_equal(v):
+        return all(bool(p.grad.eq(v).all()) for _, p in st.params())
+
+    dist.all_reduce = recording
+    tot = float(sum(range(1, world + 1)))
+    backward(step.sync.hook())
+    marks = list(seq)
+    scale = step.allreduce_grads()
+    fused = list(seq)
+    ok = scale == 1.0 / world and grads_equal(tot) and not step.sync.armed and toy._dp.exchanged is False
+    backward(toy._dp.hook())
+    toy._dp.finish()
+    ok = ok and grads_equal(tot / world) and toy._dp.exchanged is True
+    dist.all_reduce = real
+    q.put((rank, bool(ok), marks, fused, list(seq), [span(f"transformer_blocks.{i}.to_q.") for i in (2, 1, 0)],
+           span("extra."), span("transformer_blocks.2.img_mod.1.")))
+    dist.destroy_process_group()
+
+
+def test_fused_step_and_drop_in_model_issue_the_same_bucket_sequence_world2():
+    for rank, ok, marks, fused, dropin, blocks, extra, cond in _spawn(_worker_one_exchange, 2, 41500):
+        assert ok, rank
+        assert marks == blocks and fused == dropin == blocks + [extra, cond], (rank, fused, dropin)
+        assert extra[1] <= blocks[2][0] and cond[0] >= blocks[0][1]      # the toy is what the docstring says: extra first, head last
 
 
 def _worker_cond_late(rank, world, port, q):
@@ -192,13 +254,13 @@ def _worker_cond_late(rank, world, port, q):
     from qflux_amd.trainer import QwenLoraTrainStep
     toy = _toy_model()
     step = QwenLoraTrainStep(toy, bucket_mb=1e-4)
-    hook = step._bucket_hook()
+    hook = step.sync.hook()
     for i in range(2, -1, -1):
         for n, p in toy.named_parameters():
             if n.startswith(f"transformer_blocks.{i}.to_q.") and "lora_" in n:
                 p.grad.fill_(float((rank + 1) * (i + 1)))
         hook(f"transformer_blocks.{i}.")
-    for w in step._pending:      # let every early bucket complete BEFORE the head's gradients are written (worst case for the bug:
+    for w in step.sync._pending:      # let every early bucket complete BEFORE the head's gradients are written (worst case for the bug:
         w.wait()                 # the slice has already been reduced when the local gradient lands in it)
     for n, p in toy.named_parameters():
         if ".img_mod.1." in n and "lora_" in n:
@@ -374,7 +436,7 @@ def _worker_ragged(rank, world, port, q, root):
         # a "backward" whose per-rank work depends on the batch's padded shape (ragged buckets): the gradient VALUES differ per
         # rank and per shape, the collective sequence must not
         S_pad = int(batch["image_latents"].shape[1]) + int(batch["control_latents"].shape[1])
-        hook = step._bucket_hook()
+        hook = step.sync.hook()
         for i in range(3, -1, -1):
             for n, p in toy.named_parameters():
                 if n.startswith(f"transformer_blocks.{i}.to_q.") and "lora_" in n:

@@ -51,7 +51,7 @@ def test_two_ranks_one_gpu_stay_identical_and_match_manual_average():
 def test_two_ranks_rccl_stay_identical_and_match_manual_average():
     """Same check over backend "nccl" (= RCCL over xGMI) with one device per rank: the bucketed async all-reduces run on RCCL's
     own stream, ordered against the main stream and the side gradient stream only by the events the step records
-    (qwen_step.py _bucket_hook / allreduce_grads vs base_trainer.py:384-393).  Runs wherever >= 2 GPUs are visible."""
+    (dp.py LoraGradSync.hook / qwen_step.py allreduce_grads vs base_trainer.py:384-393).  Runs wherever >= 2 GPUs are visible."""
     _two_rank_check("nccl")
 
 
@@ -204,7 +204,7 @@ def _worker_rccl1(port, q, force):
     hip, tiny_embeddings = _mk("cuda:0")
     from qflux_amd.trainer import QwenLoraTrainStep
     step = QwenLoraTrainStep(hip, lr=1e-2, bucket_mb=1e-3)      # tiny buckets: one async RCCL all-reduce per DiT block
-    assert step._force_dp == force
+    assert step.sync.force == force
     losses = []
     for s_ in (11, 12, 13):
         emb, noise, u = tiny_embeddings(seed=s_)

@@ -92,7 +92,7 @@ def test_resolve_family_defaults_and_the_train_steps_accept_muon():
 
 
 def test_config_mapping_and_its_refusals():
-    from qflux_amd.trainer.qwen_step import optimizer_kwargs_from_config as K
+    from qflux_amd.trainer import optimizer_kwargs_from_config as K
     for path in ("torch.optim.Muon", "qflux_amd.optim.Muon"):
         assert K(path, {"lr": 1e-3}) == {"optimizer": "muon", "optimizer_args": {}, "lr": 1e-3}
         out = K(path, dict(lr=2e-3, weight_decay=0.0, momentum=0.9, nesterov=False, ns_coefficients=[3.0, -4.0, 2.0], eps=1e-6, ns_steps=3,
