@@ -1,4 +1,5 @@
-"""Argument-struct builders (pure functions of their arguments) and the batching flushes that need no plan state."""
+"""Argument-struct builders (pure functions of their arguments), the batching flushes and the attention-backward emitter: what needs
+no plan state."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,6 +8,7 @@ from collections import namedtuple
 import torch
 
 from .. import _lib as L
+from .. import ops
 from .prog import _ptr
 
 lib = L.lib
@@ -38,6 +40,30 @@ def _gargs(*, A1, lda1, B1, K1, M, N, C_, ldc, ldb1=None, bias=None, A2=None, ld
     g.aux_unmapped = aux_unmapped
     g.row_mask = _ptr(row_mask)
     return _GemmOp(g, (A1, lda1, a_map, g.rows_per_batch, B1), nxt)
+
+
+def _kext(ext, ld, W, K2):
+    """Keywords of a GEMM's second K segment: `ext` (row stride ld) against W over K2 columns -- an adapter's K-extension."""
+    return dict(A2=ext, lda2=ld, B2=W, ldb2=W.stride(0), K2=K2)
+
+
+def emit_attn_backward(p, a, A, mode):
+    """Emit the attention backward of one block into launch program `p`: the two-pass pair qfx_attn_bwd_dq + qfx_attn_bwd_dkv, or the
+    one-pass qfx_attn_bwd_fused (csrc/qfx_attn_bwd1.hip) with its workspace kept once per plan in the arena `A`.  mode (the plan's
+    QFX_ATTN_BWD lever) = 2pass | 1pass | auto; auto (default) = whichever measured faster for the shape: the two-pass pair
+    everywhere as of round 6 (profiles/r06_attn_onepass.json: the ordered fp32 dQ accumulation across key blocks costs what the
+    saved recompute returns)."""
+    if mode == "1pass":
+        if "dq_ws" not in A:
+            A["dq_ws"] = ops.attn_bwd_fused_workspace(a)
+        ws = A["dq_ws"]
+        if ws is not None:
+            a.dq_acc, a.dq_turn = ws[0].data_ptr(), ws[1].data_ptr()
+            p.c(lib.qfx_attn_bwd_fused, C.byref(a))
+            return "1pass"
+    p.c(lib.qfx_attn_bwd_dq, C.byref(a))
+    p.c(lib.qfx_attn_bwd_dkv, C.byref(a))
+    return "2pass"
 
 
 def _emit_or_defer(prog, a, fn, defer):

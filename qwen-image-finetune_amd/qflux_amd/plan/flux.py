@@ -6,16 +6,14 @@ and backward mirrors it with ONE dX GEMM over K = 3D (dq|dk|dv) + 4D (d mlp) + L
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 
 from .. import _lib as L
-from .. import ops
 from ..cond_hip import CondHeadHip
-from .emit import _flush_batch, _gargs, _ln_fwd_args
+from .emit import _flush_batch, _gargs, _kext, _ln_fwd_args, emit_attn_backward
 from .prog import _Prog, _ceil, _ptr
-from .qwen import F32, _QwenPlan
+from .qwen import F32, STREAMS, _QwenPlan
 
 lib = L.lib
 
@@ -45,14 +43,7 @@ class _FluxPlan(_QwenPlan):
         P = model._prepared
         A = self.A
         if multires:
-            # dynamic per-step buffers: per-sample RoPE, additive key mask, padded-row masks (set_multires fills them)
-            A["rope_b"] = buf(B, S, dh // 2, 2, dtype=F32)
-            A["kmask"] = buf(B, S, dtype=F32, zero=True)
-            A["rm_img"] = buf(B * S_i, dtype=F32)
-            A["rm_joint"] = buf(B * S, dtype=F32)
-            self.rope, self.rope_bs = A["rope_b"], S * (dh // 2) * 2
-            self.kmask = A["kmask"]
-            self.rmask = {"img": A["rm_img"], "txt": None, "joint": A["rm_joint"]}
+            self.rmask["joint"] = self._alloc_multires(rm_joint=B * S)      # row mask of the joint [text | image] rows (single blocks)
         else:
             self.rope = flux_joint_rope(ids, cfg.axes_dims_rope).to(model.device)
             assert self.rope.shape == (S, dh // 2, 2)
@@ -62,7 +53,7 @@ class _FluxPlan(_QwenPlan):
             A[k] = buf(B, 256)
         for k in ("t1", "t2", "g1", "g2", "p1", "p2", "temb"):
             A[k] = buf(1, B, D)
-        A["X"] = {s: [buf(rows[s], D) for _ in range(Ld + 1)] for s in ("img", "txt")}
+        A["X"] = {s: [buf(rows[s], D) for _ in range(Ld + 1)] for s in STREAMS}
         A["J"] = [buf(B * S, D) for _ in range(Ls + 1)]
         A["mods"] = buf(max(2 * Ld, 1), B, 6 * D); A["smods"] = buf(max(Ls, 1), B, 3 * D); A["mod_out"] = buf(1, B, 2 * D)
         A["xn_out"] = buf(B * S_i, D); A["out"] = buf(B * S_i, Cout)
@@ -117,8 +108,8 @@ class _FluxPlan(_QwenPlan):
             banks.append(([model.norm_out.linear], A["mod_out"], A["dmod_out"]))
             self.cond_head = CondHeadHip(model, B, D, chains=chains, temb=A["temb"], banks=banks, buf=buf)
             for bb in A["blk"]:
-                bb["y1"] = {s: buf(rows[s], D) for s in ("img", "txt")}
-                bb["y2"] = {s: buf(rows[s], D) for s in ("img", "txt")}
+                bb["y1"] = {s: buf(rows[s], D) for s in STREAMS}
+                bb["y2"] = {s: buf(rows[s], D) for s in STREAMS}
             for bb in A["sblk"]:
                 bb["y"] = buf(B * S, D)
         A["site"] = {"x_in": self._site_alloc(P["x_in"], rows["img"]), "c_in": self._site_alloc(P["c_in"], rows["txt"]),
@@ -183,92 +174,67 @@ class _FluxPlan(_QwenPlan):
         # ---- embedders; with no double blocks the embeddings go straight into the joint buffer
         if Ld == 0 and Ls == 0:
             raise NotImplementedError("FLUX model without any transformer block")
-        first_out = {s: ((A["X"][s][0], (0, 0)) if Ld else (A["J"][0], (S, off[s]))) for s in ("img", "txt")}
-        kw = self._site_fwd(p, P["x_in"], A["site"]["x_in"], A["in_img"], cfg.in_channels, rows["img"])
+        first_out = {s: ((A["X"][s][0], (0, 0)) if Ld else (A["J"][0], (S, off[s]))) for s in STREAMS}
+        site = A["site"]
+        kw = self._adapter_fwd(p, P["x_in"], A["in_img"], cfg.in_channels, rows["img"], site["x_in"].U, site["x_in"].ext)
         self._gemm(p, A1=A["in_img"], lda1=cfg.in_channels, B1=P["x_in"].W, K1=cfg.in_channels, M=rows["img"], N=D,
                    C_=first_out["img"][0], ldc=D, bias=P["x_in"].b, rpb=rpb["img"], c_map=first_out["img"][1], row_mask=self.rmask["img"], **kw)
-        kw = self._site_fwd(p, P["c_in"], A["site"]["c_in"], A["in_txt"], P["c_in"].K, rows["txt"])
+        kw = self._adapter_fwd(p, P["c_in"], A["in_txt"], P["c_in"].K, rows["txt"], site["c_in"].U, site["c_in"].ext)
         self._gemm(p, A1=A["in_txt"], lda1=P["c_in"].K, B1=P["c_in"].W, K1=P["c_in"].K, M=rows["txt"], N=D,
                    C_=first_out["txt"][0], ldc=D, bias=P["c_in"].b, rpb=rpb["txt"], c_map=first_out["txt"][1], **kw)
         self.attn_args, self.attn_hl_qkv = [], []
         for i in range(Ld):
             mods = {"img": A["mods"][2 * i], "txt": A["mods"][2 * i + 1]}
             to_joint = (i + 1 == Ld) and Ls > 0
-            x_out = {s: ((A["J"][0], (S, off[s])) if to_joint else (A["X"][s][i + 1], (0, 0))) for s in ("img", "txt")}
-            self._emit_double_fwd(p, P["blocks"][i], A["blk"][i], mods, {s: A["X"][s][i] for s in ("img", "txt")}, x_out,
+            x_out = {s: ((A["J"][0], (S, off[s])) if to_joint else (A["X"][s][i + 1], (0, 0))) for s in STREAMS}
+            self._emit_double_fwd(p, P["blocks"][i], A["blk"][i], mods, {s: A["X"][s][i] for s in STREAMS}, x_out,
                                   last=(i + 1 == Ld and Ls == 0), norm_flags=self.NORM_FLAGS)
         self.sattn_args = []
         for i in range(Ls):
             self._emit_single_fwd(p, P["singles"][i], A["sblk"][i], A["smods"][i], A["J"][i], A["J"][i + 1])
         # ---- norm_out + proj_out on the image rows of the joint buffer (per sample: contiguous row ranges)
-        mo = A["mod_out"][0]
         if Ls:
-            JL = A["J"][Ls]
+            mo, JL = A["mod_out"][0], A["J"][Ls]
             for b in range(B):
                 p.c(lib.qfx_ln_modulate_fwd, _ptr(JL[b * S + T:]), _ptr(mo[b:b + 1, D:2 * D]), _ptr(mo[b:b + 1, 0:D]), 2 * D,
                     _ptr(A["xn_out"][b * S_i:]), S_i, D, S_i, eps)
         else:
-            p.c(lib.qfx_ln_modulate_fwd, _ptr(A["X"]["img"][Ld]), _ptr(mo[:, D:2 * D]), _ptr(mo[:, 0:D]), 2 * D, _ptr(A["xn_out"]),
-                rows["img"], D, rpb["img"], eps)
-        po = P["proj_out"]
-        kw = self._site_fwd(p, po, A["site"]["proj_out"], A["xn_out"], D, rows["img"])
-        self._gemm(p, A1=A["xn_out"], lda1=D, B1=po.W, K1=D, M=rows["img"], N=po.N, C_=A["out"], ldc=po.N, bias=po.b,
-                   row_mask=self.rmask["img"], **kw)
+            self._norm_out_fwd(p, A["X"]["img"][Ld])
+        self._proj_out_fwd(p, P["proj_out"])
 
     def _emit_single_fwd(self, p, w, bb, mod, x, x_next):
         """FluxSingleTransformerBlock.forward (transformer_flux.py:407-436) on the joint buffer; mod [B,3D] = shift|scale|gate."""
         A, B, D, S, H, dh, T = self.A, self.B, self.D, self.S, self.H, self.dh, self.T
-        S_pad = self.S_pad
         eps = 1e-6
         M = B * S
         grp = w["qkv_lora"]
         xm = bb.get("xm", A["xm_j"])
         q2 = bb["qkv"].view(M, 3 * D)
         sqk2 = bb["sqk"].view(M, 2 * D)
+        e3 = A.get("ext3_j")
         fused = grp is not None and self._ln_down(p, [(_ln_fwd_args(x, mod[:, 0:D], mod[:, D:2 * D], 3 * D, xm, M, D, S, eps),
-                                                       dict(W_hi=grp["A_hi"], W_lo=grp["A_lo"], W_fr=grp.get("A_fr"), ldw=D, R=3 * grp["Rp"], Ut=bb["Uqkv"],
-                                                            ext=A["ext3_j"], ld_ext=A["ext3_j"].stride(0), group_R=grp["Rp"],
-                                                            group_stride=grp["Kext"]))])
+                                                       dict(self._qkv_down_kw(grp, bb["Uqkv"], e3), W_fr=grp.get("A_fr")))])
         if not fused:
             p.c(lib.qfx_ln_modulate_fwd, _ptr(x), _ptr(mod[:, 0:D]), _ptr(mod[:, D:2 * D]), 3 * D, _ptr(xm), M, D, S, eps)
-            if grp is not None:
-                self._down(p, X=xm, ldx=D, M=M, K=D, W_hi=grp["A_hi"], W_lo=grp["A_lo"], ldw=D, R=3 * grp["Rp"], Ut=bb["Uqkv"],
-                           ext=A["ext3_j"], ld_ext=A["ext3_j"].stride(0), group_R=grp["Rp"], group_stride=grp["Kext"])
         groups = []
-        for sec in range(3):
-            lw = w["qkv"][sec]
-            kw = {}
-            if lw.lora is not None:
-                kw = dict(A2=A["ext3_j"][:, sec * grp["Kext"]:], lda2=A["ext3_j"].stride(0), B2=lw.lora.We, ldb2=lw.lora.We.stride(0),
-                          K2=lw.lora.Kext)
+        for sec, (lw, kw) in enumerate(zip(w["qkv"], self._qkv_adapters_fwd(p, w["qkv"], grp, xm, M, bb.get("Uqkv"), e3, fused))):
             c_, ldc = (sqk2[:, sec * D:], 2 * D) if sec < 2 else (q2[:, 2 * D:], 3 * D)    # q,k: see the Qwen double block
             groups.append(_gargs(A1=xm, lda1=D, B1=lw.W, K1=D, M=M, N=D, C_=c_, ldc=ldc, bias=lw.b, **kw))
         self._gemm_group(p, groups)
         ml, wo = w["mlp"], w["out"]
         cat = bb.get("cat")                       # [M, 5D] = [attn | gelu(mlp)] when proj_out carries an adapter
         gact, ldg = (cat[:, D:], 5 * D) if cat is not None else (A["g_j"], 4 * D)
-        kw = self._site_fwd(p, ml, bb["site_mlp"], xm, D, M)
+        kw = self._adapter_fwd(p, ml, xm, D, M, bb["site_mlp"].U, bb["site_mlp"].ext)
         self._gemm(p, A1=xm, lda1=D, B1=ml.W, K1=D, M=M, N=4 * D, C_=bb["h"], ldc=4 * D, bias=ml.b, epi=L.EPI_GELU, C2=gact, ldc2=ldg, **kw)
         nq, nk = w["norms"]
         p.c(lib.qfx_qk_norm_rope_fwd, _ptr(bb["qkv"]), _ptr(bb["sqk"]), _ptr(self.rope), _ptr(nq), _ptr(nk), _ptr(nq), _ptr(nk),
             B, S, T, H, dh, eps, self.NORM_FLAGS | 2, self.rope_bs)
-        a = L.AttnArgs()
-        a.B, a.S, a.S_pad, a.H, a.dh, a.scale = B, S, S_pad, H, dh, 1.0 / math.sqrt(dh)
-        a.Q, a.K, a.V = _ptr(q2[:, 0:]), _ptr(q2[:, D:]), _ptr(q2[:, 2 * D:])
-        a.ldq = a.ldk = a.ldv = 3 * D
-        a.O, a.ldo, a.lse2 = _ptr(bb["ao"]), bb["ao"].stride(0), _ptr(bb["lse"])
-        a.key_mask = _ptr(self.kmask)
-        a.dsum = _ptr(A["dsum"])
-        a.dO, a.lddo = _ptr(A["dao"]), D
-        dq2 = A["dqkv"].view(M, 3 * D)
-        a.dQ, a.dK, a.dV = _ptr(dq2[:, 0:]), _ptr(dq2[:, D:]), _ptr(dq2[:, 2 * D:])
-        a.lddq = a.lddk = a.lddv = 3 * D
-        self._fuse_qk_bwd(a, bb["sqk"], (nq, nk, nq, nk), self.NORM_FLAGS, eps)
+        a = self._attn_args(bb["qkv"], bb["sqk"], bb["ao"], bb["ao"].stride(0), bb["lse"], A["dqkv"], (nq, nk, nq, nk), self.NORM_FLAGS, eps)
         self.sattn_args.append(a)
         p.c(lib.qfx_attn_fwd, C.byref(a))
         if cat is not None:
             # adapted proj_out: ONE contraction over the kept [attn | gelu(mlp)] buffer + the LoRA K-extension (base rounded first)
-            kw = self._site_fwd(p, wo, bb["site_out"], cat, 5 * D, M)
+            kw = self._adapter_fwd(p, wo, cat, 5 * D, M, bb["site_out"].U, bb["site_out"].ext)
             if "y" in bb:
                 kw.update(C2=bb["y"], ldc2=D)
             self._gemm(p, A1=cat, lda1=5 * D, B1=wo.W, ldb1=5 * D, K1=5 * D, M=M, N=D, C_=x_next, ldc=D, bias=wo.b, epi=L.EPI_GATE_RES,
@@ -276,8 +242,8 @@ class _FluxPlan(_QwenPlan):
             return
         # proj_out([attn | gelu(mlp)]) as a two-segment contraction, epilogue x + gate * y
         kw = dict(C2=bb["y"], ldc2=D) if "y" in bb else {}
-        self._gemm(p, A1=bb["ao"].view(M, D), lda1=D, B1=wo.W, ldb1=5 * D, K1=D, A2=A["g_j"], lda2=4 * D, B2=wo.W[:, D:], ldb2=5 * D,
-                   K2=4 * D, M=M, N=D, C_=x_next, ldc=D, bias=wo.b, epi=L.EPI_GATE_RES, aux=x, ldaux=D, gate=mod[:, 2 * D:3 * D],
+        self._gemm(p, A1=bb["ao"].view(M, D), lda1=D, B1=wo.W, ldb1=5 * D, K1=D, **_kext(A["g_j"], 4 * D, wo.W[:, D:], 4 * D),
+                   M=M, N=D, C_=x_next, ldc=D, bias=wo.b, epi=L.EPI_GATE_RES, aux=x, ldaux=D, gate=mod[:, 2 * D:3 * D],
                    gate_bs=3 * D, rpb=S, seg2_plain=1, row_mask=self.rmask["joint"], **kw)
 
     # ------------------------------------------------------------------ backward
@@ -288,9 +254,7 @@ class _FluxPlan(_QwenPlan):
         Ld, Ls = cfg.num_layers, cfg.num_single_layers
         rows, rpb, off = self.rows, self.rpb, self.off
         eps = 1e-6
-        po = P["proj_out"]
-        kw = self._site_bwd(p, po, A["site"]["proj_out"], A["dpred"], po.N, rows["img"], A["xn_out"], D)
-        self._gemm(p, A1=A["dpred"], lda1=po.N, B1=po.WT, K1=po.N, M=rows["img"], N=D, C_=A["dxn"], ldc=D, **kw)
+        self._proj_out_bwd(p, P["proj_out"], masked=False)
         mo = A["mod_out"][0]
         cur = dcur = 0   # (dcur: single block 0 writes the per-stream gradients into A["dX"][s][0] / A["dyg2"][s])
         if self.cond:
@@ -321,26 +285,22 @@ class _FluxPlan(_QwenPlan):
             if Ld == 0:
                 return
         else:
-            modL = A["mods"][2 * (Ld - 1)]
-            if self.cond:
-                self._mod_grad(p, dy=A["dxn"], x=A["X"]["img"][Ld], rows=rows["img"], rpb=rpb["img"], dshift=dmo[:, D:2 * D],
-                               dscale=dmo[:, 0:D], out_bs=2 * D, row_mask=self.rmask["img"])
-            p.c(lib.qfx_ln_modulate_bwd, _ptr(A["dxn"]), _ptr(A["X"]["img"][Ld]), _ptr(mo[:, 0:D]), 2 * D, None,
-                _ptr(modL[:, 5 * D:6 * D]), 6 * D, _ptr(A["dX"]["img"][dcur]), _ptr(A["dyg2"]["img"]), rows["img"], D, rpb["img"], eps, None)
+            self._norm_out_bwd(p, A["X"]["img"][Ld], A["mods"][2 * (Ld - 1)][:, 5 * D:6 * D], A["dX"]["img"][dcur])
         for i in range(Ld - 1, -1, -1):
             nxt = dcur ^ 1
             mods = {"img": A["mods"][2 * i], "txt": A["mods"][2 * i + 1]}
             gate_prev = None if i == 0 else {"img": A["mods"][2 * (i - 1)][:, 5 * D:6 * D], "txt": A["mods"][2 * (i - 1) + 1][:, 5 * D:6 * D]}
-            self._emit_double_bwd(p, P["blocks"][i], A["blk"][i], self.attn_args[i], self.attn_hl_qkv[i], mods, {s: A["X"][s][i] for s in ("img", "txt")},
-                                  dx2={s: A["dX"][s][dcur] for s in ("img", "txt")}, out_dx={s: A["dX"][s][nxt] for s in ("img", "txt")},
+            self._emit_double_bwd(p, P["blocks"][i], A["blk"][i], self.attn_args[i], self.attn_hl_qkv[i], mods, {s: A["X"][s][i] for s in STREAMS},
+                                  dx2={s: A["dX"][s][dcur] for s in STREAMS}, out_dx={s: A["dX"][s][nxt] for s in STREAMS},
                                   gate_prev=gate_prev, last=(i + 1 == Ld and Ls == 0), first=(i == 0 and not self.full_bwd),
                                   norm_flags=self.NORM_FLAGS,
                                   dmods=({"img": A["dmods"][2 * i], "txt": A["dmods"][2 * i + 1]} if self.cond else None))
             p.mark(f"transformer_blocks.{i}.")
             dcur = nxt
         if self.in_grad:   # the embedders' adapters: d(block-0 input) = A["dX"][s][dcur]; their own inputs carry no gradient
-            self._site_bwd(p, P["x_in"], A["site"]["x_in"], A["dX"]["img"][dcur], D, rows["img"], A["in_img"], cfg.in_channels)
-            self._site_bwd(p, P["c_in"], A["site"]["c_in"], A["dX"]["txt"][dcur], D, rows["txt"], A["in_txt"], P["c_in"].K)
+            site = A["site"]
+            for key, s, x, ldx in (("x_in", "img", A["in_img"], cfg.in_channels), ("c_in", "txt", A["in_txt"], P["c_in"].K)):
+                self._adapter_bwd(p, P[key], A["dX"][s][dcur], D, rows[s], x, ldx, site[key].U, site[key].V, site[key].extb)
         if self.cond:
             self.cond_head.emit_backward(p)
 
@@ -363,62 +323,37 @@ class _FluxPlan(_QwenPlan):
         # they were 8 x 38 latency-bound launches on the main stream (the FLUX programs keep their gradients there)
         gl = []
         if wo.lora is not None:
-            kwo = self._site_bwd(p, wo, bb["site_out"], A["dyg_j"], D, M, bb["cat"], 5 * D, defer=gl)
+            sb = bb["site_out"]
+            kwo = self._adapter_bwd(p, wo, A["dyg_j"], D, M, bb["cat"], 5 * D, sb.U, sb.V, sb.extb, dB=gl, dA=gl)
             kwa = dict(kwo, B2=wo.lora.WeT[:D])
             kwm = dict(kwo, B2=wo.lora.WeT[D:])
         self._gemm(p, A1=A["dyg_j"], lda1=D, B1=wo.WT, K1=D, M=M, N=D, C_=dao2, ldc=D, **kwa)
         self._gemm(p, A1=A["dyg_j"], lda1=D, B1=wo.WT[D:], K1=D, M=M, N=4 * D, C_=A["A2"], ldc=ldA2, epi=L.EPI_DGELU, aux=bb["h"],
                    ldaux=4 * D, **kwm)
-        ops.emit_attn_backward(p, a, A)      # two-pass pair, or the one-pass kernel (QFX_ATTN_BWD)
+        emit_attn_backward(p, a, A, self.lv.attn_bwd)      # two-pass pair, or the one-pass kernel (QFX_ATTN_BWD)
         if not a.qk_saved:
             nq, nk = w["norms"]
             p.c(lib.qfx_qk_norm_rope_bwd, _ptr(A["dqkv"]), _ptr(bb["sqk"]), _ptr(self.rope), _ptr(nq), _ptr(nk), _ptr(nq), _ptr(nk),
                 B, S, T, H, dh, eps, self.NORM_FLAGS, self.rope_bs)
         K2 = 4 * D
         if grp is not None:
-            Rp, Kext = grp["Rp"], grp["Kext"]
-            Vth, Vtl = A["Vt_j"]
-            Uth, Utl = bb["Uqkv"]
             dl = []     # the q / k / v down projections of dqkv: one launch
-            for sec in range(3):
-                lo = w["qkv"][sec].lora
-                if lo is None:
-                    continue
-                sl = slice(sec * Rp, (sec + 1) * Rp)
-                self._down(p, X=dq2[:, sec * D:], ldx=3 * D, M=M, K=D, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=Rp,
-                           Ut=(Vth[sl], Vtl[sl]), ext=A["A2"][:, 4 * D + sec * Kext:], ld_ext=ldA2, defer=dl)
-                self._grad(p, Vt=(Uth[sl], Utl[sl]), R=Rp, r_valid=lo.r, X=dq2[:, sec * D:], ldx=3 * D, M=M, K=D, G=lo.gB, g_sr=1,
-                           g_sc=lo.r, out_scale=lo.scale, defer=gl)
+            self._qkv_adapters_bwd(p, w["qkv"], grp, dq2, M, bb["xm"], bb["Uqkv"], A["Vt_j"], A["A2"][:, 4 * D:], down=dl, grads=gl)
             _flush_batch(p, dl, L.LoraDownArgs, lib.qfx_lora_down_batch)
-            los = [w["qkv"][sec].lora for sec in range(3)]
-            if all(l is not None for l in los):
-                self._grad(p, Vt=(Vth[:3 * Rp], Vtl[:3 * Rp]), R=3 * Rp, r_valid=los[0].r, group_R=Rp, X=bb["xm"], ldx=D, M=M, K=D,
-                           G=[l.gA for l in los], g_sr=D, g_sc=1, defer=gl)
-            else:
-                for sec, lo in enumerate(los):
-                    if lo is not None:
-                        sl = slice(sec * Rp, (sec + 1) * Rp)
-                        self._grad(p, Vt=(Vth[sl], Vtl[sl]), R=Rp, r_valid=lo.r, X=bb["xm"], ldx=D, M=M, K=D, G=lo.gA, g_sr=D, g_sc=1,
-                                   defer=gl)
-            K2 = 4 * D + 3 * Kext
+            K2 = 4 * D + 3 * grp["Kext"]
         if ml.lora is not None:
             # proj_mlp's adapter: v = d(mlp pre-act) (sB)^T goes into the last K-extension columns of A2; dB / dA as for any site
-            lo = ml.lora
             sb = bb["site_mlp"]
-            self._down(p, X=A["A2"], ldx=ldA2, M=M, K=4 * D, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=lo.Rp, Ut=sb["V"],
-                       ext=A["A2"][:, K2:], ld_ext=ldA2)
-            self._grad(p, Vt=sb["U"], R=lo.Rp, r_valid=lo.r, X=A["A2"], ldx=ldA2, M=M, K=4 * D, G=lo.gB, g_sr=1, g_sc=lo.r, out_scale=lo.scale,
-                       defer=gl)
-            self._grad(p, Vt=sb["V"], R=lo.Rp, r_valid=lo.r, X=bb["xm"], ldx=D, M=M, K=D, G=lo.gA, g_sr=D, g_sc=1, defer=gl)
-            K2 += lo.Kext
+            self._adapter_bwd(p, ml, A["A2"], ldA2, M, bb["xm"], D, sb.U, sb.V, A["A2"][:, K2:], dB=gl, dA=gl)
+            K2 += ml.lora.Kext
         # d(norm_x) = [dq|dk|dv] Wqkv + [d mlp | LoRA v] [W_mlp ; A]
         if self.model._quant == "mxfp8-fb" and D % 128 == 0 and D >= 1024:
             # low-precision trunk: the four frozen contractions as one MX-FP8 GEMM over K = 3D + 4D, adapters as its bf16 K-extension
             self.fp8._gemm_mxfp8_cat(p, [(dq2, 3 * D, 3 * D, w["qkvT"]), (A["A2"], ldA2, 4 * D, w["B2"])], M=M, N=D, C_=A["dxm_j"], ldc=D,
-                                 ext=(A["A2"][:, 4 * D:], ldA2, w["B2"][:, 4 * D:], w["B2"].stride(0), K2 - 4 * D))
+                                     ext=_kext(A["A2"][:, 4 * D:], ldA2, w["B2"][:, 4 * D:], K2 - 4 * D))
         else:
-            self._gemm(p, A1=dq2, lda1=3 * D, B1=w["qkvT"], K1=3 * D, A2=A["A2"], lda2=ldA2, B2=w["B2"], ldb2=w["B2"].stride(0), K2=K2,
-                       M=M, N=D, C_=A["dxm_j"], ldc=D, seg2_plain=1)
+            self._gemm(p, A1=dq2, lda1=3 * D, B1=w["qkvT"], K1=3 * D, **_kext(A["A2"], ldA2, w["B2"], K2), M=M, N=D, C_=A["dxm_j"],
+                       ldc=D, seg2_plain=1)
         if self.cond:   # d(shift, scale, gate) of the single block's AdaLayerNormZeroSingle
             dm = A["dsmods"][i]
             self._mod_grad(p, dy=A["dxm_j"], x=x, rows=M, rpb=S, dshift=dm[:, 0:D], dscale=dm[:, D:2 * D], dgate=dm[:, 2 * D:3 * D],

@@ -124,7 +124,7 @@ class _Fp8Trunk:
                 prog.c(lib.qfx_gemm_mxfp8, C.byref(f))
 
     def _gemm_mxfp8_cat(self, prog, parts, *, M, N, C_, ldc, ext=None):
-        """C = sum_i X_i W_i^T (+ the bf16 LoRA K-extension `ext` = (A2, lda2, B2, ldb2, K2)) as ONE MX-FP8 contraction over the
+        """C = sum_i X_i W_i^T (+ the bf16 LoRA K-extension `ext`: the keywords emit._kext returns) as ONE MX-FP8 contraction over the
         concatenated K of `parts` = [(X_i [M, K_i] bf16, row stride, K_i, W_i^T as [N, >= K_i] bf16)]: the operands are quantised
         side by side into one byte buffer / one tile-major scale array (K_i % 128 == 0: MX blocks and scale tiles never straddle a
         seam), the weights once (cached on the model).  Used for dX contractions that sum several frozen linears ("mxfp8-fb")."""
@@ -145,10 +145,7 @@ class _Fp8Trunk:
             prog.keep.append(qa)
             prog.c(lib.qfx_quant_mxfp8, C.byref(qa))
             col += K
-        kw = {}
-        if ext is not None and ext[4] > 0:
-            kw = dict(A2=ext[0], lda2=ext[1], B2=ext[2], ldb2=ext[3], K2=ext[4])
-        g = _gargs(A1=xq, lda1=Kt, B1=wq, K1=Kt, M=M, N=N, C_=C_, ldc=ldc, **kw).args
+        g = _gargs(A1=xq, lda1=Kt, B1=wq, K1=Kt, M=M, N=N, C_=C_, ldc=ldc, **(ext or {})).args
         f = L.GemmFp8Args()
         C.memmove(C.byref(f.g), C.byref(g), C.sizeof(L.GemmArgs))
         f.sa, f.ldsa, f.sb, f.ldsb = _ptr(xs), 0, _ptr(ws), 0

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from collections import namedtuple
 
 import torch
 
@@ -13,13 +14,19 @@ from .. import levers, ops
 from ..cond_hip import CondHeadHip
 from ..rope import normalize_img_shapes, qwen_joint_rope
 from .emit import (_down_args, _emit_or_defer, _flush_batch, _flush_head_reduce, _flush_ln, _flush_mod_grad, _gargs, _grad_args,
-                   _head_reduce_args, _ln_bwd_args, _ln_fwd_args, _mod_grad_args)
+                   _head_reduce_args, _kext, _ln_bwd_args, _ln_fwd_args, _mod_grad_args, emit_attn_backward)
 from .fp8 import _Fp8Trunk
 from .prog import _Prog, _ceil, _ptr
 
 lib = L.lib
 BF = torch.bfloat16
 F32 = torch.float32
+STREAMS = ("img", "txt")
+_NONE = dict.fromkeys(STREAMS)      # stands in for the per-stream rank-r scratch of a plan without adapters
+
+# Private rank-r buffers of one stand-alone adapted linear: K-extension images of the forward (ext) and backward (extb) GEMM,
+# transposed hi/lo splits of u = x A^T (kept for dB) and v = dy (sB)^T (for dA).  All None for a linear without an adapter.
+_Site = namedtuple("_Site", "ext extb U V", defaults=(None,) * 4)
 
 
 class _QwenPlan:
@@ -41,16 +48,7 @@ class _QwenPlan:
         self.multires = multires
         self.rm_txt0 = None
         if multires:
-            # per-batch contents, filled by set_multires(): per-sample RoPE (identity on unrotated rows), additive key mask,
-            # row masks of the padded image tokens (every block) and of the padded text tokens (once, after txt_in)
-            A["rope_b"] = buf(B, S, self.dh // 2, 2, dtype=F32)
-            A["kmask"] = buf(B, S, dtype=F32, zero=True)
-            A["rm_img"] = buf(B * S_i, dtype=F32)
-            A["rm_txt0"] = buf(B * T, dtype=F32)
-            self.rope, self.rope_bs = A["rope_b"], S * (self.dh // 2) * 2
-            self.kmask = A["kmask"]
-            self.rmask = {"img": A["rm_img"], "txt": None, "joint": None}
-            self.rm_txt0 = A["rm_txt0"]
+            self.rm_txt0 = self._alloc_multires(rm_txt0=B * T)      # row mask of the padded text tokens (applied once, after txt_in)
         else:
             self.rope = qwen_joint_rope(shapes, T, cfg.axes_dims_rope).to(model.device)
             assert self.rope.shape == (S, self.dh // 2, 2)
@@ -210,6 +208,20 @@ class _QwenPlan:
         self.rmask = {"img": None, "txt": None, "joint": None}   # fp32 row masks of padded tokens (multi-resolution)
         self.kmask = None         # additive fp32 key mask [B,S] (multi-resolution)
 
+    def _alloc_multires(self, **extra):
+        """Per-batch contents of a multi-resolution plan, filled by set_multires(): per-sample RoPE (identity on unrotated rows),
+        additive key mask, row mask of the padded image tokens (every block) and one further fp32 row mask `name=rows`, returned."""
+        A, buf, B, S = self.A, self.buf, self.B, self.S
+        A["rope_b"] = buf(B, S, self.dh // 2, 2, dtype=F32)
+        A["kmask"] = buf(B, S, dtype=F32, zero=True)
+        A["rm_img"] = buf(B * self.S_i, dtype=F32)
+        self.rope, self.rope_bs = A["rope_b"], S * (self.dh // 2) * 2
+        self.kmask = A["kmask"]
+        self.rmask["img"] = A["rm_img"]
+        (name, n), = extra.items()
+        A[name] = buf(n, dtype=F32)
+        return A[name]
+
     def _alloc_double_block(self, w):
         """Per-block saved activations of a double-stream block."""
         buf, rows, B, S, D, H, S_pad = self.buf, self.rows, self.B, self.S, self.D, self.H, self.S_pad
@@ -327,39 +339,105 @@ class _QwenPlan:
         """defer: list collecting the problem for ONE batched launch (_flush_mod_grad) -- the image and text stream of a block."""
         _emit_or_defer(prog, _mod_grad_args(self.D, **kw), lib.qfx_mod_grad, defer)
 
-    # ------------------------------------------------------------------ stand-alone adapted linears (embedders, output projection ...)
+    # ------------------------------------------------------------------ adapted linears
     def _site_alloc(self, lw, M):
-        """Private rank-r buffers of one adapted linear with M input rows: K-extension images of the forward (ext) and backward
-        (extb) GEMM, transposed hi/lo splits of u = x A^T (kept for dB) and v = dy (sB)^T (for dA)."""
+        """The private rank-r buffers (_Site) of one stand-alone adapted linear with M input rows: embedders, output projection ..."""
         if lw.lora is None:
-            return None
+            return _Site()
         lo, buf, mp = lw.lora, self.buf, _ceil(M, 128)
-        return dict(ext=buf(M, lo.Kext, zero=True), extb=buf(M, lo.Kext, zero=True),
-                    U=(buf(lo.Rp, mp, zero=True), buf(lo.Rp, mp, zero=True)), V=(buf(lo.Rp, mp, zero=True), buf(lo.Rp, mp, zero=True)))
+        return _Site(ext=buf(M, lo.Kext, zero=True), extb=buf(M, lo.Kext, zero=True),
+                     U=(buf(lo.Rp, mp, zero=True), buf(lo.Rp, mp, zero=True)), V=(buf(lo.Rp, mp, zero=True), buf(lo.Rp, mp, zero=True)))
 
-    def _site_fwd(self, p, lw, sb, X, ldx, M):
-        """u = x A^T (fp32-accurate), returns the K-extension arguments of the site's GEMM."""
-        if lw.lora is None:
-            return {}
+    def _adapter_fwd(self, p, lw, X, ldx, M, U, ext, *, defer=None, rmap=(None, (0, 0)), xq=None):
+        """Forward of the adapter of linear `lw` (none: nothing, {}): u = x A^T (fp32-accurate) into the hi/lo pair U (kept for dB)
+        and the K-extension image `ext`; returns the K-extension keywords of the linear's GEMM.  defer: list that collects the down
+        projection for a batched launch by the caller; rmap = (rows per sample, (joint rows per sample, offset)) when X is a stream's
+        rows of a joint buffer; xq: see _down_args."""
         lo = lw.lora
-        self._down(p, X=X, ldx=ldx, M=M, K=lo.A_hi.shape[1], W_hi=lo.A_hi, W_lo=lo.A_lo, ldw=lo.A_hi.stride(0), R=lo.Rp, Ut=sb["U"],
-                   ext=sb["ext"], ld_ext=sb["ext"].stride(0))
-        return dict(A2=sb["ext"], lda2=sb["ext"].stride(0), B2=lo.We, ldb2=lo.We.stride(0), K2=lo.Kext)
+        if lo is None:
+            return {}
+        self._down(p, X=X, ldx=ldx, M=M, K=lo.A_hi.shape[1], W_hi=lo.A_hi, W_lo=lo.A_lo, ldw=lo.A_hi.stride(0), R=lo.Rp, Ut=U,
+                   ext=ext, ld_ext=ext.stride(0), rpb=rmap[0], x_map=rmap[1], xq=xq, defer=defer)
+        return _kext(ext, ext.stride(0), lo.We, lo.Kext)
 
-    def _site_bwd(self, p, lw, sb, dY, ldy, M, Xin, ldxin, defer=None):
-        """v = dy (sB)^T, dB += dy^T u, dA += v^T x; returns the K-extension arguments of the site's dX GEMM.  defer: list that
-        collects the two weight-gradient problems for a batched launch by the caller (who keeps dY / Xin / the site buffers intact
-        until it flushes)."""
-        if lw.lora is None:
-            return {}
+    def _adapter_bwd(self, p, lw, dY, ldy, M, Xin, ldxin, U, V, ext, *, down=None, dB=None, dA=None, rmap=(None, (0, 0))):
+        """Backward of the adapter of linear `lw` (none: nothing, {}): v = dy (sB)^T into the first Rp rows of the hi/lo pair V and
+        the K-extension image `ext`, dB += dy^T u, dA += v^T x; returns the K-extension keywords of the linear's dX GEMM.  down / dB /
+        dA: lists that collect the down projection and the two weight-gradient problems for batched launches by the caller (who keeps
+        dY, Xin, U and V intact until it flushes).  rmap: as in _adapter_fwd, for the adapter's input Xin."""
         lo = lw.lora
-        self._down(p, X=dY, ldx=ldy, M=M, K=lw.N, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=lo.Rp, Ut=sb["V"],
-                   ext=sb["extb"], ld_ext=sb["extb"].stride(0))
-        self._grad(p, Vt=sb["U"], R=lo.Rp, r_valid=lo.r, X=dY, ldx=ldy, M=M, K=lw.N, G=lo.gB, g_sr=1, g_sc=lo.r, out_scale=lo.scale,
-                   defer=defer)
-        self._grad(p, Vt=sb["V"], R=lo.Rp, r_valid=lo.r, X=Xin, ldx=ldxin, M=M, K=lo.A_hi.shape[1], G=lo.gA, g_sr=lo.A_hi.shape[1], g_sc=1,
-                   defer=defer)
-        return dict(A2=sb["extb"], lda2=sb["extb"].stride(0), B2=lo.WeT, ldb2=lo.WeT.stride(0), K2=lo.Kext)
+        if lo is None:
+            return {}
+        K, Vt = lo.A_hi.shape[1], (V[0][:lo.Rp], V[1][:lo.Rp])
+        self._down(p, X=dY, ldx=ldy, M=M, K=lw.N, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=lo.Rp, Ut=Vt,
+                   ext=ext, ld_ext=ext.stride(0), defer=down)
+        self._grad(p, Vt=U, R=lo.Rp, r_valid=lo.r, X=dY, ldx=ldy, M=M, K=lw.N, G=lo.gB, g_sr=1, g_sc=lo.r, out_scale=lo.scale, defer=dB)
+        self._grad(p, Vt=Vt, R=lo.Rp, r_valid=lo.r, X=Xin, ldx=ldxin, M=M, K=K, G=lo.gA, g_sr=K, g_sc=1, rpb=rmap[0], x_map=rmap[1],
+                   defer=dA)
+        return _kext(ext, ext.stride(0), lo.WeT, lo.Kext)
+
+    def _qkv_adapters_fwd(self, p, qkv, grp, xm, M, U, ext3, fused):
+        """Forward of the grouped q/k/v adapters (grp; None: nothing) on the LayerNorm output xm [M, D]: one down projection for the
+        three (unless the LayerNorm launch carried it: fused); returns the K-extension keywords of the three projections."""
+        if grp is None:
+            return [{}, {}, {}]
+        if not fused:
+            self._down(p, X=xm, ldx=self.D, M=M, K=self.D, **self._qkv_down_kw(grp, U, ext3))
+        return [{} if lw.lora is None else _kext(ext3[:, sec * grp["Kext"]:], ext3.stride(0), lw.lora.We, lw.lora.Kext)
+                for sec, lw in enumerate(qkv)]
+
+    def _qkv_down_kw(self, grp, U, ext3):
+        """Weight and output keywords of the q/k/v group's down projection (qfx_lora_down; with W_fr: qfx_ln_down_fwd)."""
+        return dict(W_hi=grp["A_hi"], W_lo=grp["A_lo"], ldw=self.D, R=3 * grp["Rp"], Ut=U, ext=ext3, ld_ext=ext3.stride(0),
+                    group_R=grp["Rp"], group_stride=grp["Kext"])
+
+    def _qkv_adapters_bwd(self, p, qkv, grp, dq2, M, xm, U, V, ext, *, down, grads, rmap=(None, (0, 0)), pq=None, reduced=False):
+        """Backward of the grouped q/k/v adapters on dq2 [*, 3D] = d(q | k | v): per adapted section v = d(section) (sB)^T into its
+        rows of the hi/lo pair V and its columns of `ext` (collected in `down`; not when the attention epilogues and a head reduce
+        have produced them: reduced) and dB; then dA over xm [M, D], the group's input: one pass for the three when all are adapted,
+        else one per section.  The weight-gradient problems join `grads`.  rmap: as in _adapter_fwd, for dq2; pq: dq2's MX-FP8
+        image (bytes, scales) that the down projections write on their way.  Returns the K-extension keywords of the group's dX GEMM."""
+        D, Rp, Kext = self.D, grp["Rp"], grp["Kext"]
+        (Vth, Vtl), (Uth, Utl) = V, U
+        los = [lw.lora for lw in qkv]
+        for sec, lo in enumerate(los):
+            if lo is None:
+                continue
+            sl = slice(sec * Rp, (sec + 1) * Rp)
+            if not reduced:
+                self._down(p, X=dq2[:, sec * D:], ldx=3 * D, M=M, K=D, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=Rp,
+                           Ut=(Vth[sl], Vtl[sl]), ext=ext[:, sec * Kext:], ld_ext=ext.stride(0), rpb=rmap[0], x_map=rmap[1], defer=down,
+                           xq=None if pq is None else (_ptr(pq[0]) + sec * D, _ptr(pq[1]), 3 * D, M, sec * D // 32))
+            self._grad(p, Vt=(Uth[sl], Utl[sl]), R=Rp, r_valid=lo.r, X=dq2[:, sec * D:], ldx=3 * D, M=M, K=D, G=lo.gB, g_sr=1,
+                       g_sc=lo.r, rpb=rmap[0], x_map=rmap[1], out_scale=lo.scale, defer=grads)
+        if all(lo is not None for lo in los):   # one pass over xm for dA of q, k and v
+            self._grad(p, Vt=(Vth[:3 * Rp], Vtl[:3 * Rp]), R=3 * Rp, r_valid=los[0].r, group_R=Rp, X=xm, ldx=D, M=M, K=D,
+                       G=[lo.gA for lo in los], g_sr=D, g_sc=1, defer=grads)
+        else:
+            for sec, lo in enumerate(los):
+                if lo is not None:
+                    sl = slice(sec * Rp, (sec + 1) * Rp)
+                    self._grad(p, Vt=(Vth[sl], Vtl[sl]), R=Rp, r_valid=lo.r, X=xm, ldx=D, M=M, K=D, G=lo.gA, g_sr=D, g_sc=1, defer=grads)
+        return _kext(ext, ext.stride(0), grp["WeT"], 3 * Kext)
+
+    def _attn_args(self, qkv, sqk, ao, ldo, lse, dqkv, norms, norm_flags, eps):
+        """The qfx_attn_args of one block, forward and backward fields (the backward program reuses the struct): q/k/v and their
+        gradients as column sections of the joint [B*S, 3D] buffers qkv / dqkv, output ao (row stride ldo), saved pre-norm q|k sqk."""
+        B, S, D = self.B, self.S, self.D
+        a = L.AttnArgs()
+        a.B, a.S, a.S_pad, a.H, a.dh, a.scale = B, S, self.S_pad, self.H, self.dh, 1.0 / math.sqrt(self.dh)
+        q2 = qkv.view(B * S, 3 * D)
+        a.Q, a.K, a.V = _ptr(q2[:, 0:]), _ptr(q2[:, D:]), _ptr(q2[:, 2 * D:])
+        a.ldq = a.ldk = a.ldv = 3 * D
+        a.O, a.ldo, a.lse2 = _ptr(ao), ldo, _ptr(lse)   # no transposed copies: the kernels use LDS transpose reads
+        a.key_mask = _ptr(self.kmask)
+        a.dsum = _ptr(self.A["dsum"])
+        a.dO, a.lddo = _ptr(self.A["dao"]), D
+        dq2 = dqkv.view(B * S, 3 * D)
+        a.dQ, a.dK, a.dV = _ptr(dq2[:, 0:]), _ptr(dq2[:, D:]), _ptr(dq2[:, 2 * D:])
+        a.lddq = a.lddk = a.lddv = 3 * D
+        self._fuse_qk_bwd(a, sqk, norms, norm_flags, eps)
+        return a
 
     # ------------------------------------------------------------------ forward program
     def _build_forward(self, P):
@@ -369,7 +447,7 @@ class _QwenPlan:
         cfg = model.config
         Lyr = cfg.num_layers
         Jd = cfg.joint_attention_dim
-        rows, rpb = self.rows, self.rpb
+        rows = self.rows
         eps = 1e-6
         # head: timestep embedding -> temb ; img_in ; txt_norm + txt_in ; all modulation vectors in one GEMV launch
         p.c(lib.qfx_timestep_embed, _ptr(A["t"]), B, 256, 1000.0, 1.0, _ptr(A["tproj"]))
@@ -394,11 +472,12 @@ class _QwenPlan:
             p.c(lib.qfx_mod_gemv, _ptr(A["t1"]), B, D, _ptr(P["t2_Wp"]), _ptr(P["t2_bp"]), 1, D, 1, _ptr(A["temb"]))
             p.c(lib.qfx_mod_gemv, _ptr(A["temb"]), B, D, _ptr(P["mod_W"]), _ptr(P["mod_b"]), 2 * Lyr, 6 * D, 1, _ptr(A["mods"]))
             p.c(lib.qfx_mod_gemv, _ptr(A["temb"]), B, D, _ptr(P["norm_out_Wp"]), _ptr(P["norm_out_bp"]), 1, 2 * D, 1, _ptr(A["mod_out"]))
-        kw = self._site_fwd(p, P["img_in"], A["site"]["img_in"], A["in_img"], cfg.in_channels, rows["img"])
+        site = A["site"]
+        kw = self._adapter_fwd(p, P["img_in"], A["in_img"], cfg.in_channels, rows["img"], site["img_in"].U, site["img_in"].ext)
         self._gemm(p, A1=A["in_img"], lda1=cfg.in_channels, B1=P["img_in"].W, K1=cfg.in_channels, M=rows["img"], N=D,
                    C_=A["X"]["img"][0], ldc=D, bias=P["img_in"].b, row_mask=self.rmask["img"], **kw)
         p.c(lib.qfx_rmsnorm_fwd, _ptr(A["in_txt"]), _ptr(model.txt_norm.weight.data), _ptr(A["txt_n"]), rows["txt"], Jd, eps)
-        kw = self._site_fwd(p, P["txt_in"], A["site"]["txt_in"], A["txt_n"], Jd, rows["txt"])
+        kw = self._adapter_fwd(p, P["txt_in"], A["txt_n"], Jd, rows["txt"], site["txt_in"].U, site["txt_in"].ext)
         self._gemm(p, A1=A["txt_n"], lda1=Jd, B1=P["txt_in"].W, K1=Jd, M=rows["txt"], N=D, C_=A["X"]["txt"][0], ldc=D,
                    bias=P["txt_in"].b, row_mask=self.rm_txt0, **kw)
         self.attn_args, self.attn_hl_qkv = [], []   # per block: qfx_attn_args, {stream: Rp} of the q/k/v projections fused in its backward
@@ -406,23 +485,51 @@ class _QwenPlan:
             mods = {"img": A["mods"][2 * i], "txt": A["mods"][2 * i + 1]}   # [B, 6D]: shift1 scale1 gate1 shift2 scale2 gate2
             self._emit_double_fwd(p, P["blocks"][i], A["blk"][i], mods, {s: A["X"][s][i] for s in ("img", "txt")},
                                   {s: (A["X"][s][i + 1], (0, 0)) for s in ("img", "txt")}, last=(i == Lyr - 1), norm_flags=0, par=i % 2)
+        self._norm_out_fwd(p, A["X"]["img"][Lyr])
+        self._proj_out_fwd(p, P["proj_out"])
+
+    def _norm_out_fwd(self, p, x):
+        """norm_out (AdaLayerNormContinuous) on the image stream x [B*S_i, D] -> A["xn_out"]."""
+        A, D = self.A, self.D
         mo = A["mod_out"][0]  # [B, 2D]: scale | shift  (AdaLayerNormContinuous chunk order)
-        p.c(lib.qfx_ln_modulate_fwd, _ptr(A["X"]["img"][Lyr]), _ptr(mo[:, D:2 * D]), _ptr(mo[:, 0:D]), 2 * D, _ptr(A["xn_out"]),
-            rows["img"], D, rpb["img"], eps)
-        po = P["proj_out"]
-        kw = self._site_fwd(p, po, A["site"]["proj_out"], A["xn_out"], D, rows["img"])
-        self._gemm(p, A1=A["xn_out"], lda1=D, B1=po.W, K1=D, M=rows["img"], N=po.N, C_=A["out"], ldc=po.N, bias=po.b,
+        p.c(lib.qfx_ln_modulate_fwd, _ptr(x), _ptr(mo[:, D:2 * D]), _ptr(mo[:, 0:D]), 2 * D, _ptr(A["xn_out"]),
+            self.rows["img"], D, self.rpb["img"], 1e-6)
+
+    def _proj_out_fwd(self, p, po):
+        """proj_out (+ its adapter): A["xn_out"] -> A["out"], padded image rows masked."""
+        A, D, M = self.A, self.D, self.rows["img"]
+        kw = self._adapter_fwd(p, po, A["xn_out"], D, M, A["site"]["proj_out"].U, A["site"]["proj_out"].ext)
+        self._gemm(p, A1=A["xn_out"], lda1=D, B1=po.W, K1=D, M=M, N=po.N, C_=A["out"], ldc=po.N, bias=po.b,
                    row_mask=self.rmask["img"], **kw)
+
+    def _proj_out_bwd(self, p, po, masked):
+        """proj_out dX (+ its adapter): A["dpred"] -> A["dxn"].  masked: the backward of the output masked_fill, no gradient enters
+        through padded rows (the Qwen program passes the row mask here, the FLUX program does not)."""
+        A, D, M = self.A, self.D, self.rows["img"]
+        sb = A["site"]["proj_out"]
+        kw = self._adapter_bwd(p, po, A["dpred"], po.N, M, A["xn_out"], D, sb.U, sb.V, sb.extb)
+        self._gemm(p, A1=A["dpred"], lda1=po.N, B1=po.WT, K1=po.N, M=M, N=D, C_=A["dxn"], ldc=D,
+                   row_mask=self.rmask["img"] if masked else None, **kw)
+
+    def _norm_out_bwd(self, p, x, gate, dx):
+        """norm_out backward on the image stream (+ d scale / d shift with a conditioning-head adapter): A["dxn"] -> dx = d(x) and
+        A["dyg2"]["img"] = gate * dx for the last double block, whose gate2 = gate [B, D] of a [B, 6D] bank."""
+        A, D, rows, rpb = self.A, self.D, self.rows["img"], self.rpb["img"]
+        mo = A["mod_out"][0]
+        if self.cond:
+            dmo = A["dmod_out"][0]       # [B, 2D] = d scale | d shift (AdaLayerNormContinuous chunk order)
+            self._mod_grad(p, dy=A["dxn"], x=x, rows=rows, rpb=rpb, dshift=dmo[:, D:2 * D], dscale=dmo[:, 0:D], out_bs=2 * D,
+                           row_mask=self.rmask["img"])
+        p.c(lib.qfx_ln_modulate_bwd, _ptr(A["dxn"]), _ptr(x), _ptr(mo[:, 0:D]), 2 * D, None, _ptr(gate), 6 * D, _ptr(dx),
+            _ptr(A["dyg2"]["img"]), rows, D, rpb, 1e-6, None)
 
     def _emit_double_fwd(self, p, w, bb, mods, x_in, x_out, last, norm_flags, par=0):
         """One double-stream block (reference: transformer_qwenimage.py:425-494; FLUX: transformer_flux.py:467-523).
         x_in[s]: [rows_s, D] block input; x_out[s] = (tensor, c_map): where the block output goes (possibly a joint buffer)."""
         A, B, D, S, H, dh, T = self.A, self.B, self.D, self.S, self.H, self.dh, self.T
-        S_pad = self.S_pad
         rows, rpb, off = self.rows, self.rpb, self.off
         eps = 1e-6
-        scale = 1.0 / math.sqrt(dh)
-        STREAMS = ("img", "txt")
+        e1, e3 = A.get("ext1", _NONE), A.get("ext3", _NONE)
         qkv = bb["qkv"]
         q2 = qkv.view(B * S, 3 * D)
         sqk2 = bb["sqk"].view(B * S, 2 * D)
@@ -431,57 +538,33 @@ class _QwenPlan:
         groups = []
         lnl = []
         ents = []
+        xm1 = {s: (bb["xm1." + s] if w[s + ".qkv_lora"] is not None else A["xm"][s]) for s in STREAMS}
         for s in STREAMS:
             mod = mods[s]
             grp = w[s + ".qkv_lora"]
-            xm1 = bb["xm1." + s] if grp is not None else A["xm"][s]
-            ln = _ln_fwd_args(x_in[s], mod[:, 0:D], mod[:, D:2 * D], 6 * D, xm1, rows[s], D, rpb[s], eps)
-            pq_ = self.fp8._preq_out(p, xm1, D, rows[s], D, s)       # MX-FP8 trunk: the q/k/v GEMMs take xm1 quantised by its producer
+            ln = _ln_fwd_args(x_in[s], mod[:, 0:D], mod[:, D:2 * D], 6 * D, xm1[s], rows[s], D, rpb[s], eps)
+            pq_ = self.fp8._preq_out(p, xm1[s], D, rows[s], D, s)    # MX-FP8 trunk: the q/k/v GEMMs take xm1 quantised by its producer
             if pq_ is not None:
                 ln.yq, ln.ys, ln.ldyq, ln.ys_rows = _ptr(pq_[0]), _ptr(pq_[1]), D, rows[s]
             lnl.append(ln)
-            ents.append((ln, None if grp is None else dict(W_hi=grp["A_hi"], W_lo=grp["A_lo"], W_fr=grp.get("A_fr"), ldw=D, R=3 * grp["Rp"],
-                                                           Ut=bb["Uqkv." + s], ext=A["ext3"][s], ld_ext=A["ext3"][s].stride(0),
-                                                           group_R=grp["Rp"], group_stride=grp["Kext"])))
+            ents.append((ln, None if grp is None else dict(self._qkv_down_kw(grp, bb["Uqkv." + s], e3[s]), W_fr=grp.get("A_fr"))))
         # LayerNorm+modulate and the q/k/v down projection of its output in ONE pass over the row block (qfx_ln_down_fwd)
         fused = self._ln_down(p, ents)
         if not fused:
             _flush_ln(p, lnl, L.LnFwdArgs, lib.qfx_ln_modulate_fwd_batch)
         for s in STREAMS:
-            grp = w[s + ".qkv_lora"]
-            xm1 = bb["xm1." + s] if grp is not None else A["xm"][s]
-            if grp is not None and not fused:
-                self._down(p, X=xm1, ldx=D, M=rows[s], K=D, W_hi=grp["A_hi"], W_lo=grp["A_lo"], ldw=D, R=3 * grp["Rp"],
-                           Ut=bb["Uqkv." + s], ext=A["ext3"][s], ld_ext=A["ext3"][s].stride(0),
-                           group_R=grp["Rp"], group_stride=grp["Kext"])
-            for sec in range(3):
-                lw = w[s + ".qkv"][sec]
-                kw = {}
-                if lw.lora is not None:
-                    kw = dict(A2=A["ext3"][s][:, sec * grp["Kext"]:], lda2=A["ext3"][s].stride(0), B2=lw.lora.We,
-                              ldb2=lw.lora.We.stride(0), K2=lw.lora.Kext)
+            kws = self._qkv_adapters_fwd(p, w[s + ".qkv"], w[s + ".qkv_lora"], xm1[s], rows[s], bb.get("Uqkv." + s), e3[s], fused)
+            for sec, (lw, kw) in enumerate(zip(w[s + ".qkv"], kws)):
                 # q and k go straight into the block's saved pre-norm copy (what the backward of the QK norm needs); the
                 # norm+RoPE pass reads them there and writes the joint buffer (out-of-place mode: no copy pass)
                 c_, ldc = (sqk2[:, sec * D:], 2 * D) if sec < 2 else (q2[:, 2 * D:], 3 * D)
-                groups.append(_gargs(A1=xm1, lda1=D, B1=lw.W, K1=D, M=rows[s], N=D, C_=c_, ldc=ldc,
+                groups.append(_gargs(A1=xm1[s], lda1=D, B1=lw.W, K1=D, M=rows[s], N=D, C_=c_, ldc=ldc,
                                      bias=lw.b, rpb=rpb[s], c_map=(S, off[s]), **kw))
         self._gemm_group(p, groups)
         nq_t, nk_t, nq_i, nk_i = w["norms"]
         p.c(lib.qfx_qk_norm_rope_fwd, _ptr(qkv), _ptr(bb["sqk"]), _ptr(self.rope), _ptr(nq_t), _ptr(nk_t), _ptr(nq_i), _ptr(nk_i),
             B, S, T, H, dh, eps, norm_flags | 2, self.rope_bs)
-        a = L.AttnArgs()
-        a.B, a.S, a.S_pad, a.H, a.dh, a.scale = B, S, S_pad, H, dh, scale
-        a.Q, a.K, a.V = _ptr(q2[:, 0:]), _ptr(q2[:, D:]), _ptr(q2[:, 2 * D:])
-        a.ldq = a.ldk = a.ldv = 3 * D
-        a.O, a.ldo, a.lse2 = _ptr(bb["ao"]), D, _ptr(bb["lse"])   # no transposed copies: the kernels use LDS transpose reads
-        a.key_mask = _ptr(self.kmask)
-        # backward fields (same struct reused by the backward program)
-        a.dsum = _ptr(A["dsum"])
-        a.dO, a.lddo = _ptr(A["dao"]), D
-        dq2 = self._sb("dqkv", par).view(B * S, 3 * D)
-        a.dQ, a.dK, a.dV = _ptr(dq2[:, 0:]), _ptr(dq2[:, D:]), _ptr(dq2[:, 2 * D:])
-        a.lddq = a.lddk = a.lddv = 3 * D
-        self._fuse_qk_bwd(a, bb["sqk"], (nq_t, nk_t, nq_i, nk_i), norm_flags, eps)
+        a = self._attn_args(qkv, bb["sqk"], bb["ao"], D, bb["lse"], self._sb("dqkv", par), w["norms"], norm_flags, eps)
         # the text stream of the last block never reaches the output (:661-663): dead compute, skipped
         live = [s for s in STREAMS if not (last and s == "txt")]
         hl_o, hl_qkv = self._head_lora_slots(a, w, live)
@@ -493,21 +576,17 @@ class _QwenPlan:
         dho = []
         for s in live:
             lw = w[s + ".o"]
-            kw = {}
-            if lw.lora is not None and s in hl_o:
+            lo = lw.lora
+            if lo is not None and s in hl_o:
                 # u = ao A_o^T left the attention epilogue as per-head partial sums: reduce + pack (what qfx_lora_down wrote)
-                dho.append(_head_reduce_args(A["hl_o"], hl_o[s], lw.lora.Rp, rows[s], rpb[s], S, off[s], A["ext1"][s], bb["Uo." + s],
-                                             lw.lora.Rp, 0))
-            elif lw.lora is not None:
+                dho.append(_head_reduce_args(A["hl_o"], hl_o[s], lo.Rp, rows[s], rpb[s], S, off[s], e1[s], bb["Uo." + s], lo.Rp, 0))
+                kw = _kext(e1[s], e1[s].stride(0), lo.We, lo.Kext)
+            else:
                 # MX-FP8 trunk: the down projection reads every attention-output row of this stream anyway and leaves its
                 # MX-FP8 image for the out-projection GEMM
-                pq_ = self.fp8._preq_out(p, ao2, D, rows[s], D, "ao." + s, a_map=(S, off[s]))
-                self._down(p, X=ao2, ldx=D, M=rows[s], K=D, W_hi=lw.lora.A_hi, W_lo=lw.lora.A_lo, ldw=D, R=lw.lora.Rp,
-                           Ut=bb["Uo." + s], ext=A["ext1"][s], ld_ext=A["ext1"][s].stride(0),
-                           rpb=rpb[s], x_map=(S, off[s]), defer=dfo,
-                           xq=None if pq_ is None else (_ptr(pq_[0]), _ptr(pq_[1]), D, rows[s], 0))
-            if lw.lora is not None:
-                kw = dict(A2=A["ext1"][s], lda2=A["ext1"][s].stride(0), B2=lw.lora.We, ldb2=lw.lora.We.stride(0), K2=lw.lora.Kext)
+                pq_ = None if lo is None else self.fp8._preq_out(p, ao2, D, rows[s], D, "ao." + s, a_map=(S, off[s]))
+                kw = self._adapter_fwd(p, lw, ao2, D, rows[s], bb.get("Uo." + s), e1[s], defer=dfo, rmap=(rpb[s], (S, off[s])),
+                                       xq=None if pq_ is None else (_ptr(pq_[0]), _ptr(pq_[1]), D, rows[s], 0))
             if "y1" in bb:
                 kw.update(C2=bb["y1"][s], ldc2=D)
             groups.append(_gargs(A1=ao2, lda1=D, B1=lw.W, K1=D, M=rows[s], N=D, C_=bb["x1"][s], ldc=D, bias=lw.b,
@@ -527,20 +606,10 @@ class _QwenPlan:
             if pq_ is not None:
                 ln.yq, ln.ys, ln.ldyq, ln.ys_rows = _ptr(pq_[0]), _ptr(pq_[1]), D, rows[s]
         _flush_ln(p, lnl, L.LnFwdArgs, lib.qfx_ln_modulate_fwd_batch)
-
-        def lora_ext(s, lw, X, ldx, ukey):
-            """Down-projection of a single adapted linear; returns the K-extension arguments of its GEMM."""
-            if lw.lora is None:
-                return {}
-            lo, e1 = lw.lora, A["ext1"][s]
-            self._down(p, X=X, ldx=ldx, M=rows[s], K=lw.K, W_hi=lo.A_hi, W_lo=lo.A_lo, ldw=lo.A_hi.stride(0), R=lo.Rp,
-                       Ut=bb[ukey + s], ext=e1, ld_ext=e1.stride(0), defer=dfw)
-            return dict(A2=e1, lda2=e1.stride(0), B2=lo.We, ldb2=lo.We.stride(0), K2=lo.Kext)
-
         dfw = []      # the image- and text-stream down projections of one site go out as ONE batched launch
         for s in live:
             f1 = w[s + ".fc1"]
-            kw = lora_ext(s, f1, xm2[s], D, "Uf1.")
+            kw = self._adapter_fwd(p, f1, xm2[s], D, rows[s], bb.get("Uf1." + s), e1[s], defer=dfw)
             groups.append(_gargs(A1=xm2[s], lda1=D, B1=f1.W, K1=D, M=rows[s], N=4 * D, C_=bb["h"][s], ldc=4 * D,
                                  bias=f1.b, epi=L.EPI_GELU, C2=gact[s], ldc2=4 * D,
                                  nxt=(gact[s], 4 * D, w[s + ".fc2"].lora is not None), **kw))   # gelu(h) feeds fc2 (and its adapter's dA, if any)
@@ -549,7 +618,7 @@ class _QwenPlan:
         groups = []
         for s in live:
             f2 = w[s + ".fc2"]
-            kw = lora_ext(s, f2, gact[s], 4 * D, "Uf2.")
+            kw = self._adapter_fwd(p, f2, gact[s], 4 * D, rows[s], bb.get("Uf2." + s), e1[s], defer=dfw)
             if "y2" in bb:
                 kw.update(C2=bb["y2"][s], ldc2=D)
             groups.append(_gargs(A1=gact[s], lda1=4 * D, B1=f2.W, K1=4 * D, M=rows[s], N=D, C_=x_out[s][0], ldc=D,
@@ -564,24 +633,14 @@ class _QwenPlan:
         p = self.bwd
         cfg = self.model.config
         Lyr = cfg.num_layers
-        rows, rpb = self.rows, self.rpb
-        eps = 1e-6
-        po = P["proj_out"]
+        rows, site = self.rows, A["site"]
         # tail: proj_out dX (+ its adapter), norm_out LN backward (+ gate2 of the last block folded in)
-        kw = self._site_bwd(p, po, A["site"]["proj_out"], A["dpred"], po.N, rows["img"], A["xn_out"], D)
-        self._gemm(p, A1=A["dpred"], lda1=po.N, B1=po.WT, K1=po.N, M=rows["img"], N=D, C_=A["dxn"], ldc=D,
-                   row_mask=self.rmask["img"], **kw)   # backward of the output masked_fill: no gradient enters through padded rows
-        mo = A["mod_out"][0]
-        modL = A["mods"][2 * (Lyr - 1)]
+        self._proj_out_bwd(p, P["proj_out"], masked=True)
         cur = 0
         if self.cond:
             p.py(A["dmods"].zero_)
             p.py(A["dmod_out"].zero_)
-            dmo = A["dmod_out"][0]       # [B, 2D] = d scale | d shift (AdaLayerNormContinuous chunk order)
-            self._mod_grad(p, dy=A["dxn"], x=A["X"]["img"][Lyr], rows=rows["img"], rpb=rpb["img"], dshift=dmo[:, D:2 * D],
-                           dscale=dmo[:, 0:D], out_bs=2 * D, row_mask=self.rmask["img"])
-        p.c(lib.qfx_ln_modulate_bwd, _ptr(A["dxn"]), _ptr(A["X"]["img"][Lyr]), _ptr(mo[:, 0:D]), 2 * D, None,
-            _ptr(modL[:, 5 * D:6 * D]), 6 * D, _ptr(A["dX"]["img"][cur]), _ptr(A["dyg2"]["img"]), rows["img"], D, rpb["img"], eps, None)
+        self._norm_out_bwd(p, A["X"]["img"][Lyr], A["mods"][2 * (Lyr - 1)][:, 5 * D:6 * D], A["dX"]["img"][cur])
         for i in range(Lyr - 1, -1, -1):
             nxt = cur ^ 1
             mods = {"img": A["mods"][2 * i], "txt": A["mods"][2 * i + 1]}
@@ -597,8 +656,8 @@ class _QwenPlan:
         self._side_join(p)
         # head: the embedders' adapters (their inputs carry no gradient: rank-r launches only); d(block-0 input) = A["dX"][s][cur]
         if self.in_grad:
-            self._site_bwd(p, P["img_in"], A["site"]["img_in"], A["dX"]["img"][cur], D, rows["img"], A["in_img"], cfg.in_channels)
-            self._site_bwd(p, P["txt_in"], A["site"]["txt_in"], A["dX"]["txt"][cur], D, rows["txt"], A["txt_n"], cfg.joint_attention_dim)
+            for key, s, x, ldx in (("img_in", "img", A["in_img"], cfg.in_channels), ("txt_in", "txt", A["txt_n"], cfg.joint_attention_dim)):
+                self._adapter_bwd(p, P[key], A["dX"][s][cur], D, rows[s], x, ldx, site[key].U, site[key].V, site[key].extb)
         if self.cond:
             self.cond_head.emit_backward(p)
 
@@ -609,14 +668,15 @@ class _QwenPlan:
         rows, rpb, off = self.rows, self.rpb, self.off
         eps = 1e-6
         dao2 = A["dao"].view(B * S, D)
-        dqkv, dyg1, VtO, VtQ = self._sb("dqkv", par), self._sb("dyg1", par), self._sb("VtO", par), self._sb("Vt", par)
+        dqkv, dyg1 = self._sb("dqkv", par), self._sb("dyg1", par)
+        VtO, VtQ = self._sb("VtO", par) or _NONE, self._sb("Vt", par) or _NONE
         ff_side = self.side_grads and self._ff_side
         dh_ = self._sb("dh", par) if ff_side else A["dh"]
-        vtf = {"VtF1": self._sb("VtF1", par) if ff_side else A.get("VtF1"), "VtF2": self._sb("VtF2", par) if ff_side else A.get("VtF2")}
+        VtF1, VtF2 = ((self._sb(name, par) if ff_side else A.get(name)) or _NONE for name in ("VtF1", "VtF2"))
+        e1, e3 = A.get("ext1", _NONE), A.get("ext3", _NONE)
         if ff_side:
             self._side_join(p, keep=1)      # the launch of block i+2 read this parity's dh: overwritten by this block's first GEMM
         dq2 = dqkv.view(B * S, 3 * D)
-        STREAMS = ("img", "txt")
         i = 0 if first else 1
         # LoRA weight gradients are leaves: every qfx_lora_grad of the block is deferred to ONE batched launch per rank at the
         # end of the block (their X operands -- dyg1, ao, dqkv, xm1, dh, the kept feed-forward inputs -- stay intact until the next block's backward
@@ -629,25 +689,12 @@ class _QwenPlan:
             p.py(A["dao"][:, :T].zero_)
         # ---- MLP backward: dh = (gate2*dx2) W2 * gelu'(h) ; dxm2 = dh W1   (both streams per launch)
         ge = []   # gradients whose X operand (dyg2) is overwritten before the end of the block: flushed right after the MLP
-
-        def lora_bwd(s, lw, dY, ldy, Xin, ldxin, ukey, vkey, early):
-            """dY -> v = dY B (K-extension of the dX GEMM) + the two deferred weight-gradient problems of an adapted linear."""
-            if lw.lora is None:
-                return {}
-            lo, e1 = lw.lora, A["ext1"][s]
-            Vt = (vtf[vkey][s][0][:lo.Rp], vtf[vkey][s][1][:lo.Rp])
-            self._down(p, X=dY, ldx=ldy, M=rows[s], K=lw.N, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=lo.Rp,
-                       Ut=Vt, ext=e1, ld_ext=e1.stride(0), defer=dbw)
-            self._grad(p, Vt=bb[ukey + s], R=lo.Rp, r_valid=lo.r, X=dY, ldx=ldy, M=rows[s], K=lw.N, G=lo.gB, g_sr=1, g_sc=lo.r,
-                       out_scale=lo.scale, defer=ge if early else gl)
-            self._grad(p, Vt=Vt, R=lo.Rp, r_valid=lo.r, X=Xin, ldx=ldxin, M=rows[s], K=lw.K, G=lo.gA, g_sr=lw.K, g_sc=1, defer=gl)
-            return dict(A2=e1, lda2=e1.stride(0), B2=lo.WeT, ldb2=lo.WeT.stride(0), K2=lo.Kext)
-
         groups = []
         dbw = []      # both streams' v = dY B of a site in ONE batched launch
         for s in live:
             f2 = w[s + ".fc2"]
-            kw = lora_bwd(s, f2, A["dyg2"][s], D, bb.get("g." + s), 4 * D, "Uf2.", "VtF2", early=True)
+            kw = self._adapter_bwd(p, f2, A["dyg2"][s], D, rows[s], bb.get("g." + s), 4 * D, bb.get("Uf2." + s), VtF2[s], e1[s],
+                                   down=dbw, dB=ge, dA=gl)
             groups.append(_gargs(A1=A["dyg2"][s], lda1=D, B1=f2.WT, K1=D, M=rows[s], N=4 * D, C_=dh_[s],
                                  ldc=4 * D, epi=L.EPI_DGELU, aux=bb["h"][s], ldaux=4 * D,
                                  nxt=(dh_[s], 4 * D, w[s + ".fc1"].lora is not None), **kw))   # dh feeds fc1's dX GEMM (and its adapter's v / dB)
@@ -656,7 +703,8 @@ class _QwenPlan:
         groups = []
         for s in live:
             f1 = w[s + ".fc1"]
-            kw = lora_bwd(s, f1, dh_[s], 4 * D, bb.get("xm2." + s), D, "Uf1.", "VtF1", early=False)
+            kw = self._adapter_bwd(p, f1, dh_[s], 4 * D, rows[s], bb.get("xm2." + s), D, bb.get("Uf1." + s), VtF1[s], e1[s],
+                                   down=dbw, dB=gl, dA=gl)
             groups.append(_gargs(A1=dh_[s], lda1=4 * D, B1=f1.WT, K1=4 * D, M=rows[s], N=D, C_=A["dxm"][s], ldc=D, **kw))
         _flush_batch(p, dbw, L.LoraDownArgs, lib.qfx_lora_down_batch)
         self._gemm_group(p, groups)
@@ -682,23 +730,14 @@ class _QwenPlan:
         for s in live:
             # attention out-projection backward (+ LoRA)
             lw = w[s + ".o"]
-            kw = {}
-            if lw.lora is not None:
-                lo = lw.lora
-                Vt = (VtO[s][0][:lo.Rp], VtO[s][1][:lo.Rp])
-                self._down(p, X=dyg1[s], ldx=D, M=rows[s], K=lw.N, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0),
-                           R=lo.Rp, Ut=Vt, ext=A["ext1"][s], ld_ext=A["ext1"][s].stride(0), defer=dbo)
-                self._grad(p, Vt=bb["Uo." + s], R=lo.Rp, r_valid=lo.r, X=dyg1[s], ldx=D, M=rows[s], K=lw.N,
-                           G=lo.gB, g_sr=1, g_sc=lo.r, out_scale=lo.scale, defer=gl)
-                self._grad(p, Vt=Vt, R=lo.Rp, r_valid=lo.r, X=ao2, ldx=D, M=rows[s], K=lw.K, G=lo.gA,
-                           g_sr=lw.K, g_sc=1, rpb=rpb[s], x_map=(S, off[s]), defer=gl)
-                kw = dict(A2=A["ext1"][s], lda2=A["ext1"][s].stride(0), B2=lo.WeT, ldb2=lo.WeT.stride(0), K2=lo.Kext)
+            kw = self._adapter_bwd(p, lw, dyg1[s], D, rows[s], ao2, D, bb.get("Uo." + s), VtO[s], e1[s], down=dbo, dB=gl, dA=gl,
+                                   rmap=(rpb[s], (S, off[s])))
             groups.append(_gargs(A1=dyg1[s], lda1=D, B1=lw.WT, K1=lw.N, M=rows[s], N=lw.K, C_=dao2, ldc=D, rpb=rpb[s],
                                  c_map=(S, off[s]), **kw))
         _flush_batch(p, dbo, L.LoraDownArgs, lib.qfx_lora_down_batch)
         self._gemm_group(p, groups)
         # ---- attention backward
-        ops.emit_attn_backward(p, a, A)      # two-pass pair, or the one-pass kernel (QFX_ATTN_BWD)
+        emit_attn_backward(p, a, A, self.lv.attn_bwd)      # two-pass pair, or the one-pass kernel (QFX_ATTN_BWD)
         if not a.qk_saved:      # (else: the backward of the QK norm + RoPE runs in the epilogues of the two kernels above)
             nq_t, nk_t, nq_i, nk_i = w["norms"]
             p.c(lib.qfx_qk_norm_rope_bwd, _ptr(dqkv), _ptr(bb["sqk"]), _ptr(self.rope), _ptr(nq_t), _ptr(nk_t), _ptr(nq_i),
@@ -711,44 +750,17 @@ class _QwenPlan:
             grp = w[s + ".qkv_lora"]
             kw = {}
             if grp is not None:
-                Rp, Kext = grp["Rp"], grp["Kext"]
-                Vth, Vtl = VtQ[s]
-                Uth, Utl = bb["Uqkv." + s]
-                e3 = A["ext3"][s]
+                Rp = grp["Rp"]
                 # "mxfp8-fb": the three down projections together read every element of this stream's dqkv rows and leave
                 # its MX-FP8 image (q, k, v column sections of one operand) for the qkv dX GEMM
                 pq_ = None
-                if i > 0 and all(w[s + ".qkv"][sec].lora is not None for sec in range(3)):
+                if i > 0 and all(lw.lora is not None for lw in w[s + ".qkv"]):
                     pq_ = self.fp8._preq_out(p, dq2, 3 * D, rows[s], 3 * D, "dqkv." + s, a_map=(S, off[s]))
-                hl_fused = s in hl_qkv
-                if hl_fused:     # v = d(pre-norm q | k), dV times (sB)^T left the attention epilogues as per-head partial sums
-                    dhq.append(_head_reduce_args(A["hl_qkv"], H, 3 * Rp, rows[s], rpb[s], S, off[s], e3, (Vth[:3 * Rp], Vtl[:3 * Rp]),
-                                                 Rp, Kext))
-                for sec in range(3):
-                    lw = w[s + ".qkv"][sec]
-                    if lw.lora is None:
-                        continue
-                    lo = lw.lora
-                    sl = slice(sec * Rp, (sec + 1) * Rp)
-                    if not hl_fused:
-                        self._down(p, X=dq2[:, sec * D:], ldx=3 * D, M=rows[s], K=D, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo,
-                                   ldw=lo.Bt_hi.stride(0), R=Rp, Ut=(Vth[sl], Vtl[sl]), ext=e3[:, sec * Kext:],
-                                   ld_ext=e3.stride(0), rpb=rpb[s], x_map=(S, off[s]), defer=dl,
-                                   xq=None if pq_ is None else (_ptr(pq_[0]) + sec * D, _ptr(pq_[1]), 3 * D, rows[s], sec * D // 32))
-                    self._grad(p, Vt=(Uth[sl], Utl[sl]), R=Rp, r_valid=lo.r, X=dq2[:, sec * D:], ldx=3 * D,
-                               M=rows[s], K=D, G=lo.gB, g_sr=1, g_sc=lo.r, rpb=rpb[s], x_map=(S, off[s]), out_scale=lo.scale,
-                               defer=gl)
-                los = [w[s + ".qkv"][sec].lora for sec in range(3)]
-                if all(l is not None for l in los):   # one pass over xm1 for dA of q, k and v
-                    self._grad(p, Vt=(Vth[:3 * Rp], Vtl[:3 * Rp]), R=3 * Rp, r_valid=los[0].r, group_R=Rp, X=bb["xm1." + s],
-                               ldx=D, M=rows[s], K=D, G=[l.gA for l in los], g_sr=D, g_sc=1, defer=gl)
-                else:
-                    for sec, lo in enumerate(los):
-                        if lo is not None:
-                            sl = slice(sec * Rp, (sec + 1) * Rp)
-                            self._grad(p, Vt=(Vth[sl], Vtl[sl]), R=Rp, r_valid=lo.r, X=bb["xm1." + s], ldx=D, M=rows[s],
-                                       K=D, G=lo.gA, g_sr=D, g_sc=1, defer=gl)
-                kw = dict(A2=e3, lda2=e3.stride(0), B2=grp["WeT"], ldb2=grp["WeT"].stride(0), K2=3 * Kext)
+                if s in hl_qkv:     # v = d(pre-norm q | k), dV times (sB)^T left the attention epilogues as per-head partial sums
+                    dhq.append(_head_reduce_args(A["hl_qkv"], H, 3 * Rp, rows[s], rpb[s], S, off[s], e3[s],
+                                                 (VtQ[s][0][:3 * Rp], VtQ[s][1][:3 * Rp]), Rp, grp["Kext"]))
+                kw = self._qkv_adapters_bwd(p, w[s + ".qkv"], grp, dq2, rows[s], bb["xm1." + s], bb["Uqkv." + s], VtQ[s], e3[s],
+                                            down=dl, grads=gl, rmap=(rpb[s], (S, off[s])), pq=pq_, reduced=s in hl_qkv)
             if i > 0:   # nothing upstream of block 0 needs a gradient (frozen embedders, inputs without grad)
                 groups.append(_gargs(A1=dq2, lda1=3 * D, B1=w[s + ".qkvT"], K1=3 * D, M=rows[s], N=D, C_=A["dxm"][s], ldc=D,
                                      rpb=rpb[s], a_map=(S, off[s]), **kw))

@@ -6,21 +6,34 @@ from parity_util import ROOT  # noqa: F401  (puts the package on sys.path)
 # name -> default, as DESIGN.md section 3 states them (every fusion / side-stream / deterministic path is on by default)
 EXPECTED = {"QFX_SIDE_GRADS": True, "QFX_SIDE_GRADS_FF": True, "QFX_FUSE_QKNORM_BWD": True, "QFX_FUSE_HEAD_LORA": True,
             "QFX_FUSE_LN_DOWN": True, "QFX_LN_DOWN_FRAG": True, "QFX_FP8_FUSED_QUANT": True, "QFX_GRAD_DET": True}
+CHOICES = {"QFX_ATTN_BWD": "auto"}      # the levers that are not switches: taken verbatim, the last fields of the snapshot
 
 
 def _clear(monkeypatch):
-    for name in EXPECTED:
+    for name in (*EXPECTED, *CHOICES):
         monkeypatch.delenv(name, raising=False)
 
 
 def test_defaults_match_the_table(monkeypatch):
     from qflux_amd import levers
     _clear(monkeypatch)
-    assert {name: default for name, default, _ in levers.TABLE} == EXPECTED
+    both = {**EXPECTED, **CHOICES}
+    assert {name: default for name, default, _ in levers.TABLE} == both
     assert all(isinstance(meaning, str) and meaning for _, _, meaning in levers.TABLE)
     snap = levers.read()
-    assert snap._fields == tuple(levers.field(name) for name in EXPECTED)
-    assert {name: getattr(snap, levers.field(name)) for name in EXPECTED} == EXPECTED
+    assert snap._fields == tuple(levers.field(name) for name in both)
+    assert {name: getattr(snap, levers.field(name)) for name in both} == both
+
+
+@pytest.mark.parametrize("value", [None, "auto", "2pass", "1pass", "0"])
+def test_the_attention_backward_choice_is_taken_verbatim(monkeypatch, value):
+    from qflux_amd import levers
+    _clear(monkeypatch)
+    if value is not None:
+        monkeypatch.setenv("QFX_ATTN_BWD", value)
+    snap = levers.read()
+    assert snap.attn_bwd == ("auto" if value is None else value)
+    assert all(getattr(snap, levers.field(name)) is True for name in EXPECTED)
 
 
 @pytest.mark.parametrize("name", sorted(EXPECTED))
