@@ -25,11 +25,18 @@ LOSS_BAR, PRED_BAR, GRAD_BAR = FLUX_BARS      # (the looser set: for callers tha
 _OBSERVED = {}
 
 
-def _observe(kind, res):
+def _observe(kind, res, dump=None):
     """Running maxima of what the step-parity drivers measured in this process (gpurun_out/parity_observed.json): the bars below are
-    ratcheted to ~2x these (VERDICT r3 weak #3)."""
+    ratcheted to ~2x these.
+    dump = (file name, table): only write that table as JSON into the same directory, created if absent (kernel tests that keep
+    their own figures)."""
     import json
     d = os.path.join(ROOT, "gpurun_out")
+    if dump is not None:
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, dump[0]), "w") as f:
+            json.dump(dump[1], f, indent=1)
+        return
     path = os.path.join(d, "parity_observed.json")
     if not _OBSERVED and os.path.exists(path):      # several processes (pytest, smoke) add to one file
         try:
