@@ -496,6 +496,40 @@ int qfx_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, floa
                  int32_t nesterov, int32_t first, const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale,
                  void* stream);
 
+/* ---- parameter groups (torch.optim's second axis: LoRA+ gives lora_B a higher lr than lora_A, peft's create_loraplus_optimizer /
+ * kohya's loraplus_lr_ratio; no weight decay on lora_B; other rates per stream).  Every *_grouped entry below is its family's ONE
+ * launch with the hyperparameters read per element from the row of the group the element's tensor belongs to; the arithmetic is the
+ * ungrouped entry's, statement for statement (both kernels call one element function in one translation unit), so a grouped step
+ * gives every tensor the bits an ungrouped step with its group's scalars gives it.  The clip stays global: ONE coefficient from
+ * gnorm_sq / max_norm / grad_scale for all groups (clip_grad_norm_ runs over all parameters before step()).
+ * groups: HOST array of n_groups rows, 1 <= n_groups <= QFX_MAX_PARAM_GROUPS, copied into the argument block (no device allocation, no
+ * copy per step) and turned into per-group constants in LDS at workgroup start.
+ * fp32 families: tile_group = device uint8[ceil(n / 64)], the group of every 64-element tile of the flat buffers -- every tensor
+ * starts on a multiple of 64 elements (LoraStore), so a tile never holds two tensors; the padding behind a tensor carries the
+ * tensor's group.  16-byte accesses when the buffers are 16-byte aligned.
+ * blockwise 8-bit families: block_group = device uint8[n_blocks], the group of every block-table entry (an entry never leaves its
+ * tensor); the scalar hyperparameters of the args struct are ignored, `step` is the one count of all groups.
+ * A map entry >= n_groups cannot be seen from the host without a synchronisation: the builder of the maps checks the range before
+ * upload (ops.tile_group_map / ops.block_group_map); the kernels clamp the index to the table.
+ * Rejected with QFX_EINVAL before any launch: what the ungrouped entry rejects, a NULL map or groups pointer, n_groups outside
+ * 1..QFX_MAX_PARAM_GROUPS, a row with a negative lr, a beta outside [0, 1), a negative weight_decay or eps (SGD: a negative momentum, a NULL
+ * buf with a row whose momentum != 0, nesterov with momentum <= 0 or dampening != 0).  No atomics: same inputs -> same bits.
+ * qfx_grouped_sweep_elems: the elements one grid sweep of a grouped launcher covers before its stride loop runs again -- blocksize
+ * 0: the fp32 kernels (16-byte form), 256 / 2048: the blockwise kernels with full blocks; QFX_EINVAL otherwise. ---- */
+#define QFX_MAX_PARAM_GROUPS 16
+typedef struct qfx_adamw_group { float lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2; } qfx_adamw_group;
+typedef struct qfx_sgd_group { float lr, momentum, dampening, weight_decay; int32_t nesterov; } qfx_sgd_group;
+typedef struct qfx_lion_group { float lr, beta1, beta2, weight_decay; } qfx_lion_group;
+typedef struct qfx_adam8bit_group { float lr, beta1, beta2, eps, weight_decay; } qfx_adam8bit_group;
+int64_t qfx_grouped_sweep_elems(int32_t blocksize);
+int qfx_adamw_step_grouped(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* tile_group,
+                           const qfx_adamw_group* groups, int32_t n_groups, const float* gnorm_sq /* may be NULL */, float max_norm,
+                           float grad_scale, void* stream);
+/* `first` as qfx_sgd_step's: the one step that creates buf, for every group */
+int qfx_sgd_step_grouped(float* p, const float* g, float* buf, int64_t n, const uint8_t* tile_group, const qfx_sgd_group* groups,
+                         int32_t n_groups, int32_t first, const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale,
+                         void* stream);
+
 /* ---- Prodigy, the reference's parameter-free optimizer choice (third party prodigyopt.Prodigy, requirements.txt:33; selected by
  * configs/face_seg_flux_kontext_fp16_prodigy.yaml:41-47 and the optimizer section of every tests/test_configs/test_example_*.yaml;
  * instantiated generically at base_trainer.py:884-898, stepped at :531 after clip_gradients :449-455).  One fused step over the
@@ -567,6 +601,10 @@ typedef struct qfx_adam8bit_args {
   float max_norm, grad_scale;
 } qfx_adam8bit_args;
 int qfx_adam8bit_step(const qfx_adam8bit_args* a, void* stream);
+/* parameter groups (see above): a->lr / beta1 / beta2 / eps / weight_decay are ignored, every table entry bi takes the row
+ * groups[block_group[bi]]; step_size and eps_hat are formed per group, in double on the host, from the row and a->step */
+int qfx_adam8bit_step_grouped(const qfx_adam8bit_args* a, const uint8_t* block_group, const qfx_adam8bit_group* groups,
+                              int32_t n_groups, void* stream);
 
 /* ---- Adafactor (third party transformers.optimization.Adafactor, the optimizer LoRA fine-tuning stacks offer next to the ones
  * above; in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909, stepped at :531 after
@@ -652,6 +690,11 @@ typedef struct qfx_lion8bit_args {
   float max_norm, grad_scale;
 } qfx_lion8bit_args;
 int qfx_lion8bit_step(const qfx_lion8bit_args* a, void* stream);
+/* parameter groups (see above); qfx_lion8bit_step_grouped ignores a->lr / beta1 / beta2 / weight_decay */
+int qfx_lion_step_grouped(float* p, const float* g, float* m, int64_t n, const uint8_t* tile_group, const qfx_lion_group* groups,
+                          int32_t n_groups, const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale, void* stream);
+int qfx_lion8bit_step_grouped(const qfx_lion8bit_args* a, const uint8_t* block_group, const qfx_lion_group* groups, int32_t n_groups,
+                              void* stream);
 
 /* ---- Schedule-Free AdamW (Defazio et al., "The Road Less Scheduled", 2024; third party schedulefree.AdamWScheduleFree, the method
  * made for the constant learning rate the reference's configs run (lr_scheduler.scheduler_type: constant / constant_with_warmup);

@@ -61,11 +61,49 @@ __global__ __launch_bounds__(256) void lion_kernel(float* __restrict__ p, const 
   }
 }
 
+// parameter groups: lion_elem with the LionConst of the tile's group, formed by lion_const in LDS at workgroup start
+template <bool VEC>
+__global__ __launch_bounds__(256) void lion_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           int64_t n, const uint8_t* __restrict__ tile_group,
+                                                           const GroupTable<qfx_lion_group> tab, int n_groups,
+                                                           const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
+  __shared__ LionConst ks[QFX_MAX_PARAM_GROUPS];
+  if ((int)threadIdx.x < n_groups) {
+    const qfx_lion_group q = tab.g[threadIdx.x];
+    ks[threadIdx.x] = lion_const(q.lr, q.beta1, q.beta2, q.weight_decay, opt_clip(gnorm_sq, max_norm, grad_scale));
+  }
+  __syncthreads();
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nv = VEC ? n / 4 : 0;
+  for (int64_t i = tid; i < nv; i += nt) {
+    const LionConst k = ks[group_index(tile_group, i >> 4)];
+    f32x4 pv = *(const f32x4*)(p + 4 * i);
+    const f32x4 gv = *(const f32x4*)(g + 4 * i);
+    f32x4 mv = *(const f32x4*)(m + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], mj = mv[j];
+      lion_elem(pj, gv[j], mj, k);
+      pv[j] = pj; mv[j] = mj;
+    }
+    *(f32x4*)(p + 4 * i) = pv;
+    *(f32x4*)(m + 4 * i) = mv;
+  }
+  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
+    const LionConst k = ks[group_index(tile_group, i >> 6)];
+    float pi = p[i], mi = m[i];
+    lion_elem(pi, g[i], mi, k);
+    p[i] = pi; m[i] = mi;
+  }
+}
+
 // ---- blockwise 8-bit state (the tile helpers of qfx_optim.h, shared with adam8bit_kernel).
 // BS = 256: E = 4, a wave per entry (4 entries per workgroup and iteration), the block maximum a cross-lane reduction;
 // BS = 2048: E = 8, the workgroup per entry, the maximum through LDS
-template <int BS>
-__global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a) {
+// GROUPED: the LionConst of every table entry is the one of its group (block_group, one byte per entry; tab: the groups' rows)
+template <int BS, bool GROUPED>
+__device__ __forceinline__ void lion8bit_body(const qfx_lion8bit_args& a, const uint8_t* __restrict__ block_group,
+                                              const GroupTable<qfx_lion_group>* tab, int n_groups) {
   constexpr bool WG = BS > 256;
   constexpr int E = WG ? 8 : 4;
   constexpr int LANES = WG ? 256 : 64;
@@ -75,7 +113,16 @@ __global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a
   const int t = threadIdx.x;
   q1s[t] = a.qmap1[t];
   mid1[t] = t < 255 ? (a.qmap1[t] + a.qmap1[t + 1]) / 2.0f : INFINITY;
-  const LionConst k = lion_const(a.lr, a.beta1, a.beta2, a.weight_decay, opt_clip(a.gnorm_sq, a.max_norm, a.grad_scale));
+  __shared__ LionConst ks[GROUPED ? QFX_MAX_PARAM_GROUPS : 1];
+  LionConst k;
+  if (GROUPED) {
+    if (t < n_groups) {
+      const qfx_lion_group q = tab->g[t];
+      ks[t] = lion_const(q.lr, q.beta1, q.beta2, q.weight_decay, opt_clip(a.gnorm_sq, a.max_norm, a.grad_scale));
+    }
+  } else {
+    k = lion_const(a.lr, a.beta1, a.beta2, a.weight_decay, opt_clip(a.gnorm_sq, a.max_norm, a.grad_scale));
+  }
   __syncthreads();
   const int lane = WG ? t : (t & 63);
   const int64_t first = WG ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + (t >> 6);
@@ -83,6 +130,7 @@ __global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a
   int parity = 0;
   for (int64_t bi = first; bi < a.n_blocks; bi += stride) {      // WG: bi is uniform over the workgroup, every thread reaches the barrier
     const qfx_adam8bit_block e = a.table[bi];
+    if (GROUPED) k = ks[group_index(block_group, bi)];
     const int64_t base = e.off + (int64_t)lane * E;
     const int n = e.len - lane * E;
     float p[E], g[E], m[E];
@@ -132,6 +180,16 @@ __global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a
   }
 }
 
+template <int BS>
+__global__ __launch_bounds__(256) void lion8bit_kernel(const qfx_lion8bit_args a) {
+  lion8bit_body<BS, false>(a, nullptr, nullptr, 0);
+}
+template <int BS>
+__global__ __launch_bounds__(256) void lion8bit_grouped_kernel(const qfx_lion8bit_args a, const uint8_t* __restrict__ block_group,
+                                                               const GroupTable<qfx_lion_group> tab, int n_groups) {
+  lion8bit_body<BS, true>(a, block_group, &tab, n_groups);
+}
+
 bool lion_scalars_ok(float lr, float beta1, float beta2, float weight_decay) {
   return lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && weight_decay >= 0.f;      // a NaN fails each
 }
@@ -142,7 +200,7 @@ extern "C" int qfx_lion_step(float* p, const float* g, float* m, int64_t n, floa
                              const float* gnorm_sq, float max_norm, float grad_scale, void* stream) {
   if (!p || !g || !m || n <= 0 || !lion_scalars_ok(lr, beta1, beta2, weight_decay)) return QFX_EINVAL;
   const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0;
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, 4096);      // adamw_kernel's grid policy
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);      // adamw_kernel's grid policy
   if (vec)
     hipLaunchKernelGGL(lion_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, n, lr, beta1, beta2, weight_decay,
                        gnorm_sq, max_norm, grad_scale);
@@ -162,6 +220,46 @@ extern "C" int qfx_lion8bit_step(const qfx_lion8bit_args* a, void* stream) {
     hipLaunchKernelGGL(lion8bit_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, *a);
   else
     hipLaunchKernelGGL(lion8bit_kernel<2048>, grid, dim3(256), 0, (hipStream_t)stream, *a);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+namespace {
+bool lion_groups_ok(const qfx_lion_group* groups, int n_groups) {
+  if (!groups_count_ok(groups, n_groups)) return false;
+  for (int i = 0; i < n_groups; ++i)
+    if (!lion_scalars_ok(groups[i].lr, groups[i].beta1, groups[i].beta2, groups[i].weight_decay)) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" int qfx_lion_step_grouped(float* p, const float* g, float* m, int64_t n, const uint8_t* tile_group,
+                                     const qfx_lion_group* groups, int32_t n_groups, const float* gnorm_sq, float max_norm,
+                                     float grad_scale, void* stream) {
+  if (!p || !g || !m || !tile_group || n <= 0 || !lion_groups_ok(groups, n_groups)) return QFX_EINVAL;
+  const GroupTable<qfx_lion_group> tab = group_table(groups, n_groups);
+  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0;
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
+  if (vec)
+    hipLaunchKernelGGL(lion_grouped_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, n, tile_group, tab, n_groups,
+                       gnorm_sq, max_norm, grad_scale);
+  else
+    hipLaunchKernelGGL(lion_grouped_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, n, tile_group, tab, n_groups,
+                       gnorm_sq, max_norm, grad_scale);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int qfx_lion8bit_step_grouped(const qfx_lion8bit_args* a, const uint8_t* block_group, const qfx_lion_group* groups,
+                                         int32_t n_groups, void* stream) {
+  if (!a || !a->p || !a->g || !a->q1 || !a->absmax1 || !a->m32 || !a->table || !a->qmap1 || !block_group) return QFX_EINVAL;
+  if ((a->blocksize != 256 && a->blocksize != 2048) || a->n_blocks <= 0 || !lion_groups_ok(groups, n_groups)) return QFX_EINVAL;
+  const GroupTable<qfx_lion_group> tab = group_table(groups, n_groups);
+  const dim3 grid(blockwise_grid(a->n_blocks, a->blocksize));
+  if (a->blocksize == 256)
+    hipLaunchKernelGGL(lion8bit_grouped_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, *a, block_group, tab, n_groups);
+  else
+    hipLaunchKernelGGL(lion8bit_grouped_kernel<2048>, grid, dim3(256), 0, (hipStream_t)stream, *a, block_group, tab, n_groups);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

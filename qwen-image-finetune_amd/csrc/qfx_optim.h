@@ -93,10 +93,36 @@ inline int flat_grid(int64_t work, int64_t cap) {
   return (int)(b < cap ? b : cap);
 }
 
+// workgroup caps of the one-launch steps: the fp32 elementwise kernels (adamw_kernel's policy) and the blockwise 8-bit kernels
+constexpr int64_t FLAT_STEP_CAP = 4096;
+constexpr int64_t BLOCKWISE_CAP = 2048;
+
 // grid of a blockwise 8-bit kernel over n_blocks table entries: a wave per entry (blocksize 256) or a workgroup per entry (2048)
 inline unsigned blockwise_grid(int64_t n_blocks, int blocksize) {
   const int64_t wgs = blocksize == 256 ? (n_blocks + 3) / 4 : n_blocks;
-  return (unsigned)(wgs < 2048 ? wgs : 2048);
+  return (unsigned)(wgs < BLOCKWISE_CAP ? wgs : BLOCKWISE_CAP);
 }
+
+// ---- parameter groups (include/qfx.h): the grouped kernels take their hyperparameter rows by value in the argument block, the
+// first n_groups lanes of every workgroup turn them into the family's per-group constants in LDS, and every 64-element tile (fp32
+// kernels) or block-table entry (blockwise kernels) names its row with one byte.  An index the builder did not range-check is
+// clamped to the table here, so that it can never read LDS outside it.
+template <typename Row>
+struct GroupTable { Row g[QFX_MAX_PARAM_GROUPS]; };
+
+template <typename Row>
+inline GroupTable<Row> group_table(const Row* groups, int n_groups) {
+  GroupTable<Row> t = {};
+  for (int i = 0; i < n_groups; ++i) t.g[i] = groups[i];
+  return t;
+}
+
+__device__ __forceinline__ int group_index(const uint8_t* __restrict__ map, int64_t i) {
+  const int gi = map[i];
+  return gi < QFX_MAX_PARAM_GROUPS ? gi : QFX_MAX_PARAM_GROUPS - 1;
+}
+
+inline bool groups_count_ok(const void* groups, int n_groups) { return groups != nullptr && n_groups >= 1 && n_groups <= QFX_MAX_PARAM_GROUPS; }
+inline bool beta_ok(float b) { return b >= 0.f && b < 1.f; }      // a NaN fails
 
 }  // namespace

@@ -1,6 +1,7 @@
 // qfx_optim.hip -- the fp32-state optimizers over the flat LoRA buffers and the gradient norm that feeds their clip, see
-// include/qfx.h: the squared-sum kernels (atomic and deterministic form), AdamW, SGD and Prodigy.  Built with the compiler's
-// default contraction: the products and sums of these kernels fuse where the compiler chooses, the clip prologue's included.
+// include/qfx.h: the squared-sum kernels (atomic and deterministic form), AdamW and SGD (each with its parameter-group form) and
+// Prodigy.  Built with the compiler's default contraction: the products and sums of these kernels fuse where the compiler chooses,
+// the clip prologue's included -- except in adamw_elem / sgd_elem, which two kernels each must round alike and which pin them.
 #include "qfx_common.h"
 #include "qfx_optim.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
@@ -39,6 +40,23 @@ __global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict
   if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// one AdamW element (torch.optim.AdamW): the ONE statement of the arithmetic, called by adamw_kernel and adamw_grouped_kernel.
+// step = lr / bias_corr1 and rs2 = 1 / sqrt(bias_corr2) are formed once per launch (per group); 1 - b1, 1 - b2 and 1 - lr wd here.
+// Which products fuse with their sums is written out (contraction off inside, explicit fmaf): these are the fusions the default
+// contraction chose for adamw_kernel when it held this arithmetic inline, and left to the compiler they moved with the code
+// around them (the operand order of the first moment's FMA changed when the loads were reordered) -- pinned, the ungrouped step
+// keeps its bits and the grouped step rounds like it.
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float clip, float lr, float b1, float b2, float eps,
+                                           float wd, float step, float rs2) {
+#pragma clang fp contract(off)
+  const float gi = g * clip;
+  const float pi = p * fmaf(-lr, wd, 1.0f);
+  const float mi = fmaf(1.0f - b1, gi, b1 * m);
+  const float vi = b2 * v + ((1.0f - b2) * gi) * gi;
+  p = pi - (step * mi) / fmaf(rs2, sqrtf(vi), eps);
+  m = mi; v = vi;
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
                                                     float wd, float bc1, float bc2, const float* __restrict__ gnorm_sq,
@@ -47,31 +65,135 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   const float step = lr / bc1;
   const float rs2 = 1.0f / sqrtf(bc2);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * clip;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    pi -= step * mi / (sqrtf(vi) * rs2 + eps);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_elem(pi, g[i], mi, vi, clip, lr, b1, b2, eps, wd, step, rs2);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+// ---- parameter groups: the same element function, its scalars read per 64-element tile from the group's row in LDS.
+// VEC: p, g, m, v are 16-byte aligned -> one dwordx4 per buffer and lane (a quad never leaves its tile: tiles start at multiples
+// of 64); the n % 4 tail (and everything, without VEC) is scalar.
+struct AdamWRow { float lr, b1, b2, eps, wd, step, rs2, pad; };
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, int64_t n, const uint8_t* __restrict__ tile_group,
+                                                            const GroupTable<qfx_adamw_group> tab, int n_groups,
+                                                            const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
+  __shared__ AdamWRow rows[QFX_MAX_PARAM_GROUPS];
+  if ((int)threadIdx.x < n_groups) {
+    const qfx_adamw_group q = tab.g[threadIdx.x];
+    AdamWRow r;
+    r.lr = q.lr; r.b1 = q.beta1; r.b2 = q.beta2; r.eps = q.eps; r.wd = q.weight_decay;
+    r.step = q.lr / q.bias_corr1;
+    r.rs2 = 1.0f / sqrtf(q.bias_corr2);
+    r.pad = 0.f;
+    rows[threadIdx.x] = r;
+  }
+  const float clip = opt_clip(gnorm_sq, max_norm, grad_scale);
+  __syncthreads();
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nv = VEC ? n / 4 : 0;
+  for (int64_t i = tid; i < nv; i += nt) {
+    const AdamWRow r = rows[group_index(tile_group, i >> 4)];
+    f32x4 pv = *(const f32x4*)(p + 4 * i);
+    const f32x4 gv = *(const f32x4*)(g + 4 * i);
+    f32x4 mv = *(const f32x4*)(m + 4 * i);
+    f32x4 vv = *(const f32x4*)(v + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], mj = mv[j], vj = vv[j];
+      adamw_elem(pj, gv[j], mj, vj, clip, r.lr, r.b1, r.b2, r.eps, r.wd, r.step, r.rs2);
+      pv[j] = pj; mv[j] = mj; vv[j] = vj;
+    }
+    *(f32x4*)(p + 4 * i) = pv;
+    *(f32x4*)(m + 4 * i) = mv;
+    *(f32x4*)(v + 4 * i) = vv;
+  }
+  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
+    const AdamWRow r = rows[group_index(tile_group, i >> 6)];
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_elem(pi, g[i], mi, vi, clip, r.lr, r.b1, r.b2, r.eps, r.wd, r.step, r.rs2);
     p[i] = pi; m[i] = mi; v[i] = vi;
   }
 }
 
 // torch.optim.SGD over the flat LoRA buffers after the clip prologue (include/qfx.h).  buf is never touched when mom == 0.
+// one SGD element, called by sgd_kernel and sgd_grouped_kernel.  b: the element's momentum buffer value (read by the caller only
+// when it exists and is not created by this step; written back by the caller when mom != 0); keep = 1 - dampening.  The fusions
+// are pinned as in adamw_elem: the decayed gradient and the buffer update round every product, the Nesterov sum and the
+// parameter update are one FMA each.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& b, float clip, float lr, float mom, float keep, float wd, int nesterov,
+                                         int first) {
+#pragma clang fp contract(off)
+  const float pi = p;
+  float gi = g * clip;
+  if (wd != 0.f) gi = wd * pi + gi;
+  if (mom != 0.f) {
+    const float bi = first ? gi : keep * gi + mom * b;
+    b = bi;
+    gi = nesterov ? fmaf(mom, bi, gi) : bi;
+  }
+  p = fmaf(-lr, gi, pi);
+}
+
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                   int64_t n, float lr, float mom, float damp, float wd, int nesterov, int first,
                                                   const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
   const float clip = opt_clip(gnorm_sq, max_norm, grad_scale);
   const float keep = 1.0f - damp;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float pi = p[i];
-    float gi = g[i] * clip;
-    if (wd != 0.f) gi += wd * pi;
-    if (mom != 0.f) {
-      const float bi = first ? gi : mom * buf[i] + keep * gi;
-      buf[i] = bi;
-      gi = nesterov ? gi + mom * bi : bi;
+    float pi = p[i], bi = 0.f;
+    if (mom != 0.f && !first) bi = buf[i];
+    sgd_elem(pi, g[i], bi, clip, lr, mom, keep, wd, nesterov, first);
+    if (mom != 0.f) buf[i] = bi;
+    p[i] = pi;
+  }
+}
+
+// parameter groups: a group with momentum == 0 neither reads nor writes its part of buf
+struct SgdRow { float lr, mom, keep, wd; int nesterov, pad0, pad1, pad2; };
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                          int64_t n, const uint8_t* __restrict__ tile_group,
+                                                          const GroupTable<qfx_sgd_group> tab, int n_groups, int first,
+                                                          const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
+  __shared__ SgdRow rows[QFX_MAX_PARAM_GROUPS];
+  if ((int)threadIdx.x < n_groups) {
+    const qfx_sgd_group q = tab.g[threadIdx.x];
+    SgdRow r;
+    r.lr = q.lr; r.mom = q.momentum; r.keep = 1.0f - q.dampening; r.wd = q.weight_decay; r.nesterov = q.nesterov;
+    r.pad0 = r.pad1 = r.pad2 = 0;
+    rows[threadIdx.x] = r;
+  }
+  const float clip = opt_clip(gnorm_sq, max_norm, grad_scale);
+  __syncthreads();
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nv = VEC ? n / 4 : 0;
+  for (int64_t i = tid; i < nv; i += nt) {
+    const SgdRow r = rows[group_index(tile_group, i >> 4)];
+    f32x4 pv = *(const f32x4*)(p + 4 * i);
+    const f32x4 gv = *(const f32x4*)(g + 4 * i);
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (r.mom != 0.f && !first) bv = *(const f32x4*)(buf + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], bj = bv[j];
+      sgd_elem(pj, gv[j], bj, clip, r.lr, r.mom, r.keep, r.wd, r.nesterov, first);
+      pv[j] = pj; bv[j] = bj;
     }
-    p[i] = pi - lr * gi;
+    if (r.mom != 0.f) *(f32x4*)(buf + 4 * i) = bv;
+    *(f32x4*)(p + 4 * i) = pv;
+  }
+  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
+    const SgdRow r = rows[group_index(tile_group, i >> 6)];
+    float pi = p[i], bi = 0.f;
+    if (r.mom != 0.f && !first) bi = buf[i];
+    sgd_elem(pi, g[i], bi, clip, r.lr, r.mom, r.keep, r.wd, r.nesterov, first);
+    if (r.mom != 0.f) buf[i] = bi;
+    p[i] = pi;
   }
 }
 
@@ -167,7 +289,7 @@ extern "C" int qfx_adamw_step(float* p, const float* g, float* m, float* v, int6
                               float eps, float weight_decay, float bias_corr1, float bias_corr2, const float* gnorm_sq,
                               float max_norm, float grad_scale, void* stream) {
   if (!p || !g || !m || !v || n <= 0) return QFX_EINVAL;
-  const int blocks = flat_grid(n, 4096);
+  const int blocks = flat_grid(n, FLAT_STEP_CAP);
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                      weight_decay, bias_corr1, bias_corr2, gnorm_sq, max_norm, grad_scale);
   QFX_CHECK_LAUNCH();
@@ -180,9 +302,61 @@ extern "C" int qfx_sgd_step(float* p, const float* g, float* buf, int64_t n, flo
   if (!p || !g || n <= 0) return QFX_EINVAL;
   if (!buf && momentum != 0.f) return QFX_EINVAL;
   if (nesterov && (!(momentum > 0.f) || dampening != 0.f)) return QFX_EINVAL;
-  const int blocks = flat_grid(n, 4096);
+  const int blocks = flat_grid(n, FLAT_STEP_CAP);
   hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, momentum, dampening,
                      weight_decay, nesterov, first, gnorm_sq, max_norm, grad_scale);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int64_t qfx_grouped_sweep_elems(int32_t blocksize) {
+  if (blocksize == 0) return FLAT_STEP_CAP * 256 * 4;      // the 16-byte form of the fp32 kernels: a quad per lane
+  if (blocksize == 256) return BLOCKWISE_CAP * 4 * 256;    // a wave per table entry, four entries per workgroup
+  if (blocksize == 2048) return BLOCKWISE_CAP * 2048;      // a workgroup per table entry
+  return QFX_EINVAL;
+}
+
+extern "C" int qfx_adamw_step_grouped(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* tile_group,
+                                      const qfx_adamw_group* groups, int32_t n_groups, const float* gnorm_sq, float max_norm,
+                                      float grad_scale, void* stream) {
+  if (!p || !g || !m || !v || !tile_group || n <= 0 || !groups_count_ok(groups, n_groups)) return QFX_EINVAL;
+  for (int i = 0; i < n_groups; ++i) {
+    const qfx_adamw_group& q = groups[i];
+    if (!(q.lr >= 0.f) || !beta_ok(q.beta1) || !beta_ok(q.beta2) || !(q.eps >= 0.f) || !(q.weight_decay >= 0.f)) return QFX_EINVAL;
+    if (!(q.bias_corr1 > 0.f) || !(q.bias_corr2 > 0.f)) return QFX_EINVAL;
+  }
+  const GroupTable<qfx_adamw_group> tab = group_table(groups, n_groups);
+  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
+  if (vec)
+    hipLaunchKernelGGL(adamw_grouped_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, tile_group, tab,
+                       n_groups, gnorm_sq, max_norm, grad_scale);
+  else
+    hipLaunchKernelGGL(adamw_grouped_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, tile_group, tab,
+                       n_groups, gnorm_sq, max_norm, grad_scale);
+  QFX_CHECK_LAUNCH();
+  return QFX_OK;
+}
+
+extern "C" int qfx_sgd_step_grouped(float* p, const float* g, float* buf, int64_t n, const uint8_t* tile_group,
+                                    const qfx_sgd_group* groups, int32_t n_groups, int32_t first, const float* gnorm_sq,
+                                    float max_norm, float grad_scale, void* stream) {
+  if (!p || !g || !tile_group || n <= 0 || !groups_count_ok(groups, n_groups)) return QFX_EINVAL;
+  for (int i = 0; i < n_groups; ++i) {
+    const qfx_sgd_group& q = groups[i];
+    if (!(q.lr >= 0.f) || !(q.momentum >= 0.f) || !(q.weight_decay >= 0.f)) return QFX_EINVAL;
+    if (!buf && q.momentum != 0.f) return QFX_EINVAL;
+    if (q.nesterov && (!(q.momentum > 0.f) || q.dampening != 0.f)) return QFX_EINVAL;
+  }
+  const GroupTable<qfx_sgd_group> tab = group_table(groups, n_groups);
+  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0;
+  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
+  if (vec)
+    hipLaunchKernelGGL(sgd_grouped_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, tile_group, tab,
+                       n_groups, first, gnorm_sq, max_norm, grad_scale);
+  else
+    hipLaunchKernelGGL(sgd_grouped_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, tile_group, tab,
+                       n_groups, first, gnorm_sq, max_norm, grad_scale);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

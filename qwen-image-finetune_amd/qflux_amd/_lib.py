@@ -158,6 +158,27 @@ class Lion8bitArgs(C.Structure):
                 ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
+MAX_PARAM_GROUPS = 16     # QFX_MAX_PARAM_GROUPS
+
+
+class AdamwGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("bias_corr1", C.c_float), ("bias_corr2", C.c_float)]
+
+
+class SgdGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float), ("weight_decay", C.c_float),
+                ("nesterov", C.c_int32)]
+
+
+class LionGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("weight_decay", C.c_float)]
+
+
+class Adam8bitGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
+
+
 class MuonTensor(C.Structure):
     _fields_ = [("off", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("lr_ratio", C.c_float), ("reserved", C.c_int32)]
 
@@ -259,12 +280,18 @@ SYMBOLS = {
     "qfx_sumsq_det": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp]),
     "qfx_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _vp, _f, _f, _vp]),
     "qfx_sgd_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _i32, _i32, _vp, _f, _f, _vp]),
+    "qfx_grouped_sweep_elems": (_i64, [_i32]),
+    "qfx_adamw_step_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, C.POINTER(AdamwGroup), _i32, _vp, _f, _f, _vp]),
+    "qfx_sgd_step_grouped": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.POINTER(SgdGroup), _i32, _i32, _vp, _f, _f, _vp]),
     "qfx_prodigy_init_state": (C.c_int, [_vp, C.c_double, _vp]),
     "qfx_prodigy_step": (C.c_int, [C.POINTER(ProdigyArgs), _vp]),
     "qfx_adam8bit_step": (C.c_int, [C.POINTER(Adam8bitArgs), _vp]),
+    "qfx_adam8bit_step_grouped": (C.c_int, [C.POINTER(Adam8bitArgs), _vp, C.POINTER(Adam8bitGroup), _i32, _vp]),
     "qfx_adafactor_step": (C.c_int, [C.POINTER(AdafactorArgs), _vp]),
     "qfx_lion_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _f, _f, _vp]),
     "qfx_lion8bit_step": (C.c_int, [C.POINTER(Lion8bitArgs), _vp]),
+    "qfx_lion_step_grouped": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.POINTER(LionGroup), _i32, _vp, _f, _f, _vp]),
+    "qfx_lion8bit_step_grouped": (C.c_int, [C.POINTER(Lion8bitArgs), _vp, C.POINTER(LionGroup), _i32, _vp]),
     "qfx_sfadamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i32, _vp, _f, _f, _vp]),
     "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
     "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),

@@ -439,6 +439,124 @@ def lion8bit_step(p, g, q1, absmax1, m32, layout, qmap1, lr, betas, weight_decay
     L.check(lib.qfx_lion8bit_step(a, stream_ptr()), "qfx_lion8bit_step")
 
 
+# ---- parameter groups (qfx.h): the one-byte maps from the flat layout to a group, and the grouped step launches
+MAX_PARAM_GROUPS = L.MAX_PARAM_GROUPS
+
+
+def grouped_sweep_elems(blocksize=0):
+    """Elements one grid sweep of a grouped launcher covers (0: the fp32 kernels; 256 / 2048: the blockwise kernels)."""
+    return int(lib.qfx_grouped_sweep_elems(int(blocksize)))
+
+
+def _check_assign(what, n_entries, assign, n_groups):
+    if not 1 <= n_groups <= MAX_PARAM_GROUPS:
+        raise ValueError(f"{what}: {n_groups} parameter groups, 1 to {MAX_PARAM_GROUPS} are supported")
+    if len(assign) != n_entries:
+        raise ValueError(f"{what}: {len(assign)} group indices for {n_entries} tensors")
+    for i, gi in enumerate(assign):
+        if int(gi) != gi or not 0 <= gi < n_groups:
+            raise ValueError(f"{what}: tensor {i} is assigned to group {gi}, outside 0..{n_groups - 1}")
+
+
+def tile_group_map(entries, assign, n_groups, numel=None, device=None):
+    """uint8[ceil(numel / 64)]: the group of every 64-element tile of the flat buffers.  entries: (offset, numel) of every tensor, in
+    ascending order, every offset a multiple of 64 (LoraStore's layout: a tile never holds two tensors); assign[i]: the group of
+    tensor i.  The padding behind a tensor (the tail of its last tile, and any whole tile up to the next tensor) carries the tensor's
+    group.  Range-checked here, on the host, before the upload: the kernels cannot."""
+    _check_assign("tile_group_map", len(entries), assign, n_groups)
+    extent = max((int(off) + int(k) for off, k in entries), default=0)
+    numel = extent if numel is None else int(numel)
+    if not entries or numel < extent:
+        raise ValueError(f"tile_group_map: {len(entries)} tensors up to element {extent} in a buffer of {numel}")
+    tiles = torch.empty((numel + 63) // 64, dtype=torch.uint8)
+    last = 0
+    for i, ((off, k), gi) in enumerate(zip(entries, assign)):
+        off, k = int(off), int(k)
+        if off % 64 or k <= 0 or off < last:
+            raise ValueError(f"tile_group_map: tensor {i} at offset {off} with {k} elements (offsets are ascending multiples of 64)")
+        nxt = int(entries[i + 1][0]) // 64 if i + 1 < len(entries) else tiles.numel()
+        tiles[off // 64 if i else 0:nxt] = int(gi)
+        last = off + k
+    return tiles if device is None else tiles.to(device)
+
+
+def block_group_map(layout, assign, n_groups, device=None):
+    """uint8[layout.n_blocks]: the group of every entry of an adam8bit_block_table (its rows are per tensor, in entry order: an entry
+    never spans two tensors, so never two groups).  Range-checked on the host before the upload."""
+    _check_assign("block_group_map", len(layout.tensors), assign, n_groups)
+    rows = []
+    for (off, k, *_), gi in zip(layout.tensors, assign):
+        rows += [int(gi)] * ((k + layout.blocksize - 1) // layout.blocksize)
+    if len(rows) != layout.n_blocks:
+        raise ValueError(f"block_group_map: {len(rows)} rows for a table of {layout.n_blocks}")
+    t = torch.tensor(rows, dtype=torch.uint8)
+    return t if device is None else t.to(device)
+
+
+def _group_rows(what, ctype, rows, tmap, need, p):
+    if not 1 <= len(rows) <= MAX_PARAM_GROUPS:
+        raise ValueError(f"{what}: {len(rows)} parameter groups, 1 to {MAX_PARAM_GROUPS} are supported")
+    _check_tensors(what, p, (("the group map", tmap, torch.uint8, need),))
+    return (ctype * len(rows))(*[ctype(*r) for r in rows])
+
+
+def adamw_step_grouped(p, g, m, v, tile_group, groups, step, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """adamw_step with per-group hyperparameters: groups = [(lr, beta1, beta2, eps, weight_decay)], tile_group from tile_group_map."""
+    rows = _group_rows("adamw_step_grouped", L.AdamwGroup, [(lr, b1, b2, eps, wd, 1.0 - b1 ** step, 1.0 - b2 ** step)
+                                                            for lr, b1, b2, eps, wd in groups], tile_group, (p.numel() + 63) // 64, p)
+    _check_tensors("adamw_step_grouped", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p), ("g", g), ("m", m), ("v", v))])
+    L.check(lib.qfx_adamw_step_grouped(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(tile_group), rows, len(groups), _p(gnorm_sq), max_norm,
+                                       grad_scale, stream_ptr()), "qfx_adamw_step_grouped")
+
+
+def sgd_step_grouped(p, g, buf, tile_group, groups, first=False, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """sgd_step with per-group hyperparameters: groups = [(lr, momentum, dampening, weight_decay, nesterov)]; buf: None iff every
+    group's momentum is 0."""
+    rows = _group_rows("sgd_step_grouped", L.SgdGroup, [(lr, mom, damp, wd, int(bool(nes))) for lr, mom, damp, wd, nes in groups],
+                       tile_group, (p.numel() + 63) // 64, p)
+    _check_tensors("sgd_step_grouped", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p), ("g", g)) + ((("buf", buf),) if buf is not None else ())])
+    L.check(lib.qfx_sgd_step_grouped(_p(p), _p(g), _p(buf), p.numel(), _p(tile_group), rows, len(groups), int(bool(first)), _p(gnorm_sq),
+                                     max_norm, grad_scale, stream_ptr()), "qfx_sgd_step_grouped")
+
+
+def lion_step_grouped(p, g, m, tile_group, groups, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """lion_step with per-group hyperparameters: groups = [(lr, beta1, beta2, weight_decay)]."""
+    rows = _group_rows("lion_step_grouped", L.LionGroup, groups, tile_group, (p.numel() + 63) // 64, p)
+    _check_tensors("lion_step_grouped", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p), ("g", g), ("m", m))])
+    L.check(lib.qfx_lion_step_grouped(_p(p), _p(g), _p(m), p.numel(), _p(tile_group), rows, len(groups), _p(gnorm_sq), max_norm,
+                                      grad_scale, stream_ptr()), "qfx_lion_step_grouped")
+
+
+def adam8bit_step_grouped(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2, block_group, groups, step, gnorm_sq=None,
+                          max_norm=0.0, grad_scale=1.0):
+    """adam8bit_step with per-group hyperparameters: groups = [(lr, beta1, beta2, eps, weight_decay)], block_group from block_group_map."""
+    f32, u8 = torch.float32, torch.uint8
+    rows = _group_rows("adam8bit_step_grouped", L.Adam8bitGroup, groups, block_group, layout.n_blocks, p)
+    _check_tensors("adam8bit_step_grouped", p, (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
+                                                ("q2", q2, u8, layout.extent), ("absmax1", absmax1, f32, max(1, layout.n_absmax)),
+                                                ("absmax2", absmax2, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
+                                                ("v32", v32, f32, max(1, layout.n_fp32)), ("qmap1", qmap1, f32, 256), ("qmap2", qmap2, f32, 256)))
+    if layout.table.device != p.device:
+        raise ValueError("adam8bit_step_grouped: the block table lives on another device")
+    a = L.Adam8bitArgs(_p(p), _p(g), _p(q1), _p(q2), _p(absmax1), _p(absmax2), _p(m32), _p(v32), _p(layout.table), layout.n_blocks,
+                       layout.blocksize, _p(qmap1), _p(qmap2), 0.0, 0.0, 0.0, 0.0, 0.0, int(step), _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_adam8bit_step_grouped(a, _p(block_group), rows, len(groups), stream_ptr()), "qfx_adam8bit_step_grouped")
+
+
+def lion8bit_step_grouped(p, g, q1, absmax1, m32, layout, qmap1, block_group, groups, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """lion8bit_step with per-group hyperparameters: groups = [(lr, beta1, beta2, weight_decay)]."""
+    f32, u8 = torch.float32, torch.uint8
+    rows = _group_rows("lion8bit_step_grouped", L.LionGroup, groups, block_group, layout.n_blocks, p)
+    _check_tensors("lion8bit_step_grouped", p, (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, layout.extent),
+                                                ("absmax1", absmax1, f32, max(1, layout.n_absmax)), ("m32", m32, f32, max(1, layout.n_fp32)),
+                                                ("qmap1", qmap1, f32, 256)))
+    if layout.table.device != p.device:
+        raise ValueError("lion8bit_step_grouped: the block table lives on another device")
+    a = L.Lion8bitArgs(_p(p), _p(g), _p(q1), _p(absmax1), _p(m32), _p(layout.table), layout.n_blocks, layout.blocksize, _p(qmap1),
+                       0.0, 0.0, 0.0, 0.0, _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_lion8bit_step_grouped(a, _p(block_group), rows, len(groups), stream_ptr()), "qfx_lion8bit_step_grouped")
+
+
 def sfadamw_schedule(k, lr, beta2, warmup_steps, r, weight_lr_power, lr_max, weight_sum):
     """The group scalars of Schedule-Free AdamW's step k (counted from 0), in Python doubles as schedulefree.AdamWScheduleFree forms
     them: (lr_t, bias_corr2, ckp1, lr_max, weight_sum) with the two running values updated."""

@@ -7,9 +7,13 @@ class takes the constructor keywords of the class it stands in for and holds the
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
 the two ways of driving the model and with the original packages'.
 
-`params` must be exactly the adapter parameters of ONE model, in one group.  The loop has clipped already
+`params` must be exactly the adapter parameters of ONE model: a plain list, or torch's list of group dicts whose union is that set,
+each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit and PagedLion8bit step several groups
+in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); Prodigy, Adafactor,
+Muon and AdamWScheduleFree refuse a second group.  loraplus_param_groups builds the two LoRA+ groups.  The loop has clipped already
 (accelerator.clip_grad_norm_, base_trainer.py:449-455), so step() launches without the fused clip; lr, betas, eps, weight_decay and
-momentum are read from param_groups[0] at every step (schedulers write there).  step() never synchronises with the host.
+the family's own fields are read from every param_groups[k] at every step (schedulers write there).  step() never synchronises
+with the host.  add_param_group is refused after the first step.
 """
 from __future__ import annotations
 
@@ -18,31 +22,55 @@ import torch
 from .trainer import optim_state as OS
 from .trainer.optim_config import optimizer_kwargs_from_config
 
-__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree"]
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree",
+           "loraplus_param_groups"]
 
 
 def _find_store(param_groups):
-    """The LoraStore whose parameters are exactly those of the one group; ValueError naming the first offender otherwise."""
-    if len(param_groups) != 1:
-        raise ValueError(f"{len(param_groups)} parameter groups: the fused step runs over one model's adapter parameters in ONE group "
-                         "(parameter group 1 is the first offender)")
-    params, store = param_groups[0]["params"], None
-    for i, p in enumerate(params):
-        ref = getattr(p, "_lora_store", None)
-        st = ref() if ref is not None else None
-        if st is None:
-            raise ValueError(f"parameter {i} (shape {tuple(p.shape)}) is not an adapter parameter of a qflux_amd model")
-        if store is not None and st is not store:
-            raise ValueError(f"parameter {i} (shape {tuple(p.shape)}) belongs to another model than parameter 0: one optimizer steps one "
-                             "model's adapters")
-        store = st
+    """The LoraStore whose adapter parameters are exactly the union of the groups, each in exactly one group; ValueError naming the
+    offending group and the first offender otherwise."""
+    store, have = None, {}
+    for k, group in enumerate(param_groups):
+        for i, p in enumerate(group["params"]):
+            where = f"parameter {i} (shape {tuple(p.shape)})" + (f" of parameter group {k}" if len(param_groups) > 1 else "")
+            ref = getattr(p, "_lora_store", None)
+            st = ref() if ref is not None else None
+            if st is None:
+                raise ValueError(f"{where} is not an adapter parameter of a qflux_amd model")
+            if store is not None and st is not store:
+                raise ValueError(f"{where} belongs to another model than parameter 0: one optimizer steps one model's adapters")
+            if id(p) in have:
+                raise ValueError(f"{where} is in parameter group {have[id(p)]} already: every adapter parameter belongs to exactly one group")
+            store, have[id(p)] = st, k
     if store is None:
         raise ValueError("no parameters")
-    have = {id(p) for p in params}
     for n, p in store.params():
         if id(p) not in have:
-            raise ValueError(f"adapter parameter {n!r} of the model is missing: stepping a subset of the adapter set is not supported")
+            raise ValueError(f"adapter parameter {n!r} of the model is missing" + (f" from all {len(param_groups)} parameter groups"
+                             if len(param_groups) > 1 else "") + ": stepping a subset of the adapter set is not supported")
     return store
+
+
+def _as_groups(params):
+    """torch's reading of `params`: a list of group dicts as it is, anything else one group."""
+    params = list(params)
+    return params if params and isinstance(params[0], dict) else [{"params": params}]
+
+
+def loraplus_param_groups(model, lr, loraplus_lr_ratio, weight_decay=0.0, b_weight_decay=None):
+    """The two LoRA+ parameter groups (Hayou et al. 2024) of `model`'s adapters, ready for any class here that takes groups: group 0 =
+    every lora_A with `lr` and `weight_decay`, group 1 = every lora_B with lr * loraplus_lr_ratio and b_weight_decay (None: the same
+    weight_decay; 0.0 is the common "no decay on lora_B").  Modelled on peft.optimizers.create_loraplus_optimizer and kohya's
+    loraplus_lr_ratio; peft's own grouping (it also splits embeddings and the decay / no-decay names) is not verified against the
+    package, which is not a dependency."""
+    if not loraplus_lr_ratio > 0:
+        raise ValueError(f"loraplus_lr_ratio must be positive, not {loraplus_lr_ratio}")
+    named = [(n, p) for n, p in model.named_parameters() if "lora_" in n]
+    a, b = [p for n, p in named if "lora_A" in n], [p for n, p in named if "lora_B" in n]
+    if not a or not b or len(a) + len(b) != len(named):
+        raise ValueError(f"loraplus_param_groups: {len(a)} lora_A and {len(b)} lora_B parameters among {len(named)} adapter parameters")
+    return [{"params": a, "lr": lr, "weight_decay": weight_decay},
+            {"params": b, "lr": lr * loraplus_lr_ratio, "weight_decay": weight_decay if b_weight_decay is None else b_weight_decay}]
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -55,10 +83,22 @@ class _FlatOptimizer(torch.optim.Optimizer):
                                                                       dict(kw.get("optimizer_args") or {}, **(_own_args or {})) or None)
         # the family's own group fields (SGD's momentum, Prodigy's init_args) are visible in the group, as in the package's
         own = {n: v for n, v in self._args.items() if n in self._cls.save(None, [], 0, self._args)[0]}
+        params = _as_groups(params)
+        _find_store(params)              # before torch's own checks: an overlap is named with its group
+        self._cls.check_groups(len(params))
         super().__init__(params, dict(dict(lr=kw["lr"], betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-8), weight_decay=wd), **own))
         self._raw_store = _find_store(self.param_groups)
         self._opt_state = None
         self._step_count_fused = 0
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_step_count_fused", 0) or getattr(self, "_opt_state", None) is not None:
+            raise RuntimeError("add_param_group after the first step (or a loaded state): the fused step's group map and state belong "
+                               "to the groups the optimizer was built with; build a new optimizer and load this one's state_dict")
+        super().add_param_group(param_group)
+        if hasattr(self, "_raw_store"):      # after the constructor: the groups must still be one model's adapter set
+            self._cls.check_groups(len(self.param_groups))
+            _find_store(self.param_groups)
 
     def _store(self):
         """The model's store through its `lora_store` property: packed on the model's current device, gradient views attached (the
@@ -72,9 +112,18 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 self._args[n] = g[n]
         return g
 
+    def _members(self, st):
+        """One tuple of store-entry indices per group, in the group's parameter order; None with one group."""
+        if len(self.param_groups) == 1:
+            return None
+        at = {id(p): i for i, (_, p, _, _) in enumerate(st.entries)}
+        return tuple(tuple(at[id(p)] for p in g["params"]) for g in self.param_groups)
+
+    def _rows(self):
+        return self.param_groups if len(self.param_groups) > 1 else None
+
     def _ensure_state(self, st):
-        if self._opt_state is None or self._opt_state.key != self._cls.layout_key(st, self._args):
-            self._opt_state = self._cls(st, self._args)      # zeroed state of the current layout
+        self._opt_state = OS.ensure_state(self._cls, self._opt_state, st, self._args, self._members(st))
         return self._opt_state
 
     @torch.no_grad()
@@ -89,18 +138,21 @@ class _FlatOptimizer(torch.optim.Optimizer):
         st.ensure_grads()
         self._ensure_state(st)
         self._step_count_fused += 1
-        self._opt_state.step(st, g["lr"], g["betas"], g["eps"], g["weight_decay"], self._step_count_fused, None, 0.0, 1.0, self._args)
+        rows = self._rows()
+        self._opt_state.step(st, g["lr"], g["betas"], g["eps"], g["weight_decay"], self._step_count_fused, None, 0.0, 1.0, self._args,
+                             **({"groups": rows} if rows else {}))
         return loss
 
     def state_dict(self):
-        g = self._group()
-        return OS.state_dict(self._cls, self._opt_state, self._store(), self._step_count_fused, self._args, g["lr"], g["betas"], g["eps"],
-                             g["weight_decay"])
+        g, st = self._group(), self._store()
+        return OS.state_dict(self._cls, self._opt_state, st, self._step_count_fused, self._args, g["lr"], g["betas"], g["eps"],
+                             g["weight_decay"], groups=self._rows(), members=self._members(st))
 
     def load_state_dict(self, state_dict):
-        g = self._group()
+        g, st = self._group(), self._store()
         hyper = {n: g[n] for n in ("lr", "betas", "eps", "weight_decay")}
-        self._opt_state, self._step_count_fused = OS.load_state_dict(self._cls, self._store(), state_dict, self._args, hyper)
+        self._opt_state, self._step_count_fused = OS.load_state_dict(self._cls, st, state_dict, self._args, hyper, groups=self._rows(),
+                                                                     members=self._members(st))
         g.update(hyper)
         g.update({n: v for n, v in self._args.items() if n in g})
 

@@ -10,7 +10,13 @@ QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of the
   cls.save(state, entries, step, args) -> (extra param-group fields, per-parameter state); state may be None (no step yet)
   cls.load(store, sd, args) -> (state or None, highest per-parameter step the family reads, else 0)
   sync_host()                    after the buffers were received from another rank: host-side copies of device scalars follow them
-  swap(store, beta1, train)      the parameter buffer between its train and eval form; a no-op for every family but the schedule-free"""
+  swap(store, beta1, train)      the parameter buffer between its train and eval form; a no-op for every family but the schedule-free
+Parameter groups (torch.optim's second axis; LoRA+): `members` = one tuple of store-entry indices per group, in the group's parameter
+order, each entry in exactly one group; None (or one group) is the single-group case and changes nothing.  The families with
+GROUPED = True step several groups in their ONE launch (the *_grouped kernels of include/qfx.h): regroup() builds the one-byte map
+from the layout to the group once per layout and grouping and keeps it with the state, step(..., groups=[row per group]) reads lr /
+betas / eps / weight_decay (and the family's own fields) from each row.  Every other family refuses a second group.  The grouping is
+part of layout_key; a change of the grouping alone rebuilds the map, not the moments (ensure_state)."""
 from __future__ import annotations
 
 import torch
@@ -26,12 +32,85 @@ def _out(t, off, k, shape=None):
     return (t if shape is None else t.view(shape)).detach().cpu().clone()
 
 
+class ParamGroupsNotImplemented(NotImplementedError, ValueError):
+    """A second parameter group given to a family whose fused step has one.  Also a ValueError: that is what the constructors
+    raised for any second group before the grouped kernels existed."""
+
+
+def norm_members(members):
+    """None for one group (the ungrouped kernels, today's keys and files), else a tuple of tuples of store-entry indices."""
+    if members is None or len(members) <= 1:
+        return None
+    return tuple(tuple(int(i) for i in m) for m in members)
+
+
+def _members_key(members):
+    return () if members is None else (("groups", members),)
+
+
+def members_assign(members, n_entries):
+    """assign[i] = the group of store entry i; every entry must be in exactly one group."""
+    assign = [None] * n_entries
+    for k, m in enumerate(members):
+        for i in m:
+            if not 0 <= i < n_entries or assign[i] is not None:
+                raise ValueError(f"parameter group {k}: store entry {i} is " + ("in more than one group" if 0 <= i < n_entries else "unknown"))
+            assign[i] = k
+    if None in assign:
+        raise ValueError(f"store entry {assign.index(None)} is in no parameter group")
+    return assign
+
+
+def ensure_state(cls, state, store, args, members=None):
+    """The state object for the store's current layout and the grouping: zeroed state when the layout changed (or there is none
+    yet), the same moments with a rebuilt group map when only the grouping did."""
+    if state is None or state.key != cls.layout_key(store, args, members):
+        if state is None or state.base_key != cls.layout_key(store, args):
+            state = cls(store, args)
+        state.regroup(store, members)
+    return state
+
+
 class FlatState:
     LAYOUT_ARGS = ()
     DEFAULTS = {}               # the family's optimizer_args and their defaults; empty: the family takes none
 
+    GROUPED = False             # the family's one launch reads per-group hyperparameters
+    FAMILY = None               # how a refusal names the family
+
     def __init__(self, store, args):
-        self.key = self.layout_key(store, args)
+        self.base_key = self.layout_key(store, args)
+        self.members = self.group_map = None
+
+    @property
+    def key(self):
+        return self.base_key + _members_key(self.members)
+
+    def regroup(self, store, members):
+        """Take the grouping `members` (None: one group): a refusal for a family without grouped kernels, else the one-byte map of
+        the layout (build_group_map: range-checked on the host, uploaded once).  The moments stay as they are."""
+        members = norm_members(members)
+        if members is not None:
+            self.check_groups(len(members))
+            assign = members_assign(members, len(store.entries))
+            self.group_map = self.build_group_map(store, assign, len(members))
+        else:
+            self.group_map = None
+        self.members = members
+
+    @classmethod
+    def check_groups(cls, n_groups):
+        if n_groups > 1 and not cls.GROUPED:
+            raise ParamGroupsNotImplemented(f"{cls.FAMILY}: {n_groups} parameter groups -- the fused {cls.FAMILY} step runs over ONE group (its "
+                                      "global estimates / per-matrix steps are defined per group in the original package; the grouped "
+                                      "kernels cover AdamW / Adam, SGD, Lion and the blockwise 8-bit families)")
+        if n_groups > ops.MAX_PARAM_GROUPS:
+            raise ValueError(f"{n_groups} parameter groups: the grouped kernels take at most {ops.MAX_PARAM_GROUPS}")
+
+    def build_group_map(self, store, assign, n_groups):
+        """fp32 families: the group of every 64-element tile of the flat buffers."""
+        return ops.tile_group_map([(off, k) for _, _, off, k in store.entries], assign, n_groups, numel=store.pflat.numel(),
+                                  device=store.pflat.device)
 
     @staticmethod
     def validate(args):
@@ -67,7 +146,11 @@ class FlatState:
         return e[n]
 
     @classmethod
-    def layout_key(cls, store, args):
+    def layout_key(cls, store, args, members=None):
+        return cls._base_key(store, args) + _members_key(norm_members(members))
+
+    @classmethod
+    def _base_key(cls, store, args):
         return (tuple((off, k) for _, _, off, k in store.entries), str(store.pflat.device)) + tuple(int(args[n]) for n in cls.LAYOUT_ARGS)
 
     @classmethod
@@ -90,13 +173,18 @@ class FlatState:
 class AdamWState(FlatState):
     """exp_avg / exp_avg_sq in fp32, indexed like pflat (also the "adam" / "adam8bit" aliases)."""
     NAMES = ("m", "v")
+    GROUPED, FAMILY = True, "AdamW"
 
     def __init__(self, store, args):
         super().__init__(store, args)
         self.m = torch.zeros_like(store.pflat)
         self.v = torch.zeros_like(store.pflat)
 
-    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        if groups is not None and len(groups) > 1:
+            rows = [(r["lr"], r["betas"][0], r["betas"][1], r["eps"], r["weight_decay"]) for r in groups]
+            return ops.adamw_step_grouped(store.pflat, store.gflat, self.m, self.v, self.group_map, rows, step, gnorm_sq=gnorm_sq,
+                                          max_norm=max_norm, grad_scale=grad_scale)
         ops.adamw_step(store.pflat, store.gflat, self.m, self.v, lr, betas[0], betas[1], eps, weight_decay, step, gnorm_sq=gnorm_sq,
                        max_norm=max_norm, grad_scale=grad_scale)
 
@@ -124,6 +212,7 @@ class ProdigyState(AdamWState):
     """AdamW's two moments plus s, p0 and the fp64 device scalars d, d_max, d_numerator, d_denom, d_hat, k (pstate)."""
     NAMES = ("m", "v", "ps", "p0", "pstate")
     GROUP = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "k")
+    GROUPED, FAMILY = False, "Prodigy"
     DEFAULTS = dict(beta3=None, decouple=True, use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
                     growth_rate=float("inf"))
 
@@ -188,6 +277,7 @@ class _BlockwiseBase(FlatState):
     DEFAULTS = dict(min_8bit_size=4096, blocksize=256)
     MOMENTS = 0
     F32 = ("m32", "v32")
+    GROUPED = True
 
     @staticmethod
     def validate(args, optimizer="blockwise 8-bit state"):
@@ -210,6 +300,10 @@ class _BlockwiseBase(FlatState):
             setattr(self, f"absmax{j}", torch.zeros(max(1, self.layout.n_absmax), dtype=torch.float32, device=dev))     # absmax 0 (decodes to 0)
             setattr(self, f32, torch.zeros(max(1, self.layout.n_fp32), dtype=torch.float32, device=dev))
             setattr(self, f"qmap{j}", A8.dynamic_map(j == 1).to(dev))
+
+    def build_group_map(self, store, assign, n_groups):
+        """The group of every block-table entry (an entry never leaves its tensor)."""
+        return ops.block_group_map(self.layout, assign, n_groups, device=store.pflat.device)
 
     def param_state(self, i, shape, step):
         """bnb's per-parameter state of entry i (CPU tensors)."""
@@ -265,8 +359,14 @@ class _BlockwiseBase(FlatState):
 class BlockwiseState(_BlockwiseBase):
     """bitsandbytes' blockwise 8-bit Adam / AdamW: two moments (q1, q2, absmax1, absmax2, m32, v32, qmap1, qmap2)."""
     MOMENTS = 2
+    FAMILY = "Adam8bit"
 
-    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        if groups is not None and len(groups) > 1:
+            rows = [(r["lr"], r["betas"][0], r["betas"][1], r["eps"], r["weight_decay"]) for r in groups]
+            return ops.adam8bit_step_grouped(store.pflat, store.gflat, self.q1, self.q2, self.absmax1, self.absmax2, self.m32, self.v32,
+                                             self.layout, self.qmap1, self.qmap2, self.group_map, rows, step, gnorm_sq=gnorm_sq,
+                                             max_norm=max_norm, grad_scale=grad_scale)
         ops.adam8bit_step(store.pflat, store.gflat, self.q1, self.q2, self.absmax1, self.absmax2, self.m32, self.v32, self.layout,
                           self.qmap1, self.qmap2, lr, betas, eps, weight_decay, step, gnorm_sq=gnorm_sq, max_norm=max_norm,
                           grad_scale=grad_scale)
@@ -277,6 +377,7 @@ class SgdState(FlatState):
     buffer (torch: buf = the decayed gradient, no dampening); a state that was loaded or received from another rank has stepped."""
     NAMES = ("buf",)
     DEFAULTS = dict(momentum=0.0, dampening=0.0, nesterov=False)
+    GROUPED, FAMILY = True, "SGD"
 
     def __init__(self, store, args):
         super().__init__(store, args)
@@ -284,8 +385,8 @@ class SgdState(FlatState):
         self.first = True
 
     @classmethod
-    def layout_key(cls, store, args):
-        return super().layout_key(store, args) + (args["momentum"] != 0,)
+    def _base_key(cls, store, args):
+        return super()._base_key(store, args) + (args["momentum"] != 0,)
 
     @classmethod
     def names(cls, args):
@@ -303,9 +404,17 @@ class SgdState(FlatState):
         self.first = False            # listed for a broadcast or a replica check: the state of a run that has stepped
         return [("buf", self.buf)] if self.buf is not None else []
 
-    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
-        ops.sgd_step(store.pflat, store.gflat, self.buf, lr, args["momentum"], args["dampening"], weight_decay, args["nesterov"],
-                     first=self.first, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        if groups is not None and len(groups) > 1:
+            rows = [(r["lr"], r.get("momentum", args["momentum"]), r.get("dampening", args["dampening"]), r["weight_decay"],
+                     r.get("nesterov", args["nesterov"])) for r in groups]
+            if self.buf is None and any(r[1] != 0 for r in rows):      # the state was shaped by a group without momentum
+                self.buf = torch.zeros_like(store.pflat)
+            ops.sgd_step_grouped(store.pflat, store.gflat, self.buf, self.group_map, rows, first=self.first, gnorm_sq=gnorm_sq,
+                                 max_norm=max_norm, grad_scale=grad_scale)
+        else:
+            ops.sgd_step(store.pflat, store.gflat, self.buf, lr, args["momentum"], args["dampening"], weight_decay, args["nesterov"],
+                         first=self.first, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
         self.first = False
 
     @classmethod
@@ -338,6 +447,7 @@ class AdafactorState(FlatState):
     step, and exp_avg indexed like pflat when beta1 is given.  Zeros are the package's initial state.  `eps` is the package's pair
     (added to the squared gradient, floor of the parameter scale) and lives in the optimizer_args: the train step's own eps is unused."""
     NAMES = ("row", "col", "v", "rms", "m")
+    FAMILY = "Adafactor"
     DEFAULTS = dict(eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, scale_parameter=True, relative_step=True,
                     warmup_init=False)
 
@@ -350,8 +460,8 @@ class AdafactorState(FlatState):
         self.m = torch.zeros_like(store.pflat) if args["beta1"] is not None else None
 
     @classmethod
-    def layout_key(cls, store, args):
-        return super().layout_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries), args["beta1"] is not None)
+    def _base_key(cls, store, args):
+        return super()._base_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries), args["beta1"] is not None)
 
     @classmethod
     def names(cls, args):
@@ -432,12 +542,17 @@ class AdafactorState(FlatState):
 class LionState(FlatState):
     """lion_pytorch.Lion / bitsandbytes.optim.Lion: the one moment exp_avg in fp32, indexed like pflat.  eps is unused."""
     NAMES = ("exp_avg",)
+    GROUPED, FAMILY = True, "Lion"
 
     def __init__(self, store, args):
         super().__init__(store, args)
         self.exp_avg = torch.zeros_like(store.pflat)
 
-    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        if groups is not None and len(groups) > 1:
+            rows = [(r["lr"], r["betas"][0], r["betas"][1], r["weight_decay"]) for r in groups]
+            return ops.lion_step_grouped(store.pflat, store.gflat, self.exp_avg, self.group_map, rows, gnorm_sq=gnorm_sq,
+                                         max_norm=max_norm, grad_scale=grad_scale)
         ops.lion_step(store.pflat, store.gflat, self.exp_avg, lr, betas[0], betas[1], weight_decay, gnorm_sq=gnorm_sq, max_norm=max_norm,
                       grad_scale=grad_scale)
 
@@ -467,8 +582,13 @@ class LionState(FlatState):
 class LionBlockwiseState(_BlockwiseBase):
     """bitsandbytes.optim.Lion8bit / PagedLion8bit: ONE moment (q1, absmax1, m32, qmap1) over the same block table."""
     MOMENTS = 1
+    FAMILY = "Lion8bit"
 
-    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        if groups is not None and len(groups) > 1:
+            rows = [(r["lr"], r["betas"][0], r["betas"][1], r["weight_decay"]) for r in groups]
+            return ops.lion8bit_step_grouped(store.pflat, store.gflat, self.q1, self.absmax1, self.m32, self.layout, self.qmap1,
+                                             self.group_map, rows, gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
         ops.lion8bit_step(store.pflat, store.gflat, self.q1, self.absmax1, self.m32, self.layout, self.qmap1, lr, betas, weight_decay,
                           gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
 
@@ -479,6 +599,7 @@ class MuonState(FlatState):
     `eps` is Muon's own (the floor of the Frobenius norm, 1e-7) and lives in the optimizer_args: the train step's Adam eps is unused,
     and so are betas.  `first` marks a state that has not stepped (torch keeps no state before the first step)."""
     NAMES = ("buf",)
+    FAMILY = "Muon"
     DEFAULTS = dict(momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None)
 
     def __init__(self, store, args):
@@ -490,8 +611,8 @@ class MuonState(FlatState):
         self.first = True
 
     @classmethod
-    def layout_key(cls, store, args):
-        return super().layout_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries), args["adjust_lr_fn"])
+    def _base_key(cls, store, args):
+        return super()._base_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries), args["adjust_lr_fn"])
 
     @staticmethod
     def validate(args):
@@ -554,6 +675,7 @@ class ScheduleFreeAdamWState(FlatState):
     or a replica check and read back by sync_host() on the ranks that received it.  k == 0 marks a state that has not stepped: its
     first step takes z = y and v = 0 in the kernel (the package creates both there), and a swap before it moves nothing."""
     NAMES = ("z", "v", "sched")
+    FAMILY = "AdamWScheduleFree"
     DEFAULTS = dict(warmup_steps=0, r=0.0, weight_lr_power=2.0)
     SCHED = ("k", "weight_sum", "lr_max", "train_mode", "scheduled_lr")
     EVAL_STEP = ("optimizer step in eval mode: the parameters hold the averaged point x, not the point y the gradient belongs to; "
@@ -708,22 +830,55 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     return alias, optimizer, cls, weight_decay, args
 
 
-def state_dict(cls, state, store, step, args, lr, betas, eps, weight_decay):
+def state_dict(cls, state, store, step, args, lr, betas, eps, weight_decay, groups=None, members=None):
     """{"state": {i: per-parameter state}, "param_groups": [...], "global_step"} with one entry per LoRA parameter in
-    named_parameters() order (what accelerate's optimizer.bin holds for the reference), in the family's own layout."""
+    named_parameters() order (what accelerate's optimizer.bin holds for the reference), in the family's own layout.
+    Several groups (groups = their rows, members = their store entries): torch's format -- one dict per group with its own fields,
+    the parameters numbered consecutively through the groups in order, "state" keyed by those numbers."""
     extra, per = cls.save(state, store.entries, step, args)
-    group = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
-    group.update(extra, params=list(range(len(store.entries))))       # a family's own field wins (Adafactor's eps is its pair)
-    return {"state": per, "param_groups": [group], "global_step": step}
+    members = norm_members(members)
+    if members is None:
+        group = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+        group.update(extra, params=list(range(len(store.entries))))       # a family's own field wins (Adafactor's eps is its pair)
+        return {"state": per, "param_groups": [group], "global_step": step}
+    number, out = {}, []
+    for row, m in zip(groups, members):
+        group = dict(lr=row["lr"], betas=tuple(row["betas"]), eps=row["eps"], weight_decay=row["weight_decay"])
+        group.update(extra)
+        group.update({n: row[n] for n in list(extra) + ["initial_lr"] if n in row}, params=list(range(len(number), len(number) + len(m))))
+        number.update({i: len(number) + j for j, i in enumerate(m)})
+        out.append(group)
+    return {"state": dict(sorted(((number[i], e) for i, e in per.items()), key=lambda t: t[0])), "param_groups": out, "global_step": step}
 
 
-def load_state_dict(cls, store, sd, args, hyper):
+def _check_file_groups(sd, members, n_entries):
+    """torch.optim.Optimizer.load_state_dict's two checks, with its messages (one group: the count alone, as before groups existed
+    a file's parameter list was never compared)."""
+    if len(sd["param_groups"]) != (len(members) if members is not None else 1):
+        raise ValueError("loaded state dict has a different number of parameter groups")
+    if members is not None and any(len(g["params"]) != len(m) for g, m in zip(sd["param_groups"], members)):
+        raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+
+
+def load_state_dict(cls, store, sd, args, hyper, groups=None, members=None):
     """Inverse of state_dict: updates args and hyper (lr, betas, eps, weight_decay; a family without betas / eps, such as
-    torch.optim.SGD's or transformers' Adafactor's own file, keeps the current values) in place and returns (state or None, step count)."""
+    torch.optim.SGD's or transformers' Adafactor's own file, keeps the current values) in place and returns (state or None, step count).
+    Several groups: the file must have the optimizer's group count and group sizes (torch's ValueError otherwise); its numbers map
+    back to store entries through the groups' lists by position, every row of `groups` takes its file group's fields, and hyper
+    those of group 0."""
+    members = norm_members(members)
+    _check_file_groups(sd, members, len(store.entries))
+    if members is not None:
+        entry = {n: i for g, m in zip(sd["param_groups"], members) for n, i in zip(g["params"], m)}
+        for row, g in zip(groups, sd["param_groups"]):
+            row.update({n: (tuple(g[n]) if n == "betas" else g[n]) for n in row if n in g and n != "params"})
+        sd = dict(sd, state={entry[n]: e for n, e in sd["state"].items()})
     g = sd["param_groups"][0]
     eps = g.get("eps", hyper["eps"])
     if isinstance(eps, (tuple, list)):      # Adafactor's pair is one of its optimizer_args (cls.load reads it), not the scalar eps
         eps = hyper["eps"]
     hyper.update(lr=g["lr"], betas=tuple(g.get("betas", hyper["betas"])), eps=eps, weight_decay=g["weight_decay"])
     state, step = cls.load(store, sd, args)
+    if state is not None:
+        state.regroup(store, members)
     return state, max(int(sd.get("global_step", g.get("k", 0))), step)    # a package's own file: its group's count k, if any

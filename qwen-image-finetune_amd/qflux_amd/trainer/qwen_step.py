@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import re
 
 import torch
 import torch.distributed as dist
@@ -47,11 +48,18 @@ def map_mask_to_latent(image_mask: torch.Tensor) -> torch.Tensor:
 class QwenLoraTrainStep:
     def __init__(self, dit, lr=1e-4, betas=None, eps=1e-8, weight_decay=None, max_grad_norm=1.0,
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
-                 bucket_mb=24.0, optimizer="adamw", optimizer_args=None):
+                 bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None):
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
         without it.
+        param_groups: parameter groups by name -- a list of dicts, each a "match" regex (re.search on the adapter parameter's name)
+        plus any of lr, weight_decay, betas, eps; the first matching rule wins, unmatched parameters form the default group with
+        this constructor's values (the last group).  The families with grouped kernels (optim_state: AdamW / Adam, SGD, Lion, the
+        blockwise 8-bit ones) step all groups in their one launch; every other family refuses a second group.  An lr schedule
+        written to `self.lr` scales every group's lr by the same factor self.lr / (the constructor's lr), as torch's schedulers do
+        with the groups' initial_lr.  loraplus_lr_ratio: shorthand for the two LoRA+ groups of
+        qflux_amd.optim.loraplus_param_groups -- lora_A at lr, lora_B at lr * ratio.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
@@ -66,6 +74,15 @@ class QwenLoraTrainStep:
         self.dit = dit
         betas = OS.default_betas(self.optimizer) if betas is None else tuple(betas)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        if loraplus_lr_ratio is not None:
+            if param_groups is not None:
+                raise ValueError("give either param_groups or loraplus_lr_ratio")
+            if not loraplus_lr_ratio > 0:
+                raise ValueError(f"loraplus_lr_ratio must be positive, not {loraplus_lr_ratio}")
+            param_groups = [{"match": r"lora_A", "lr": lr}, {"match": r"lora_B", "lr": lr * loraplus_lr_ratio}]
+        self._base_lr = lr
+        self.group_rules = self._check_rules(param_groups)
+        self._grouping = None       # (adapter names, rows, members) of the store layout the rules were last applied to
         self.max_grad_norm = max_grad_norm
         self.weight_dtype = weight_dtype
         self.group = process_group
@@ -266,10 +283,56 @@ class QwenLoraTrainStep:
             return 1.0 / self.world
         return 1.0
 
+    # ------------------------------------------------------------------ parameter groups
+    _RULE_FIELDS = ("lr", "weight_decay", "betas", "eps")
+
+    def _check_rules(self, rules):
+        if rules is None:
+            return None
+        out = []
+        for k, r in enumerate(rules):
+            unknown = set(r) - {"match", *self._RULE_FIELDS}
+            if "match" not in r or unknown:
+                raise ValueError(f"param_groups[{k}]: a rule is a dict with a 'match' regex and any of {self._RULE_FIELDS}" +
+                                 (f", not {sorted(unknown)}" if unknown else ""))
+            out.append(dict(r, match=re.compile(r["match"]), **({"betas": tuple(r["betas"])} if "betas" in r else {})))
+        self._opt_cls.check_groups(len(out))      # a second group is refused here by the families without grouped kernels
+        return out
+
+    def param_groups_of(self, store):
+        """(rows, members) of the rules over the store's adapter names: one row dict (lr, betas, eps, weight_decay) and one tuple of
+        store-entry indices per non-empty group -- the rules' groups in rule order, then the default group.  (None, None) without
+        rules or when everything lands in one group."""
+        if self.group_rules is None:
+            return None, None
+        names = tuple(n for n, _, _, _ in store.entries)
+        if self._grouping is None or self._grouping[0] != names:
+            base = dict(lr=self._base_lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+            buckets = [[] for _ in range(len(self.group_rules) + 1)]
+            for i, n in enumerate(names):
+                buckets[next((k for k, r in enumerate(self.group_rules) if r["match"].search(n)), len(self.group_rules))].append(i)
+            rows = [dict(base, **{f: r[f] for f in self._RULE_FIELDS if f in r}) for r in self.group_rules] + [base]
+            for k, (r, b) in enumerate(zip(self.group_rules, buckets)):
+                if not b:
+                    raise ValueError(f"param_groups[{k}]: {r['match'].pattern!r} matches no adapter parameter")
+            keep = [k for k, b in enumerate(buckets) if b]
+            self._opt_cls.check_groups(len(keep))
+            self._grouping = (names, [rows[k] for k in keep], tuple(tuple(buckets[k]) for k in keep))
+        _, rows, members = self._grouping
+        return (rows, members) if len(rows) > 1 else (None, None)
+
+    def _scheduled_rows(self, rows, initial=False):
+        """The groups' rows with the schedule's factor self.lr / (constructor lr) on every lr; initial: with the unscheduled lr as
+        torch's schedulers keep it in a group, "initial_lr" (a checkpoint restores the factor from it)."""
+        if rows is None:
+            return None
+        f = self.lr / self._base_lr if self.lr != self._base_lr else 1.0
+        return [dict(r, lr=r["lr"] * f if f != 1.0 else r["lr"], **({"initial_lr": r["lr"]} if initial else {})) for r in rows]
+
     def _ensure_opt_state(self):
         st = self.dit.lora_store
-        if self.opt_state is None or self.opt_state.key != self._opt_cls.layout_key(st, self.optimizer_args):
-            self.opt_state = self._opt_cls(st, self.optimizer_args)      # zeroed state of the current layout
+        _, members = self.param_groups_of(st)
+        self.opt_state = OS.ensure_state(self._opt_cls, self.opt_state, st, self.optimizer_args, members)
         return st
 
     # ------------------------------------------------------------------ train / eval form of the adapter weights
@@ -314,8 +377,9 @@ class QwenLoraTrainStep:
             self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
             self._gparts = torch.zeros(1024, dtype=torch.float32, device=st.pflat.device)
         ops.sumsq_det(st.gflat, self._gnorm, self._gparts)     # fixed reduction order: every replica computes the same clip coefficient
+        rows, _ = self.param_groups_of(st)
         self.opt_state.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm,
-                            grad_scale, self.optimizer_args)
+                            grad_scale, self.optimizer_args, **({"groups": self._scheduled_rows(rows)} if rows else {}))
 
     @property
     def _m(self):
@@ -341,13 +405,28 @@ class QwenLoraTrainStep:
         """{"state": {i: per-parameter state}, "param_groups": [...]} with one entry per LoRA parameter in named_parameters() order
         (what accelerate's optimizer.bin holds for the reference), in the optimizer's own layout: torch.optim.AdamW's, prodigyopt's
         or bitsandbytes' (optim_state)."""
-        return OS.state_dict(self._opt_cls, self.opt_state, self.dit.lora_store, self.global_step, self.optimizer_args, self.lr, self.betas,
-                             self.eps, self.weight_decay)
+        st = self.dit.lora_store
+        rows, members = self.param_groups_of(st)
+        return OS.state_dict(self._opt_cls, self.opt_state, st, self.global_step, self.optimizer_args, self.lr, self.betas,
+                             self.eps, self.weight_decay, groups=self._scheduled_rows(rows, initial=True), members=members)
 
     def load_state_dict(self, sd):
+        """With param_groups the file must hold the same groups (torch's ValueError otherwise): every group takes the file's betas,
+        eps and weight_decay, and its lr as the unscheduled one -- the file's "initial_lr" where it has one (the schedule's factor
+        lr / initial_lr then comes back into self.lr), else its lr (factor 1)."""
+        st = self.dit.lora_store
+        rows, members = self.param_groups_of(st)
         hyper = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
-        self.opt_state, self.global_step = OS.load_state_dict(self._opt_cls, self.dit.lora_store, sd, self.optimizer_args, hyper)
-        self.lr, self.betas, self.eps, self.weight_decay = hyper["lr"], hyper["betas"], hyper["eps"], hyper["weight_decay"]
+        file_rows = None if rows is None else [dict(r, initial_lr=None) for r in rows]
+        self.opt_state, self.global_step = OS.load_state_dict(self._opt_cls, st, sd, self.optimizer_args, hyper, groups=file_rows,
+                                                              members=members)
+        if rows is None:
+            self.lr, self.betas, self.eps, self.weight_decay = hyper["lr"], hyper["betas"], hyper["eps"], hyper["weight_decay"]
+            return
+        for r, f in zip(rows, file_rows):
+            r.update(betas=f["betas"], eps=f["eps"], weight_decay=f["weight_decay"], lr=f["initial_lr"] if f["initial_lr"] else f["lr"])
+        f = file_rows[0]
+        self.lr = self._base_lr * (f["lr"] / f["initial_lr"]) if f["initial_lr"] and f["lr"] != f["initial_lr"] else self._base_lr
 
     def save_checkpoint(self, save_dir, extra_state=None):
         """checkpoint-<e>-<step> folder of the reference (base_trainer.py:827-875): pytorch_lora_weights.safetensors (diffusers
@@ -406,8 +485,7 @@ class QwenLoraTrainStep:
         # moments the others do not have)
         if have:
             self.optimizer_args.update(zip(cls.LAYOUT_ARGS, ints))
-            if self.opt_state is None or self.opt_state.key != cls.layout_key(st, self.optimizer_args):
-                self.opt_state = cls(st, self.optimizer_args)
+            self.opt_state = OS.ensure_state(cls, self.opt_state, st, self.optimizer_args, self.param_groups_of(st)[1])
         else:
             self.opt_state = None
         for _, t in self._state_buffers():
