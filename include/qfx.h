@@ -808,6 +808,28 @@ int qfx_debug_tr_read(const uint16_t* in, uint16_t* out, void* stream);
 int qfx_abi_version(void);
 const char* qfx_build_arch(void);
 
+/* ---- EMA of the adapter weights (diffusers.training_utils.EMAModel, every diffusers training script's --use_ema): up to
+ * QFX_EMA_MAX_SHADOWS fp32 shadow buffers over the flat LoRA buffer p, each with its own rate.  The caller forms the decay of the
+ * step on the host (EMAModel.get_decay: qflux_amd.ema.get_decay) and passes one_minus_decay = float32(1 - decay).
+ * qfx_ema_update: ONE launch, for k < n_shadows
+ *   s_k[i] = s_k[i] - omd_k * (s_k[i] - p[i])      three separately rounded fp32 operations, in this order
+ * (EMAModel.step's `s.sub_(one_minus_decay * (s - p))`; never contracted into an FMA); p is read once for all shadows and never
+ * written.  omd == 1 is not special: the result is s - (s - p), what the package computes.  4 + 8 n_shadows bytes per element.
+ * qfx_ema_swap: exchanges the contents of p and s bit for bit (NaN payloads and -0.0 included; the words move as integers),
+ * 16 bytes per element.  16-byte accesses when every buffer of the call is 16-byte aligned, scalar ones otherwise and for the n % 4
+ * tail.  The shadow pointers and rates travel by value in the kernel argument block: there is no device-side table.  No atomics:
+ * same inputs -> same bits.  Rejected with QFX_EINVAL before any launch: a NULL p or a, n_shadows outside 1..4, n < 0, below
+ * n_shadows a NULL shadow pointer, a shadow pointer equal to p or to an earlier shadow's, a one_minus_decay outside [0, 1] or NaN;
+ * for the swap a NULL p or s, p == s, n < 0.  n == 0 returns QFX_OK without a launch. ---- */
+#define QFX_EMA_MAX_SHADOWS 4
+typedef struct qfx_ema_args {
+  float*  shadow[QFX_EMA_MAX_SHADOWS];          /* n elements each, distinct from p and from each other */
+  float   one_minus_decay[QFX_EMA_MAX_SHADOWS];
+  int32_t n_shadows;                            /* 1..4 */
+} qfx_ema_args;
+int qfx_ema_update(const float* p, int64_t n, const qfx_ema_args* a, void* stream);
+int qfx_ema_swap(float* p, float* s, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

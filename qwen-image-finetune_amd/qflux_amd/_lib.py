@@ -191,6 +191,13 @@ class MuonArgs(C.Structure):
                 ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
+EMA_MAX_SHADOWS = 4       # QFX_EMA_MAX_SHADOWS
+
+
+class EmaArgs(C.Structure):
+    _fields_ = [("shadow", C.c_void_p * EMA_MAX_SHADOWS), ("one_minus_decay", C.c_float * EMA_MAX_SHADOWS), ("n_shadows", C.c_int32)]
+
+
 class HeadLora(C.Structure):
     _fields_ = [("w_pk", C.c_void_p * 2),
                 ("part", C.c_void_p), ("part_hstride", C.c_int64), ("ld_part", C.c_int32), ("c0", C.c_int32), ("R", C.c_int32),
@@ -294,6 +301,8 @@ SYMBOLS = {
     "qfx_lion8bit_step_grouped": (C.c_int, [C.POINTER(Lion8bitArgs), _vp, C.POINTER(LionGroup), _i32, _vp]),
     "qfx_sfadamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i32, _vp, _f, _f, _vp]),
     "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
+    "qfx_ema_update": (C.c_int, [_vp, _i64, C.POINTER(EmaArgs), _vp]),
+    "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
     "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),
     "qfx_muon_step": (C.c_int, [C.POINTER(MuonArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),

@@ -587,6 +587,29 @@ def sf_swap(p, z, beta1, to_eval):
     L.check(lib.qfx_sf_swap(_p(p), _p(z), p.numel(), 1.0 - 1.0 / beta1 if to_eval else 1.0 - beta1, stream_ptr()), "qfx_sf_swap")
 
 
+EMA_MAX_SHADOWS = L.EMA_MAX_SHADOWS
+
+
+def ema_update(p, shadows, one_minus_decays):
+    """One EMA step of up to EMA_MAX_SHADOWS shadow buffers towards p in ONE launch: s_k -= float32(omd_k) * (s_k - p), the three
+    roundings of diffusers' EMAModel.step; p is read once and not written.  See qfx.h."""
+    if not 1 <= len(shadows) <= EMA_MAX_SHADOWS or len(one_minus_decays) != len(shadows):
+        raise ValueError(f"ema_update: 1..{EMA_MAX_SHADOWS} shadows and one rate for each, not {len(shadows)} and {len(one_minus_decays)}")
+    _check_tensors("ema_update", p, [("p", p, torch.float32, p.numel(), "float32")] +
+                   [(f"shadow {k}", s, torch.float32, p.numel(), "float32") for k, s in enumerate(shadows)])
+    a = L.EmaArgs()
+    for k, (s, omd) in enumerate(zip(shadows, one_minus_decays)):
+        a.shadow[k], a.one_minus_decay[k] = _p(s), omd
+    a.n_shadows = len(shadows)
+    L.check(lib.qfx_ema_update(_p(p), p.numel(), C.byref(a), stream_ptr()), "qfx_ema_update")
+
+
+def ema_swap(p, s):
+    """Exchange the contents of the flat fp32 buffers p and s bit for bit, in ONE launch; see qfx.h."""
+    _check_tensors("ema_swap", p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p), ("s", s))])
+    L.check(lib.qfx_ema_swap(_p(p), _p(s), p.numel(), stream_ptr()), "qfx_ema_swap")
+
+
 MUON_ADJUST_LR = (None, "original", "match_rms_adamw")
 MUON_MAX_SHORT_SIDE = 96
 

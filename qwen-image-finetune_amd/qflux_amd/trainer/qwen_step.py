@@ -25,6 +25,7 @@ import re
 import torch
 import torch.distributed as dist
 
+from .. import ema as E
 from .. import ops
 from ..dp import LoraGradSync, check_replicas, init_distributed_from_env  # noqa: F401  (the last: bench.py and tools/ import it from here)
 from ..schedules import flowmatch_tables
@@ -48,7 +49,8 @@ def map_mask_to_latent(image_mask: torch.Tensor) -> torch.Tensor:
 class QwenLoraTrainStep:
     def __init__(self, dit, lr=1e-4, betas=None, eps=1e-8, weight_decay=None, max_grad_norm=1.0,
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
-                 bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None):
+                 bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None, ema_decay=None,
+                 ema_args=None):
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
@@ -60,6 +62,12 @@ class QwenLoraTrainStep:
         written to `self.lr` scales every group's lr by the same factor self.lr / (the constructor's lr), as torch's schedulers do
         with the groups' initial_lr.  loraplus_lr_ratio: shorthand for the two LoRA+ groups of
         qflux_amd.optim.loraplus_param_groups -- lora_A at lr, lora_B at lr * ratio.
+        ema_decay: None, a float or 1..4 floats -- exponential moving averages of the adapter weights (qflux_amd.ema: diffusers'
+        EMAModel), one shadow per decay, updated in one launch behind every optimizer step; ema_args: EMAModel's min_decay,
+        update_after_step, use_ema_warmup, inv_gamma, power.  eval(ema=k) / eval_mode(ema=k) put shadow k into the adapter weights
+        (sampling with train_step=... uses shadow 0), save_checkpoint writes them beside the trained weights.  Refused with
+        optimizer="adamw_schedulefree", whose x is an average already and wants the same eval swap.  None: nothing is allocated or
+        launched.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
         background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
         if criterion not in ("mse", "mask_edit"):
@@ -68,6 +76,11 @@ class QwenLoraTrainStep:
                                                                                                                 optimizer_args)
         if self.optimizer == "adafactor":
             self._opt_cls.validate(self.optimizer_args, lr)
+        self.ema_decays, self.ema_args = E.check_config(ema_decay, ema_args)
+        if self.ema_decays is not None and self.optimizer == "adamw_schedulefree":
+            raise ValueError("ema_decay with optimizer='adamw_schedulefree': the schedule-free x is the averaged point already, and both "
+                             "want the eval swap of the adapter weights")
+        self.ema = None             # qflux_amd.ema.EmaState, from the first step, eval() or load_checkpoint on (ema_decay given)
         self.blockwise = optimizer in A8.BLOCKWISE
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
@@ -192,6 +205,7 @@ class QwenLoraTrainStep:
         over the first n_tok predicted tokens; token-weighted with tok_w / inv_denom when given, or with the mask_edit criterion's
         weights (embeddings["edit_mask"]).  sync: the bucketed gradient exchange runs behind the backward."""
         self.dit.lora_store  # make sure the flat buffers / grads are attached
+        self._refuse_in_ema_eval(E.EVAL_GRAD)
         self._ensure_synced()
         pred = plan.run_forward(inputs, pe, t)
         if tok_w is None and self.criterion == "mask_edit":
@@ -250,6 +264,7 @@ class QwenLoraTrainStep:
             if dit._version != version or not any(p is plan for p in dit._plans.values()):
                 raise RuntimeError("capture_graph: the plan this graph was captured on is gone (adapters / quantisation changed "
                                    "or it was evicted); capture again")
+            self._refuse_in_ema_eval(E.EVAL_GRAD)
             ins = self._prepare(emb, noise, u)
             if [tuple(t.shape) for t in ins[:4]] != shapes:
                 raise ValueError("capture_graph: batch shape differs from the captured one")
@@ -338,30 +353,50 @@ class QwenLoraTrainStep:
     # ------------------------------------------------------------------ train / eval form of the adapter weights
     @property
     def train_mode(self):
-        """False while the adapter weights hold the averaged point x of a schedule-free optimizer (eval()); True otherwise, always
-        for every other family."""
+        """False while the adapter weights hold the averaged point x of a schedule-free optimizer or an EMA shadow (eval()); True
+        otherwise."""
+        if self.ema is not None and self.ema.active is not None:
+            return False
         return self.opt_state is None or self.opt_state.train_mode
+
+    def _ensure_ema(self):
+        """The EMA state for the store's current layout (ema_decay given): created as copies of the adapter weights as they are now."""
+        self.ema = E.ensure_state(self.ema, self.dit.lora_store, self.ema_decays, self.ema_args)
+        return self.ema
+
+    def _refuse_in_ema_eval(self, message):
+        if self.ema is not None and self.ema.active is not None:
+            raise RuntimeError(message.format(k=self.ema.active))
 
     def _swap(self, train):
         if self.optimizer == "adamw_schedulefree":
             self._ensure_opt_state()
             self.opt_state.swap(self.dit.lora_store, self.betas[0], train)
 
-    def eval(self):
+    def eval(self, ema=0):
         """optimizer="adamw_schedulefree": the adapter weights (lora_store.pflat, which every plan reads its LoRA operands from at
         each pass: no plan is rebuilt) go from y to the averaged x that is sampled from and saved -- the package's optimizer.eval().
-        Nothing happens in eval mode already, and for every other family."""
-        self._swap(False)
+        With ema_decay: EMA shadow `ema` is exchanged with the adapter weights.  Nothing happens in eval mode already (the same
+        shadow), and for every other family without EMA."""
+        if self.ema_decays is not None:
+            self._ensure_ema().swap_in(self.dit.lora_store, ema)
+        else:
+            self._swap(False)
 
     def train(self):
-        """Back from x to y (the package's optimizer.train()); nothing happens in train mode already, and for every other family."""
-        self._swap(True)
+        """Back from x to y (the package's optimizer.train()), or the trained weights back in place of the EMA shadow, bit for bit;
+        nothing happens in train mode already, and for every other family without EMA."""
+        if self.ema_decays is not None:
+            if self.ema is not None:
+                self.ema.swap_out(self.dit.lora_store)
+        else:
+            self._swap(True)
 
     @contextlib.contextmanager
-    def eval_mode(self):
+    def eval_mode(self, ema=0):
         """`with step.eval_mode():` -- eval() on entry, train() on exit if the step was in train mode before."""
         was = self.train_mode
-        self.eval()
+        self.eval(ema)
         try:
             yield self
         finally:
@@ -369,9 +404,12 @@ class QwenLoraTrainStep:
                 self.train()
 
     def optimizer_step(self, grad_scale=1.0):
+        self._refuse_in_ema_eval(E.EVAL_STEP)
         if not self.train_mode:
             raise RuntimeError(self.opt_state.EVAL_STEP)
         st = self._ensure_opt_state()
+        if self.ema_decays is not None:
+            self._ensure_ema()      # before the first step: the shadows start from the weights that step starts from
         self.global_step += 1
         if self._gnorm is None or self._gnorm.device != st.pflat.device:
             self._gnorm = torch.zeros((), dtype=torch.float32, device=st.pflat.device)
@@ -380,6 +418,8 @@ class QwenLoraTrainStep:
         rows, _ = self.param_groups_of(st)
         self.opt_state.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm,
                             grad_scale, self.optimizer_args, **({"groups": self._scheduled_rows(rows)} if rows else {}))
+        if self.ema is not None:
+            self.ema.update(st)     # same stream, outside a captured graph like the optimizer launches
 
     @property
     def _m(self):
@@ -433,14 +473,45 @@ class QwenLoraTrainStep:
         key style) + optimizer.bin + state.json.  With a schedule-free optimizer the weights file holds the averaged x (what an
         inference pipeline must load): the weights are swapped to eval for it and back, and optimizer.bin is written after that, in
         the mode the step was in.  The round trip y -> x -> y rounds (the package's own does); the run goes on from the
-        swapped-back y, and so does a run resumed from the folder."""
+        swapped-back y, and so does a run resumed from the folder.
+        With ema_decay the weights file holds the trained weights (resume is exact), pytorch_lora_weights_ema.safetensors holds
+        shadow 0 and _ema1 ... the others, each written by the same writer with the shadow swapped in (any LoRA loader reads them),
+        and ema.bin is torch.save of EmaState.state_dict(); the step ends in the form it was in."""
         import json
         os.makedirs(save_dir, exist_ok=True)
-        with self.eval_mode():
-            self.dit.save_lora_weights(save_dir)
+        if self.ema_decays is not None:
+            self._save_ema(save_dir)
+        else:
+            with self.eval_mode():
+                self.dit.save_lora_weights(save_dir)
         torch.save(self.state_dict(), os.path.join(save_dir, "optimizer.bin"))
         with open(os.path.join(save_dir, "state.json"), "w") as f:
             json.dump(dict({"global_step": self.global_step, "lr": self.lr}, **(extra_state or {})), f, indent=2)
+
+    def _save_ema(self, save_dir):
+        from ..lora_io import WEIGHT_NAME
+        st, ema = self.dit.lora_store, self._ensure_ema()
+        was = ema.active
+        stem, ext = os.path.splitext(WEIGHT_NAME)
+        for k in range(len(ema.shadows)):
+            ema.swap_in(st, k)
+            os.replace(self.dit.save_lora_weights(save_dir), os.path.join(save_dir, f"{stem}_ema{k or ''}{ext}"))
+        ema.swap_out(st)
+        self.dit.save_lora_weights(save_dir)
+        torch.save(ema.state_dict(st), os.path.join(save_dir, "ema.bin"))
+        if was is not None:
+            ema.swap_in(st, was)
+
+    def _load_ema(self, save_dir):
+        """Fresh shadows from the weights now in place, then ema.bin's over them where the folder has one."""
+        import warnings
+        self.ema = None
+        ema, path = self._ensure_ema(), os.path.join(save_dir, "ema.bin")
+        if os.path.exists(path):
+            ema.load_state_dict(self.dit.lora_store, torch.load(path, map_location="cpu", weights_only=False))
+            self.ema_decays, self.ema_args = ema.decays, ema.args      # the file's settings, as load_state_dict takes the optimizer's
+        else:
+            warnings.warn(f"{save_dir} has no ema.bin: the EMA shadows start as copies of the loaded weights, with no update counted")
 
     def load_checkpoint(self, save_dir, adapter_name=None):
         """adapter_name: inject/overwrite that adapter from the saved weights first (None = the adapter is already in place).
@@ -456,6 +527,8 @@ class QwenLoraTrainStep:
             if adapter_name is not None:
                 self.opt_state.train_mode = False
             self.train()
+        if self.ema_decays is not None:      # an ema.bin in the folder is ignored without ema_decay
+            self._load_ema(save_dir)
         self.broadcast_state()       # every replica continues from rank 0's copy of the checkpoint
         with open(os.path.join(save_dir, "state.json")) as f:
             return json.load(f)
@@ -463,9 +536,12 @@ class QwenLoraTrainStep:
     # ------------------------------------------------------------------ replica consistency (main.py:58, base_trainer.py:384-393)
     def _state_buffers(self):
         """Every flat buffer that must be identical on all ranks: adapter weights, then the optimizer state's (None where this rank
-        has no state: the list has the same length on every rank)."""
+        has no state: the list has the same length on every rank), then the EMA shadows ema0 ... when ema_decay is given."""
         opt = self.opt_state.buffers() if self.opt_state is not None else [(n, None) for n in self._opt_cls.names(self.optimizer_args)]
-        return [("lora", self.dit.lora_store.pflat)] + opt
+        ema = []
+        if self.ema_decays is not None:
+            ema = self.ema.buffers() if self.ema is not None else [(n, None) for n in E.EmaState.names(self.ema_decays)]
+        return [("lora", self.dit.lora_store.pflat)] + opt + ema
 
     def broadcast_state(self, src: int = 0):
         """Rank `src`'s adapter weights (+ optimizer state, + step count) to every rank: what DDP's constructor does for the
@@ -476,10 +552,13 @@ class QwenLoraTrainStep:
         if self.world <= 1:
             return
         st, cls = self.dit.lora_store, self._opt_cls
-        head = torch.tensor([int(self.opt_state is not None), self.global_step] + [int(self.optimizer_args[n]) for n in cls.LAYOUT_ARGS],
+        head = torch.tensor([int(self.opt_state is not None), self.global_step] + [int(self.optimizer_args[n]) for n in cls.LAYOUT_ARGS] +
+                            ([self._ensure_ema().optimization_step] if self.ema_decays is not None else []),
                             dtype=torch.int64, device=st.pflat.device)
         dist.broadcast(head, src=src, group=self.group)
         have, self.global_step, *ints = head.tolist()
+        if self.ema_decays is not None:      # the shadows exist on every rank from here on and travel with the buffers below
+            self.ema.optimization_step = ints.pop()
         # the buffer list is derived from the AGREED header on every rank (same collectives in the same order everywhere): state
         # rank `src` has is created where missing, state it lacks is dropped locally (a rank that had stepped before must not carry
         # moments the others do not have)
