@@ -830,6 +830,50 @@ typedef struct qfx_ema_args {
 int qfx_ema_update(const float* p, int64_t n, const qfx_ema_args* a, void* stream);
 int qfx_ema_swap(float* p, float* s, int64_t n, void* stream);
 
+/* ---- general flow-matching criterion: per-sample weights (diffusers' compute_loss_weighting_for_sd3), per-token weights (edit mask,
+ * attention mask), L2 or kohya's pseudo-Huber / smooth-L1 with a per-sample threshold c, and the loss of every sample.  With
+ * d = pred - target in fp32 (rows s < S_t of pred enter):
+ *   loss_per_sample[b] = B * inv_denom * sum_{s<S_t} token_w[b,s] * (1/C) * sum_c rho_b(d[b,s,c])
+ *   loss               = (1/B) * sum_b sample_w[b] * loss_per_sample[b]
+ *   dpred[b,s,c]       = bf16( rho_b'(d) * sample_w[b] * token_w[b,s] * (1/C) * inv_denom * gscale ),  0 for rows s >= S_t
+ *   QFX_LOSS_L2         rho = d^2                        rho' = 2 d
+ *   QFX_LOSS_HUBER      rho = 2 c (sqrt(d^2 + c^2) - c)  rho' = 2 c d / sqrt(d^2 + c^2)
+ *   QFX_LOSS_SMOOTH_L1  rho = 2 (sqrt(d^2 + c^2) - c)    rho' = 2 d / sqrt(d^2 + c^2)
+ * inv_denom = 1/(B S_t): MseLoss with a [B,1,1] weighting (losses/mse_loss.py:66-83), and MaskEditLoss with token_w = the edit
+ * weights; token_w = attention mask * edit weight and inv_denom = 1/(n_valid + eps): AttentionMaskMseLoss(reduction="mean") with
+ * weighting.  sample_w [B] and token_w [B,S_t] fp32, NULL = ones; huber_c [B] fp32, required unless kind is L2, every value > 0 and
+ * finite (the caller checks on the host).  loss (fp32 scalar) and loss_per_sample ([B] fp32, may be NULL) are WRITTEN, not
+ * accumulated; dpred [B,S_all,C] bf16 may be NULL.
+ * The gradient is fp32, each operation rounded, the factors multiplied from left to right as written above with 1/C =
+ * float(1)/float(C); r = sqrt(d*d + c*c), rho' = (2c*d)/r resp. (2*d)/r, correctly rounded divide and square root, no FMA.
+ * sqrt(d^2 + c^2) - c is formed as d^2 / (r + c).  The loss terms are those fp32 rho values, added in fp64: per (sample, chunk of
+ * rows) into `workspace` (qfx_criterion_workspace_bytes(B, S_t, C) bytes, 8-byte aligned, need not be zeroed), then by a second
+ * one-block launch in chunk order and in sample order -- no floating-point atomics, same inputs -> same bits.  16-byte accesses
+ * when C % 8 == 0 and pred, target and dpred are 16-byte aligned, scalar ones otherwise; any C >= 1, 1 <= S_t <= S_all, B >= 1.
+ * Rejected with QFX_EINVAL before any launch: a NULL args, pred, target, loss or workspace, a non-positive dimension, S_t > S_all,
+ * an unknown kind, kind != L2 with a NULL huber_c, workspace_bytes below the query's answer.  The query returns 0 for a
+ * non-positive dimension. ---- */
+#define QFX_LOSS_L2 0
+#define QFX_LOSS_HUBER 1
+#define QFX_LOSS_SMOOTH_L1 2
+typedef struct qfx_criterion_args {
+  const uint16_t* pred;            /* [B, S_all, C] bf16 */
+  const uint16_t* target;          /* [B, S_t, C] bf16 */
+  const float*    sample_w;        /* [B] or NULL */
+  const float*    token_w;         /* [B, S_t] or NULL */
+  const float*    huber_c;         /* [B]; NULL allowed with QFX_LOSS_L2 only */
+  float*          loss;            /* scalar, written */
+  float*          loss_per_sample; /* [B] or NULL, written */
+  uint16_t*       dpred;           /* [B, S_all, C] bf16 or NULL */
+  void*           workspace;
+  int64_t         workspace_bytes;
+  int32_t         B, S_all, S_t, C;
+  int32_t         kind;            /* QFX_LOSS_* */
+  float           inv_denom, gscale;
+} qfx_criterion_args;
+int64_t qfx_criterion_workspace_bytes(int32_t B, int32_t S_t, int32_t C);
+int qfx_criterion_fwd_bwd(const qfx_criterion_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

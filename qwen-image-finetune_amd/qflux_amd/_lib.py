@@ -198,6 +198,16 @@ class EmaArgs(C.Structure):
     _fields_ = [("shadow", C.c_void_p * EMA_MAX_SHADOWS), ("one_minus_decay", C.c_float * EMA_MAX_SHADOWS), ("n_shadows", C.c_int32)]
 
 
+LOSS_L2, LOSS_HUBER, LOSS_SMOOTH_L1 = 0, 1, 2       # QFX_LOSS_*
+
+
+class CriterionArgs(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("sample_w", C.c_void_p), ("token_w", C.c_void_p), ("huber_c", C.c_void_p),
+                ("loss", C.c_void_p), ("loss_per_sample", C.c_void_p), ("dpred", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("S_all", C.c_int32), ("S_t", C.c_int32), ("C", C.c_int32),
+                ("kind", C.c_int32), ("inv_denom", C.c_float), ("gscale", C.c_float)]
+
+
 class HeadLora(C.Structure):
     _fields_ = [("w_pk", C.c_void_p * 2),
                 ("part", C.c_void_p), ("part_hstride", C.c_int64), ("ld_part", C.c_int32), ("c0", C.c_int32), ("R", C.c_int32),
@@ -303,6 +313,8 @@ SYMBOLS = {
     "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
     "qfx_ema_update": (C.c_int, [_vp, _i64, C.POINTER(EmaArgs), _vp]),
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "qfx_criterion_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "qfx_criterion_fwd_bwd": (C.c_int, [C.POINTER(CriterionArgs), _vp]),
     "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),
     "qfx_muon_step": (C.c_int, [C.POINTER(MuonArgs), _vp]),
     "qfx_stream_create_cu_masked": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),

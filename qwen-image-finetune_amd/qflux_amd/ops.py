@@ -292,6 +292,45 @@ def mse_token_weighted_fwd_bwd(pred, target, token_w, S_t, inv_denom, gscale=1.0
     return loss, dpred
 
 
+LOSS_KINDS = {"l2": L.LOSS_L2, "huber": L.LOSS_HUBER, "smooth_l1": L.LOSS_SMOOTH_L1}
+
+
+def criterion_workspace(B, S_t, C_, device):
+    """The workspace of criterion_fwd_bwd for this shape (fp64 partial sums; not zeroed: every launch writes all it reads)."""
+    return torch.empty(lib.qfx_criterion_workspace_bytes(B, S_t, C_) // 8, dtype=torch.float64, device=device)
+
+
+def criterion_fwd_bwd(pred, target, S_t, *, sample_w=None, token_w=None, huber_c=None, kind="l2", inv_denom=None, gscale=1.0,
+                      want_grad=True, workspace=None):
+    """The general criterion (qfx_criterion_fwd_bwd, see qfx.h): loss = mean_b sample_w[b] * loss_per_sample[b] over the first S_t
+    rows of pred, token-weighted with token_w [B,S_t], rho = d^2 ("l2") or kohya's "huber" / "smooth_l1" with the per-sample
+    threshold huber_c [B] (> 0 and finite: the caller's to check on the host).  inv_denom: 1/(B S_t) when None.  Returns
+    (loss, loss_per_sample [B], dpred or None); nothing is accumulated, nothing needs zeroing, no host sync."""
+    B, S_all, Cc = pred.shape
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"criterion_fwd_bwd: kind is one of {sorted(LOSS_KINDS)}, not {kind!r}")
+    if kind != "l2" and huber_c is None:
+        raise ValueError(f"criterion_fwd_bwd: kind {kind!r} needs huber_c")
+    dev = pred.device
+    _bf(pred, "pred"); _bf(target, "target")
+    assert pred.is_contiguous() and target.is_contiguous() and tuple(target.shape) == (B, S_t, Cc), "criterion_fwd_bwd: pred [B,S_all,C], target [B,S_t,C], contiguous"
+    for name, t, n in (("sample_w", sample_w, B), ("token_w", token_w, B * S_t), ("huber_c", huber_c, B)):
+        assert t is None or (t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.numel() == n), \
+            f"criterion_fwd_bwd: {name} is a contiguous float32 tensor of {n} elements on {dev}"
+    ws = criterion_workspace(B, S_t, Cc, dev) if workspace is None else workspace
+    assert ws.device == dev and ws.is_contiguous(), "criterion_fwd_bwd: workspace on the device of pred"
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lps = torch.empty(B, dtype=torch.float32, device=dev)
+    dpred = torch.empty_like(pred) if want_grad else None
+    a = L.CriterionArgs()
+    a.pred, a.target, a.sample_w, a.token_w, a.huber_c = _p(pred), _p(target), _p(sample_w), _p(token_w), _p(huber_c)
+    a.loss, a.loss_per_sample, a.dpred, a.workspace, a.workspace_bytes = _p(loss), _p(lps), _p(dpred), _p(ws), ws.numel() * ws.element_size()
+    a.B, a.S_all, a.S_t, a.C, a.kind = B, S_all, S_t, Cc, LOSS_KINDS[kind]
+    a.inv_denom, a.gscale = (1.0 / (B * S_t) if inv_denom is None else inv_denom), gscale
+    L.check(lib.qfx_criterion_fwd_bwd(C.byref(a), stream_ptr()), "qfx_criterion_fwd_bwd")
+    return loss, lps, dpred
+
+
 def flowmatch_prepare(x0, noise, ctrl, sigma, mode=0):
     B, S_t, Cc = x0.shape
     S_c = ctrl.shape[1] if ctrl is not None else 0

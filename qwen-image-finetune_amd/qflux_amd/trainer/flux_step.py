@@ -10,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from .. import ops
+from ..schedules import shift_time, timestep_density
 from .qwen_step import BF, QwenLoraTrainStep
 
 
@@ -21,6 +22,20 @@ def prepare_latent_image_ids(height: int, width: int) -> torch.Tensor:
 
 
 class FluxKontextTrainStep(QwenLoraTrainStep):
+    def _draw_t(self, n, dev, t=None):
+        """(t [n] in the weight dtype on the device, float(t) on the CPU or None).  With every objective option at its default: the
+        reference's device draw, nothing comes back to the host.  Otherwise u from the step's density on the CPU generator, shifted;
+        an injected t is final.  The CPU copy (a device-to-host copy for an injected device tensor) feeds weighting and threshold."""
+        dt = self.weight_dtype
+        if t is None and self.weighting_scheme == "none" and self.timestep_shift == 1.0 and not self._general_objective:
+            return torch.rand((n,), device=dev, dtype=dt), None
+        if t is None:
+            u = timestep_density(self.weighting_scheme, n, self.logit_mean, self.logit_std, self.mode_scale)
+            t = shift_time(u, self.timestep_shift).to(dt)
+        else:
+            t = t.to(dt)
+        return t.to(dev), (t.float().cpu() if self._general_objective else None)
+
     def _prepare_flux(self, embeddings, noise=None, t=None):
         dev = self.dit.device
         x0 = embeddings["image_latents"].to(dev, non_blocking=True)
@@ -31,7 +46,8 @@ class FluxKontextTrainStep(QwenLoraTrainStep):
         pooled = embeddings["pooled_prompt_embeds"].to(dev, non_blocking=True).to(self.weight_dtype)
         B = x0.shape[0]
         noise = torch.randn(x0.shape, device=dev, dtype=self.weight_dtype) if noise is None else noise.to(dev).to(self.weight_dtype)
-        t = torch.rand((B,), device=dev, dtype=self.weight_dtype) if t is None else t.to(dev).to(self.weight_dtype)
+        t, t_host = self._draw_t(B, dev, t)
+        self._step_objective = None if t_host is None else self._stage_objective(t_host * 1000, t_host, dev)
         packed, target = ops.flowmatch_prepare(x0.contiguous(), noise.contiguous(), ctrl.contiguous(), t.contiguous(), mode=1)
         h, w = embeddings["latent_hw"]
         img_ids = torch.cat([prepare_latent_image_ids(h, w), embeddings["control_ids"].float().cpu()], dim=0)
@@ -44,6 +60,9 @@ class FluxKontextTrainStep(QwenLoraTrainStep):
         pred = self.dit(hidden_states=packed, timestep=t, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=pe,
                         txt_ids=txt_ids, img_ids=img_ids, joint_attention_kwargs={}, return_dict=False)[0]
         pred = pred[:, :S_t]
+        if self._step_objective is not None:
+            tok_w = self._token_weights(embeddings, target.shape[0], S_t, pred.device) if self.criterion == "mask_edit" else None
+            return self._general_loss(pred, target, tok_w, 1.0 / (target.shape[0] * S_t))
         el = (pred.float() - target.float()) ** 2
         if self.criterion == "mask_edit":      # forward_loss(..., edit_mask=embeddings["edit_mask"]) (flux_kontext_trainer.py:570-574)
             el = el * self._token_weights(embeddings, target.shape[0], S_t, el.device).unsqueeze(-1)
@@ -65,6 +84,8 @@ class FluxKontextTrainStep(QwenLoraTrainStep):
         pred = self.dit(hidden_states=b["inp"], timestep=b["timestep"], guidance=b["guidance"], pooled_projections=b["pooled"],
                         encoder_hidden_states=b["pe"], txt_ids=b["txt_ids"], img_ids=b["ids"], attention_mask=b["mask"],
                         joint_attention_kwargs={}, return_dict=False)[0][:, : b["n_t_max"]]
+        if self._step_objective is not None:
+            return self._general_loss(pred, b["target"], b["tok_w"], 1.0 / (b["n_valid"] + 1e-12))
         el = (pred.float() - b["target"].float()) ** 2
         tok = (el * b["tok_w"].unsqueeze(-1)).mean(dim=2)
         return tok.sum() / (b["n_valid"] + 1e-12)
@@ -85,12 +106,13 @@ def _build_multires_batch(step, samples, txt):
     dev, dt = step.dit.device, step.weight_dtype
     B = len(samples)
     seqs, ids, n_t = [], [], []
-    noises, ts = [], []
+    noises, ts, ts_host = [], [], []
     for smp in samples:
         x0 = smp["image_latents"].to(dev)
         ctrl = smp["control_latents"].to(dev)
         noise = smp["noise"].to(dev).to(dt) if "noise" in smp else torch.randn(x0.shape, device=dev, dtype=dt)
-        t = smp["t"].to(dev).to(dt).reshape(1) if "t" in smp else torch.rand((1,), device=dev, dtype=dt)
+        t, t_host = step._draw_t(1, dev, smp["t"].reshape(1) if "t" in smp else None)
+        ts_host.append(t_host)
         t_ = t.unsqueeze(1)
         x_t = (1.0 - t_) * x0 + t_ * noise                      # bf16 * cache dtype promotes like the reference
         seqs.append(torch.cat([x_t.to(dt), ctrl.to(dt)], dim=0))
@@ -118,6 +140,8 @@ def _build_multires_batch(step, samples, txt):
         tok_w[i, : n_t[i]] = 1.0
         target[i, : n_t[i]] = noises[i] - samples[i]["image_latents"].to(dev).to(dt)
     timestep = torch.cat(ts)
+    t_host = torch.cat(ts_host) if step._general_objective else None
+    step._step_objective = None if t_host is None else step._stage_objective(t_host * 1000, t_host, dev)
     guidance = torch.ones((B,), device=dev, dtype=dt) if step.dit.config.guidance_embeds else None
     pe = txt["prompt_embeds"].to(dev).to(dt)
     pooled = txt["pooled_prompt_embeds"].to(dev).to(dt)

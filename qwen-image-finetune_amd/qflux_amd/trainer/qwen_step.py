@@ -28,7 +28,7 @@ import torch.distributed as dist
 from .. import ema as E
 from .. import ops
 from ..dp import LoraGradSync, check_replicas, init_distributed_from_env  # noqa: F401  (the last: bench.py and tools/ import it from here)
-from ..schedules import flowmatch_tables
+from ..schedules import HUBER_SCHEDULES, WEIGHTING_SCHEMES, flowmatch_tables, huber_threshold, loss_weighting, timestep_density
 from . import adam8bit as A8
 from . import optim_state as OS
 from .optim_state import resolve_family
@@ -50,7 +50,8 @@ class QwenLoraTrainStep:
     def __init__(self, dit, lr=1e-4, betas=None, eps=1e-8, weight_decay=None, max_grad_norm=1.0,
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
                  bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None, ema_decay=None,
-                 ema_args=None):
+                 ema_args=None, weighting_scheme="none", logit_mean=0.0, logit_std=1.0, mode_scale=1.29, timestep_shift=1.0,
+                 loss_type="l2", huber_c=0.1, huber_schedule="constant"):
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
@@ -69,13 +70,38 @@ class QwenLoraTrainStep:
         optimizer="adamw_schedulefree", whose x is an average already and wants the same eval swap.  None: nothing is allocated or
         launched.
         criterion: "mse" = MseLoss (losses/mse_loss.py:46-83); "mask_edit" = MaskEditLoss(forground_weight,
-        background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent)."""
+        background_weight) (losses/edit_mask_loss.py:39-90), fed by embeddings["edit_mask"] [B,S_t] (all-ones when absent).
+        weighting_scheme: diffusers' one knob over the timestep density and the loss weighting (schedules.timestep_density /
+        loss_weighting): "none" | "logit_normal" (logit_mean, logit_std) | "mode" (mode_scale) shape where the timesteps fall,
+        "sigma_sqrt" | "cosmap" draw uniformly and weight every sample's loss by its sigma.  timestep_shift: the time shift
+        shift s / (1 + (shift - 1) s) of the sigma table (Qwen: flowmatch_tables(shift=), the modulation table is keyed on the same
+        timesteps) or of the drawn t (FLUX).  loss_type: "l2" | "huber" | "smooth_l1" (kohya's pseudo-Huber forms, include/qfx.h)
+        with the threshold huber_c, per sample huber_c ** (timestep / 1000) under huber_schedule="exponential".  An injected u / t
+        is taken as the final value: density and shift are skipped, weighting and threshold follow from it.  With unit weights
+        and "l2" (every default) the step launches the two MSE kernels as before and last_sample_losses is None; otherwise the
+        general criterion kernel, after which last_sample_losses holds the per-sample losses ([B] on the device, no host sync)."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
         self.optimizer_alias, self.optimizer, self._opt_cls, weight_decay, self.optimizer_args = resolve_family(optimizer, weight_decay,
                                                                                                                 optimizer_args)
         if self.optimizer == "adafactor":
             self._opt_cls.validate(self.optimizer_args, lr)
+        if weighting_scheme not in WEIGHTING_SCHEMES:
+            raise ValueError(f"weighting_scheme is one of {WEIGHTING_SCHEMES}, not {weighting_scheme!r}")
+        if loss_type not in ops.LOSS_KINDS:
+            raise ValueError(f"loss_type is one of {tuple(ops.LOSS_KINDS)}, not {loss_type!r}")
+        if huber_schedule not in HUBER_SCHEDULES:
+            raise ValueError(f"huber_schedule is one of {HUBER_SCHEDULES}, not {huber_schedule!r}")
+        if not 0 < huber_c < float("inf"):
+            raise ValueError(f"huber_c must be positive and finite, not {huber_c}")
+        if not 0 < timestep_shift < float("inf"):
+            raise ValueError(f"timestep_shift must be positive and finite, not {timestep_shift}")
+        self.weighting_scheme, self.logit_mean, self.logit_std, self.mode_scale = weighting_scheme, logit_mean, logit_std, mode_scale
+        self.timestep_shift, self.loss_type, self.huber_c, self.huber_schedule = float(timestep_shift), loss_type, float(huber_c), huber_schedule
+        # the general criterion kernel is launched only where the objective needs it: per-sample weights or a Huber form
+        self._general_objective = weighting_scheme in ("sigma_sqrt", "cosmap") or loss_type != "l2"
+        self._step_objective = None       # (sample_w, huber_c) of the batch last prepared, on the device; None on the MSE path
+        self.last_sample_losses = None    # [B] device fp32 after a fused pass through the general criterion
         self.ema_decays, self.ema_args = E.check_config(ema_decay, ema_args)
         if self.ema_decays is not None and self.optimizer == "adamw_schedulefree":
             raise ValueError("ema_decay with optimizer='adamw_schedulefree': the schedule-free x is the averaged point already, and both "
@@ -100,7 +126,7 @@ class QwenLoraTrainStep:
         self.weight_dtype = weight_dtype
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
-        self.timesteps_tbl, self.sigmas_tbl = flowmatch_tables()
+        self.timesteps_tbl, self.sigmas_tbl = flowmatch_tables(shift=self.timestep_shift)
         # frozen conditioning head: the AdaLN modulation vectors of every training timestep, computed once here so that no step pays
         # for it (dit.ensure_modulation_table; QFX_MOD_TABLE=0 / QFX_MOD_TABLE_GB; nothing happens with adapters on the head)
         if getattr(dit, "_MOD_TABLE", False):
@@ -144,10 +170,22 @@ class QwenLoraTrainStep:
 
     # ------------------------------------------------------------------ sampling (CPU RNG like the reference)
     def sample_timesteps(self, batch_size, u=None):
-        if u is None:
-            u = torch.rand(size=(batch_size,), device="cpu")  # compute_density_for_timestep_sampling("none")
-        idx = (u * 1000).long()
+        if u is None:    # compute_density_for_timestep_sampling; "none" is torch.rand(size=(batch_size,), device="cpu")
+            u = timestep_density(self.weighting_scheme, batch_size, self.logit_mean, self.logit_std, self.mode_scale)
+        idx = (u * 1000).long().clamp_(0, 999)      # sigmoid rounds to 1.0 in fp32 far out in the tail
         return self.timesteps_tbl[idx], self.sigmas_tbl[idx]
+
+    def _stage_objective(self, timesteps, sigmas, dev):
+        """The per-sample inputs of the general criterion from the batch's timesteps (0..1000) and sigmas (CPU [B]), uploaded
+        non-blocking: (sample_w or None for unit weights, huber_c or None for l2); None when the MSE kernels serve the objective."""
+        if not self._general_objective:
+            return None
+        sw = hc = None
+        if self.weighting_scheme in ("sigma_sqrt", "cosmap"):
+            sw = loss_weighting(self.weighting_scheme, sigmas).contiguous().to(dev, non_blocking=True)
+        if self.loss_type != "l2":
+            hc = huber_threshold(self.huber_schedule, self.huber_c, timesteps).contiguous().to(dev, non_blocking=True)
+        return sw, hc
 
     def _prepare(self, embeddings, noise=None, u=None):
         dev = self.dit.device
@@ -161,6 +199,7 @@ class QwenLoraTrainStep:
             noise = noise.to(self.weight_dtype).to(dev)
         timesteps, sigmas = self.sample_timesteps(B, u)
         sig = sigmas.to(self.weight_dtype).to(dev, non_blocking=True)
+        self._step_objective = self._stage_objective(timesteps, sigmas, dev)
         packed, target = ops.flowmatch_prepare(x0.contiguous(), noise.contiguous(), ctrl.contiguous(), sig)
         t_in = (timesteps / 1000).to(dev, non_blocking=True)
         return packed, target, pe, t_in, x0.shape[1]
@@ -180,10 +219,30 @@ class QwenLoraTrainStep:
                         encoder_hidden_states=pe, img_shapes=embeddings["img_shapes"], txt_seq_lens=txt_seq_lens,
                         return_dict=False)[0]
         pred = pred[:, :S_t]
+        if self._step_objective is not None:
+            tok_w = self._token_weights(embeddings, target.shape[0], S_t, pred.device) if self.criterion == "mask_edit" else None
+            return self._general_loss(pred, target, tok_w, 1.0 / (target.shape[0] * S_t))
         el = (pred.float() - target.float()) ** 2            # MseLoss with weighting = 1 (mse_loss.py:71-81)
         if self.criterion == "mask_edit":                      # MaskEditLoss, reduction="mean" (edit_mask_loss.py:62-86)
             el = el * self._token_weights(embeddings, target.shape[0], S_t, el.device).unsqueeze(-1)
         return torch.mean(el.reshape(target.shape[0], -1), dim=1).mean()
+
+    def _general_loss(self, pred, target, tok_w, inv_denom):
+        """The objective of qfx_criterion_fwd_bwd in torch, for the autograd paths: pred [B,S_t,C], the batch's staged
+        (sample_w, huber_c), tok_w [B,S_t] or None."""
+        sw, hc = self._step_objective
+        d = pred.float() - target.float()
+        if self.loss_type == "l2":
+            rho = d ** 2
+        else:
+            c = hc.reshape(-1, 1, 1)
+            r = torch.sqrt(d ** 2 + c ** 2)
+            rho = (2 * c if self.loss_type == "huber" else 2.0) * (d ** 2 / (r + c))
+        tok = rho.mean(dim=2)
+        if tok_w is not None:
+            tok = tok * tok_w
+        per_sample = target.shape[0] * inv_denom * tok.sum(dim=1)
+        return (per_sample if sw is None else sw * per_sample).mean()
 
     def _token_weights(self, embeddings, B, S_t, dev):
         m = embeddings.get("edit_mask")
@@ -203,7 +262,9 @@ class QwenLoraTrainStep:
     def _fused_pass(self, plan, inputs, pe, t, target, n_tok, grad_scale, sync, embeddings=None, tok_w=None, inv_denom=None):
         """The device part of every fused forward_backward: forward program, loss kernel, backward program.  The loss is the MSE
         over the first n_tok predicted tokens; token-weighted with tok_w / inv_denom when given, or with the mask_edit criterion's
-        weights (embeddings["edit_mask"]).  sync: the bucketed gradient exchange runs behind the backward."""
+        weights (embeddings["edit_mask"]).  With per-sample weights or a Huber form staged by the batch's preparation
+        (_step_objective) the general criterion kernel computes it and leaves last_sample_losses.  sync: the bucketed gradient exchange
+        runs behind the backward."""
         self.dit.lora_store  # make sure the flat buffers / grads are attached
         self._refuse_in_ema_eval(E.EVAL_GRAD)
         self._ensure_synced()
@@ -211,7 +272,12 @@ class QwenLoraTrainStep:
         if tok_w is None and self.criterion == "mask_edit":
             B = target.shape[0]
             tok_w, inv_denom = self._token_weights(embeddings, B, n_tok, pred.device), 1.0 / (B * n_tok)
-        if tok_w is None:
+        self.last_sample_losses = None
+        if self._step_objective is not None:
+            sw, hc = self._step_objective
+            loss, self.last_sample_losses, dpred = ops.criterion_fwd_bwd(pred, target, n_tok, sample_w=sw, token_w=tok_w, huber_c=hc,
+                                                                         kind=self.loss_type, inv_denom=inv_denom, gscale=grad_scale)
+        elif tok_w is None:
             loss, dpred = ops.mse_loss_fwd_bwd(pred, target, n_tok, gscale=grad_scale)
         else:
             loss, dpred = ops.mse_token_weighted_fwd_bwd(pred, target, tok_w, n_tok, inv_denom, gscale=grad_scale)
@@ -241,12 +307,20 @@ class QwenLoraTrainStep:
         static = [torch.empty_like(t) for t in (packed, target, pe, t_in)]
         for d, s_ in zip(static, (packed, target, pe, t_in)):
             d.copy_(s_)
+        # the general criterion's per-step inputs, staged like the four above; its workspace is the graph's own
+        obj_static = None if self._step_objective is None else [None if t is None else t.clone() for t in self._step_objective]
+        ws = None if obj_static is None else ops.criterion_workspace(target.shape[0], S_t, target.shape[2], target.device)
 
         def body():
             pred = plan.run_forward(static[0], static[2], static[3])
-            loss, dpred = ops.mse_loss_fwd_bwd(pred, static[1], S_t)
+            if obj_static is None:
+                loss, dpred = ops.mse_loss_fwd_bwd(pred, static[1], S_t)
+                per_sample = None
+            else:
+                loss, per_sample, dpred = ops.criterion_fwd_bwd(pred, static[1], S_t, sample_w=obj_static[0], huber_c=obj_static[1],
+                                                                kind=self.loss_type, workspace=ws)
             plan.run_backward(dpred)
-            return loss
+            return loss, per_sample
 
         warm = torch.cuda.Stream(device=dit.device)     # one eager pass on a non-default stream (lazy module loads, pool warm-up)
         warm.wait_stream(torch.cuda.current_stream())
@@ -256,7 +330,7 @@ class QwenLoraTrainStep:
         self.zero_grad()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            loss_static = body()
+            loss_static, per_sample_static = body()
         self.zero_grad()
         shapes = [tuple(t.shape) for t in static]
 
@@ -270,15 +344,20 @@ class QwenLoraTrainStep:
                 raise ValueError("capture_graph: batch shape differs from the captured one")
             for d, s_ in zip(static, ins[:4]):
                 d.copy_(s_)
+            for d, s_ in zip(obj_static or (), self._step_objective or ()):
+                if d is not None:
+                    d.copy_(s_)
             self._ensure_synced()
             self._mark_unexchanged()
             graph.replay()
             self.sync.disarm()
             self.optimizer_step(grad_scale=self.allreduce_grads())
             self.zero_grad()
+            self.last_sample_losses = None if per_sample_static is None else per_sample_static.clone()
             return loss_static.clone()      # the graph overwrites loss_static on every replay
 
         step.graph = graph
+        step.criterion_workspace = ws      # the graph holds its address: it lives as long as the step does
         return step
 
     # ------------------------------------------------------------------ gradient exchange (the buckets: dp.LoraGradSync)
