@@ -874,6 +874,52 @@ typedef struct qfx_criterion_args {
 int64_t qfx_criterion_workspace_bytes(int32_t B, int32_t S_t, int32_t C);
 int qfx_criterion_fwd_bwd(const qfx_criterion_args* a, void* stream);
 
+/* ---- max-norm regularisation of the adapters (kohya's --scale_weight_norms: LoRANetwork.apply_max_norm_regularization) over the
+ * flat LoRA buffer p, behind the optimizer's launch.  Per adapter pair, A = lora_A.weight [r, in], B = lora_B.weight [out, r],
+ * s = scale (lora_alpha / r, as fp32), m = max_norm:
+ *   norm_raw    = float32(|s| * sqrt(sum_ij (A A^T)_ij (B^T B)_ij))   = ||s B A||_F; the product B A is never formed.  Both r x r
+ *                 Gram matrices and their contraction are accumulated in fp64 from the widened fp32 weights (every product exact),
+ *                 |s| * sqrt(.) is formed in fp64 and rounded ONCE to fp32; a sum that rounding left below 0 counts as 0
+ *   ratio       = norm_raw > m ? m / norm_raw : 1                     one correctly rounded fp32 divide
+ *                 (kohya's clamp(norm, min = m / 2), clamp(max = m) / norm: 1 when norm_raw <= m, else m / norm_raw)
+ *   q           = sqrtf(ratio)                                        one correctly rounded fp32 square root
+ *   A *= q, B *= q  when ratio != 1                                   one fp32 multiply per element; a pair with norm_raw <= m is
+ *                                                                     not written at all
+ *   norms[pair] = norm_raw * ratio                                    one fp32 multiply;  ratios[pair] = ratio
+ *   summary     = { keys_scaled = the number of pairs with ratio != 1 (an integer count, written as fp32),
+ *                   float32((fp64 sum of norms[] in pair order) / n_pairs),  the fp32 maximum of norms[] (a NaN is kept),  0 }
+ * B = 0 (every adapter before the first step) gives norm_raw = 0, ratio = 1 and untouched weights.  A pair whose norm_raw is not
+ * finite is left untouched and reported with ratio = 1 and its non-finite norm; the other pairs proceed (kohya multiplies by the
+ * NaN; this is the Muon step's skip rule).  max_norm = +inf measures only: nothing is written to p, the statistics are produced.
+ * ONE launch of one 256-lane workgroup per pair (any number of pairs), driven by the device table, then a second one-block launch
+ * that writes summary from norms / ratios in pair order.  A and B stream through LDS tiles; each lane owns a fixed block of the
+ * Gram matrices' upper triangle in fp64 registers; the workgroup folds in an order fixed by the shape.  No atomics, nothing crosses
+ * a workgroup: same inputs -> same bits.  16-byte accesses where the addresses and lengths allow (the tiles: A 16-byte aligned and
+ * in % 4 == 0, B 16-byte aligned and r % 4 == 0; the scaling: everything between the first and the last 16-byte boundary), scalar
+ * ones otherwise.  1 <= r <= 128, 1 <= in, out <= 2^24, any offsets.
+ * qfx_maxnorm_check_table runs on a HOST copy of the table: QFX_EINVAL for n_pairs < 0, n_elems < 0, a NULL table with n_pairs > 0,
+ * r outside 1..128, in or out outside 1..2^24, a negative offset, a matrix that reaches past n_elems, two matrices of the table
+ * that overlap, a non-finite scale.  The kernel skips a pair with such dimensions or offsets (norm 0, ratio 1), it does not check
+ * extents: launch only tables that passed.  qfx_maxnorm_apply rejects with QFX_EINVAL before any launch: a NULL args, n_pairs < 0,
+ * a max_norm that is NaN or <= 0, with n_pairs > 0 a NULL p, table, norms, ratios or summary.  n_pairs == 0 returns QFX_OK without
+ * a launch. ---- */
+typedef struct qfx_maxnorm_pair {     /* 32 bytes */
+  int64_t off_a, off_b;               /* first element of A [r, in] / B [out, r], row-major, in p */
+  int32_t r, in_features, out_features;
+  float   scale;                      /* lora_alpha / r */
+} qfx_maxnorm_pair;
+typedef struct qfx_maxnorm_args {
+  float* p;                           /* flat adapter weights, scaled in place */
+  const qfx_maxnorm_pair* table;      /* device array */
+  int32_t n_pairs;
+  float   max_norm;                   /* > 0, +inf allowed */
+  float*  norms;                      /* [n_pairs] scaled_norm, written */
+  float*  ratios;                     /* [n_pairs] ratio, written */
+  float*  summary;                    /* [4]: keys_scaled, mean, max, 0 -- written */
+} qfx_maxnorm_args;
+int qfx_maxnorm_check_table(const qfx_maxnorm_pair* host_table, int32_t n_pairs, int64_t n_elems);
+int qfx_maxnorm_apply(const qfx_maxnorm_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

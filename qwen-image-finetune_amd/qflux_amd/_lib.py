@@ -198,6 +198,16 @@ class EmaArgs(C.Structure):
     _fields_ = [("shadow", C.c_void_p * EMA_MAX_SHADOWS), ("one_minus_decay", C.c_float * EMA_MAX_SHADOWS), ("n_shadows", C.c_int32)]
 
 
+class MaxnormPair(C.Structure):
+    _fields_ = [("off_a", C.c_int64), ("off_b", C.c_int64), ("r", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32),
+                ("scale", C.c_float)]
+
+
+class MaxnormArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("table", C.c_void_p), ("n_pairs", C.c_int32), ("max_norm", C.c_float), ("norms", C.c_void_p),
+                ("ratios", C.c_void_p), ("summary", C.c_void_p)]
+
+
 LOSS_L2, LOSS_HUBER, LOSS_SMOOTH_L1 = 0, 1, 2       # QFX_LOSS_*
 
 
@@ -313,6 +323,8 @@ SYMBOLS = {
     "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
     "qfx_ema_update": (C.c_int, [_vp, _i64, C.POINTER(EmaArgs), _vp]),
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "qfx_maxnorm_check_table": (C.c_int, [C.POINTER(MaxnormPair), _i32, _i64]),
+    "qfx_maxnorm_apply": (C.c_int, [C.POINTER(MaxnormArgs), _vp]),
     "qfx_criterion_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "qfx_criterion_fwd_bwd": (C.c_int, [C.POINTER(CriterionArgs), _vp]),
     "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),

@@ -649,6 +649,57 @@ def ema_swap(p, s):
     L.check(lib.qfx_ema_swap(_p(p), _p(s), p.numel(), stream_ptr()), "qfx_ema_swap")
 
 
+MAXNORM_MAX_RANK = 128
+
+
+class MaxnormLayout:
+    """Descriptor table of one flat-buffer layout for qfx_maxnorm_apply, built once per layout.  `pairs[i]` = (off_a, off_b, r,
+    in_features, out_features, scale) of adapter pair i; extent: elements p needs."""
+
+    def __init__(self, table, pairs, extent):
+        self.table, self.pairs, self.extent = table, pairs, extent
+        self.n_pairs = len(pairs)
+
+
+def maxnorm_table(pairs, device=None, n_elems=None):
+    """pairs: (off_a, off_b, r, in_features, out_features, scale) of every adapter pair in the flat buffer -- A [r, in] at off_a,
+    B [out, r] at off_b, scale = lora_alpha / r.  Checked by qfx_maxnorm_check_table against n_elems (default: the extent of the
+    pairs themselves) before it goes to the device."""
+    rows, extent = [], 0
+    for i, (off_a, off_b, r, nin, nout, scale) in enumerate(pairs):
+        row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(scale))
+        if row[2] > MAXNORM_MAX_RANK:
+            raise NotImplementedError(f"maxnorm table: pair {i} has rank {row[2]}: ranks above {MAXNORM_MAX_RANK} are not implemented")
+        rows.append(row)
+        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
+    if not rows:
+        raise ValueError("maxnorm table: no pairs")
+    arr = (L.MaxnormPair * len(rows))(*[L.MaxnormPair(*r) for r in rows])
+    if lib.qfx_maxnorm_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
+        raise ValueError("maxnorm table: refused by qfx_maxnorm_check_table (a dimension, an offset, an overlap or a scale)")
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return MaxnormLayout(table, rows, extent)
+
+
+def maxnorm_apply(pflat, table, max_norm, norms, ratios, summary):
+    """kohya's apply_max_norm_regularization over the flat fp32 buffer in ONE launch (plus the one-block summary): every pair of
+    `table` (a maxnorm_table) whose ||scale B A||_F exceeds max_norm is scaled onto it in place; norms / ratios [n_pairs] and
+    summary [4] = (keys_scaled, mean norm, max norm, 0) are written on the device, nothing synchronises.  See qfx.h."""
+    max_norm = float(max_norm)
+    if not max_norm > 0:
+        raise ValueError(f"maxnorm_apply: max_norm must be positive (inf allowed), not {max_norm}")
+    for name, t, n in (("pflat", pflat, table.extent), ("norms", norms, table.n_pairs), ("ratios", ratios, table.n_pairs),
+                       ("summary", summary, 4)):
+        if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < n or t.device != pflat.device:
+            raise ValueError(f"maxnorm_apply: {name} must be a contiguous float32 tensor on {pflat.device} with >= {n} elements")
+    if table.table.device != pflat.device:
+        raise ValueError("maxnorm_apply: the descriptor table lives on another device")
+    a = L.MaxnormArgs(_p(pflat), _p(table.table), table.n_pairs, max_norm, _p(norms), _p(ratios), _p(summary))
+    L.check(lib.qfx_maxnorm_apply(a, stream_ptr()), "qfx_maxnorm_apply")
+
+
 MUON_ADJUST_LR = (None, "original", "match_rms_adamw")
 MUON_MAX_SHORT_SIDE = 96
 

@@ -26,6 +26,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ema as E
+from .. import regularize as RG
 from .. import ops
 from ..dp import LoraGradSync, check_replicas, init_distributed_from_env  # noqa: F401  (the last: bench.py and tools/ import it from here)
 from ..schedules import HUBER_SCHEDULES, WEIGHTING_SCHEMES, flowmatch_tables, huber_threshold, loss_weighting, timestep_density
@@ -51,7 +52,7 @@ class QwenLoraTrainStep:
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
                  bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None, ema_decay=None,
                  ema_args=None, weighting_scheme="none", logit_mean=0.0, logit_std=1.0, mode_scale=1.29, timestep_shift=1.0,
-                 loss_type="l2", huber_c=0.1, huber_schedule="constant"):
+                 loss_type="l2", huber_c=0.1, huber_schedule="constant", max_weight_norm=None):
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
@@ -79,7 +80,13 @@ class QwenLoraTrainStep:
         with the threshold huber_c, per sample huber_c ** (timestep / 1000) under huber_schedule="exponential".  An injected u / t
         is taken as the final value: density and shift are skipped, weighting and threshold follow from it.  With unit weights
         and "l2" (every default) the step launches the two MSE kernels as before and last_sample_losses is None; otherwise the
-        general criterion kernel, after which last_sample_losses holds the per-sample losses ([B] on the device, no host sync)."""
+        general criterion kernel, after which last_sample_losses holds the per-sample losses ([B] on the device, no host sync).
+        max_weight_norm: None, a positive float or inf -- kohya's --scale_weight_norms (qflux_amd.regularize): behind every
+        optimizer step, in one launch and before the EMA update, every adapter pair whose ||scaling B A||_F exceeds the value is
+        scaled back onto it (inf: measured only).  last_weight_norms then holds the per-pair norms, ratios and the summary on the
+        device (no host sync), weight_norm_stats() reads (keys_scaled, mean norm, max norm).  Refused with
+        optimizer="adamw_schedulefree": the clamp would scale y and leave z, which breaks the average.  None: nothing is allocated
+        or launched."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
         self.optimizer_alias, self.optimizer, self._opt_cls, weight_decay, self.optimizer_args = resolve_family(optimizer, weight_decay,
@@ -107,6 +114,10 @@ class QwenLoraTrainStep:
             raise ValueError("ema_decay with optimizer='adamw_schedulefree': the schedule-free x is the averaged point already, and both "
                              "want the eval swap of the adapter weights")
         self.ema = None             # qflux_amd.ema.EmaState, from the first step, eval() or load_checkpoint on (ema_decay given)
+        self.max_weight_norm = RG.check_max_norm(max_weight_norm)
+        if self.max_weight_norm is not None and self.optimizer == "adamw_schedulefree":
+            raise ValueError("max_weight_norm with optimizer='adamw_schedulefree': scaling y and not z breaks the schedule-free average")
+        self.last_weight_norms = None     # qflux_amd.regularize.MaxNormState, from the first step on (max_weight_norm given)
         self.blockwise = optimizer in A8.BLOCKWISE
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
@@ -497,8 +508,16 @@ class QwenLoraTrainStep:
         rows, _ = self.param_groups_of(st)
         self.opt_state.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm,
                             grad_scale, self.optimizer_args, **({"groups": self._scheduled_rows(rows)} if rows else {}))
+        if self.max_weight_norm is not None:      # behind the optimizer, before the EMA: the shadows average the clamped weights
+            self.last_weight_norms = RG.ensure_state(self.last_weight_norms, st)
+            self.last_weight_norms.apply(st, self.max_weight_norm)
         if self.ema is not None:
             self.ema.update(st)     # same stream, outside a captured graph like the optimizer launches
+
+    def weight_norm_stats(self):
+        """(keys_scaled, mean norm, max norm) of the last optimizer step's max-norm launch (max_weight_norm given); synchronises.
+        None before the first step and without max_weight_norm."""
+        return None if self.last_weight_norms is None else self.last_weight_norms.stats()
 
     @property
     def _m(self):
