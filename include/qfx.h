@@ -920,6 +920,52 @@ typedef struct qfx_maxnorm_args {
 int qfx_maxnorm_check_table(const qfx_maxnorm_pair* host_table, int32_t n_pairs, int64_t n_elems);
 int qfx_maxnorm_apply(const qfx_maxnorm_args* a, void* stream);
 
+/* ---- Dropout on the rank-r activation of the adapters (kohya LoRAModule.forward: `dropout` = network_dropout, F.dropout on
+ * lx = lora_down(x); `rank_dropout`, one keep / drop draw per sample and rank, broadcast over tokens, survivors scaled by
+ * 1 / (1 - p)).  Appended under ABI 7: new structs and entry points only.
+ * With u = x A^T [tokens, r] the adapted linear becomes y = base(x) + (f * u) (sB)^T and its backward v = f * (dy sB),
+ * dB += dy^T (f * u), dA += v^T x, dX += v A, with the SAME factor f[token, rank] in both passes: 0 where the element or its rank is
+ * dropped, `scale` where it is kept.  So the outputs of a rank-r producer (qfx_lora_down[_batch], qfx_ln_down_fwd,
+ * qfx_lora_head_reduce) are multiplied by f in place, after the producer and before the first consumer, and every consumer (the
+ * K-extension GEMMs, qfx_lora_grad) runs unchanged.  The mask is never stored: both passes regenerate it from the counters below.
+ *
+ * state: 8 device words  { seed_lo, seed_hi, step, active, thr_elem, thr_rank, scale (fp32 bits), sample0 }.
+ *   thr = floor(p * 2^32), formed on the host; a draw is KEPT iff its 32-bit word >= thr (thr == 0: that option is off, nothing is
+ *   drawn for it);  scale = float32(1 / ((1 - p_elem) (1 - p_rank))), formed in double on the host.
+ * Generator: Philox4x32-10 (Random123: multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key increments 0x9E3779B9 / 0xBB67AE85, 10 rounds),
+ *   key = (seed_lo, seed_hi), counter (c0, c1, c2, c3):
+ *     c3 = site    a 32-bit key of the adapter: zlib.crc32 of the adapted module's qualified name ("transformer_blocks.3.attn.to_q")
+ *     c2 = step
+ *     c1 = sample0 + m / rows_per_batch                    the global sample index (data-parallel rank k passes sample0 = k * B)
+ *     element draw:  c0 = (m % rows_per_batch) * 32 + j' / 4      the four output words serve ranks 4q .. 4q+3 of the adapter
+ *     rank draw:     c0 = 0xFFFFFFE0 + j' / 4                     (the same for every token of the sample)
+ *   with m the row of the problem and j' = j % group_R the rank within its adapter (so group_R <= 128, rows_per_batch < 2^27 - 1).
+ *   f = keep_elem && keep_rank ? scale : 0.
+ * qfx_lora_dropout_apply: n <= QFX_MAX_BATCH problems in ONE launch; one problem = the outputs of one producer call, addressed by
+ *   the fields of the same names in qfx_lora_down_args (Ut_hi / Ut_lo required, ext may be NULL); site[g] keys group g = j / group_R
+ *   (the fused q | k | v call carries three adapters).  For row m < M and column j < R:
+ *     u = float(Ut_hi[j][m]) + float(Ut_lo[j][m]);  u' = f == 0 ? +0 : u * f (one fp32 multiply);  hi' = bf16_rne(u'), lo' = bf16_rne(u' - hi')
+ *   (the split of qfx_lora_down) written back to Ut_hi / Ut_lo and as [hi' | lo' | hi'] to the three ext images of the group.  A dropped
+ *   element becomes exact zeros; padded ranks (zero) stay zero; Ut columns >= M are not touched.  The launch returns at once,
+ *   uniformly, when active == 0 or both thresholds are 0, so a captured graph honours an eval() without being captured again.
+ *   QFX_EINVAL before any launch: NULL list / state, n outside 1..QFX_MAX_BATCH, M <= 0, R <= 0 or R % 16 or R > 96, group_R <= 0 or
+ *   group_R % 16 or R % group_R or group_R > 128 or more than 3 groups, rows_per_batch <= 0 or >= 2^27 - 1, NULL Ut_hi / Ut_lo,
+ *   ld_ut < M, and with ext: ext not 8-byte aligned, ld_ext % 4, group_stride % 4 or < 0, ld_ext short of the last group's images.
+ * qfx_lora_dropout_advance: state.step += 1 when state.active != 0, on the device (a one-lane launch): the first call of a forward
+ *   program, so that eager and captured replays advance alike and an evaluation forward does not consume training masks.
+ * qfx_lora_dropout_factors_host: HOST only, no GPU call -- out[0 .. r) = f of the token (local sample b, token t of the sample,
+ *   ranks 0 .. r-1) of adapter `site` under a host copy of the state, through the same inline function the kernel calls (`active`
+ *   is not consulted).  QFX_EINVAL for a NULL pointer, b < 0, t < 0 or t >= 2^27 - 1, r outside 1..128. ---- */
+typedef struct qfx_lora_dropout_args {
+  uint16_t* ext; int64_t ld_ext;
+  uint16_t* Ut_hi; uint16_t* Ut_lo; int64_t ld_ut;
+  int32_t M; int32_t R; int32_t group_R; int32_t group_stride; int32_t rows_per_batch;
+  uint32_t site[3];
+} qfx_lora_dropout_args;
+int qfx_lora_dropout_apply(const qfx_lora_dropout_args* list, int32_t n, const uint32_t* state, void* stream);
+int qfx_lora_dropout_advance(uint32_t* state, void* stream);
+int qfx_lora_dropout_factors_host(const uint32_t* state, uint32_t site, int32_t b, int32_t t, int32_t r, float* out);
+
 #ifdef __cplusplus
 }
 #endif

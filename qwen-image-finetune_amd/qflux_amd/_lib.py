@@ -251,6 +251,13 @@ class AttnArgs(C.Structure):
     ]
 
 
+class LoraDropoutArgs(C.Structure):
+    _fields_ = [("ext", C.c_void_p), ("ld_ext", C.c_int64),
+                ("Ut_hi", C.c_void_p), ("Ut_lo", C.c_void_p), ("ld_ut", C.c_int64),
+                ("M", C.c_int32), ("R", C.c_int32), ("group_R", C.c_int32), ("group_stride", C.c_int32), ("rows_per_batch", C.c_int32),
+                ("site", C.c_uint32 * 3)]
+
+
 ABI_VERSION = 7        # QFX_ABI_VERSION
 QFX_OK, QFX_EINVAL, QFX_EUNSUPPORTED = 0, -1, -2
 MAX_BATCH = 8          # QFX_MAX_BATCH
@@ -325,6 +332,9 @@ SYMBOLS = {
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
     "qfx_maxnorm_check_table": (C.c_int, [C.POINTER(MaxnormPair), _i32, _i64]),
     "qfx_maxnorm_apply": (C.c_int, [C.POINTER(MaxnormArgs), _vp]),
+    "qfx_lora_dropout_apply": (C.c_int, [C.POINTER(LoraDropoutArgs), _i32, _vp, _vp]),
+    "qfx_lora_dropout_advance": (C.c_int, [_vp, _vp]),
+    "qfx_lora_dropout_factors_host": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, _i32, _i32, _i32, C.POINTER(C.c_float)]),
     "qfx_criterion_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "qfx_criterion_fwd_bwd": (C.c_int, [C.POINTER(CriterionArgs), _vp]),
     "qfx_muon_ws_bytes": (_i64, [C.POINTER(MuonTensor), _i32]),

@@ -244,7 +244,7 @@ class FluxTransformer2DModel(QwenImageTransformer2DModel):
         rkey = (tuple(ids.shape), hash(ids.numpy().tobytes()))
         self._prepare()
         self._prepare_lora()
-        key = (B, S_i, T, rkey, self._version)
+        key = (B, S_i, T, rkey, self._version, self._dropout is not None)
         return self._plans.get_or_build(key, lambda: _FluxPlan(self, B, S_i, T, ids))
 
     def get_plan_multires(self, B, S_i, T, img_ids, valid_lens):
@@ -255,7 +255,7 @@ class FluxTransformer2DModel(QwenImageTransformer2DModel):
         self._prepare()
         self._prepare_lora()
         S_plan = ladder(S_i)
-        key = (B, S_plan, T, "multires", self._version)
+        key = (B, S_plan, T, "multires", self._version, self._dropout is not None)
         plan = self._plans.get_or_build(key, lambda: _FluxPlan(self, B, S_plan, T, None, multires=True))
         plan.set_multires(img_ids, valid_lens)
         return plan

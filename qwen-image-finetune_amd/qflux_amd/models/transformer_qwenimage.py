@@ -20,6 +20,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import dropout as DR
 from .. import levers
 from ..dp import DataParallelMixin
 from ..plan_cache import PlanCache, ladder
@@ -160,6 +161,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._adapter_gen = 0      # bumped ONLY by add_adapter / load_lora_adapter / load_state_dict: what a data-parallel resync keys on
         self._mod_keys = None      # timestep keys of the modulation table (None: the flow-match training timesteps / 1000)
         self._mod_table = None     # None: not decided; False: decided against; dict(keys, mods, out): see ensure_modulation_table
+        self._dropout = None       # dropout.LoraDropoutState while network_dropout / rank_dropout are on (set_lora_dropout)
 
     # ------------------------------------------------------------------ reference-surface methods
     @classmethod
@@ -241,6 +243,8 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
+        if self._dropout is not None:
+            self._dropout.words = fn(self._dropout.words)
         self._invalidate()
         return r
 
@@ -380,11 +384,58 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         None restores the bf16 trunk.  Adapters, biases, norms, attention, the rank-r gradient kernels stay bf16 / fp32."""
         if mode not in (None, "mxfp8", "mxfp8-fb"):
             raise ValueError(f"unknown trunk quantisation {mode!r} (supported: 'mxfp8' = forward GEMMs, 'mxfp8-fb' = forward + dX GEMMs)")
+        if mode is not None and self._dropout is not None:
+            raise NotImplementedError(DR.MXFP8_REFUSAL)
         self._quant = mode
         self._wq_cache = {}
         self._plans = PlanCache()
         self._version += 1
         return self
+
+    # ------------------------------------------------------------------ dropout on the adapters' rank-r activation
+    def set_lora_dropout(self, network_dropout=0.0, rank_dropout=0.0, seed=0):
+        """kohya's `network_dropout` (F.dropout on lx = lora_down(x)) and `rank_dropout` (one draw per sample and rank, survivors
+        scaled by 1 / (1 - p)) on every adapter of the blocks, the embedders and the output projection (qflux_amd.dropout).  The
+        model owns the device state (seed, the count of training forwards, thresholds); masks apply while the model is in training
+        mode and the state is enabled, and are the same in the forward and the backward pass.  Both probabilities 0 switches the
+        feature off: the plans then emit exactly the launches they emit without it (on / off is part of the plan-cache key, the
+        probabilities are not: they live in the state).  Out of scope: the MX-FP8 trunk together with dropout raises
+        NotImplementedError; adapters on the conditioning head ([B, K] vectors, cond_hip.py) run without dropout.  Returns the
+        state (None when off)."""
+        pe, pr = DR.check_probability(network_dropout, "network_dropout"), DR.check_probability(rank_dropout, "rank_dropout")
+        if pe == 0.0 and pr == 0.0:
+            if self._dropout is not None:      # (plans built with the feature off are keyed apart and stay valid)
+                self._dropout = None
+                self._plans = PlanCache()
+                self._version += 1
+            return None
+        if self._quant is not None:
+            raise NotImplementedError(DR.MXFP8_REFUSAL)
+        old = self._dropout
+        self._dropout = DR.LoraDropoutState(self.device, pe, pr, seed)
+        if old is not None:      # plans bake the state's address in (those built with the feature off are keyed apart)
+            self._dropout.enabled = old.enabled
+            self._plans = PlanCache()
+            self._version += 1
+        return self._dropout
+
+    @property
+    def lora_dropout(self):
+        """The dropout.LoraDropoutState of set_lora_dropout, None while the feature is off."""
+        return self._dropout
+
+    @contextlib.contextmanager
+    def lora_dropout_off(self):
+        """No masks inside the context (the samplers run under it), whatever the mode; the switch is restored on exit."""
+        st = self._dropout
+        was = st.enabled if st is not None else None
+        if st is not None:
+            st.enabled = False
+        try:
+            yield
+        finally:
+            if st is not None:
+                st.enabled = was
 
     # ------------------------------------------------------------------ modulation table (frozen conditioning head)
     _MOD_TABLE = True     # (the FLUX head also depends on guidance and pooled text: no table there)
@@ -696,7 +747,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
             raise ValueError("max(txt_seq_lens) must equal the text sequence length (reference RoPE broadcast)")
         self._prepare()
         self._prepare_lora()
-        key = (B, S_i, T, shapes, self._version)
+        key = (B, S_i, T, shapes, self._version, self._dropout is not None)
         return self._plans.get_or_build(key, lambda: _QwenPlan(self, B, S_i, T, shapes))
 
     def get_plan_multires(self, B, S_i, T, img_shapes, txt_seq_lens, attention_mask):
@@ -706,7 +757,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._prepare()
         self._prepare_lora()
         S_plan = ladder(S_i)
-        key = ("multires", B, S_plan, T, self._version)
+        key = ("multires", B, S_plan, T, self._version, self._dropout is not None)
         plan = self._plans.get_or_build(key, lambda: _QwenPlan(self, B, S_plan, T, None, multires=True))
         plan.set_multires(img_shapes, txt_seq_lens, attention_mask, S_in=S_i)
         return plan

@@ -700,6 +700,78 @@ def maxnorm_apply(pflat, table, max_norm, norms, ratios, summary):
     L.check(lib.qfx_maxnorm_apply(a, stream_ptr()), "qfx_maxnorm_apply")
 
 
+LORA_DROPOUT_WORDS = 8      # seed_lo, seed_hi, step, active, thr_elem, thr_rank, scale (fp32 bits), sample0 (include/qfx.h)
+
+
+def lora_dropout_threshold(p, what="dropout probability"):
+    """floor(p * 2^32) for 0 <= p < 1: a 32-bit draw is kept iff it is >= the threshold."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{what} must satisfy 0 <= p < 1, not {p}")
+    return int(math.floor(p * 4294967296.0))
+
+
+def lora_dropout_state_words(seed=0, step=0, active=1, network_dropout=0.0, rank_dropout=0.0, sample0=0):
+    """The 8 state words of qfx_lora_dropout_* as a list of Python ints (host side; see include/qfx.h)."""
+    import struct
+    te = lora_dropout_threshold(network_dropout, "network_dropout")
+    tr = lora_dropout_threshold(rank_dropout, "rank_dropout")
+    scale = 1.0 / ((1.0 - float(network_dropout)) * (1.0 - float(rank_dropout)))      # in double, rounded once to fp32
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"dropout seed must fit 64 bits, not {seed}")
+    return [seed & 0xFFFFFFFF, seed >> 32, int(step) & 0xFFFFFFFF, int(bool(active)), te, tr,
+            struct.unpack("<I", struct.pack("<f", scale))[0], int(sample0) & 0xFFFFFFFF]
+
+
+def lora_dropout_args(*, Ut, M, R, rows_per_batch, sites, ext=None, ld_ext=0, group_R=None, group_stride=0):
+    """One problem of qfx_lora_dropout_apply: the outputs of one rank-r producer call.  Ut = (hi, lo) tensors [R, >= M] (or a
+    (hi pointer, lo pointer, row stride) triple), ext a tensor (row stride ld_ext, default its own) or a pointer, or None; sites: one
+    32-bit key per group of group_R columns (up to 3)."""
+    a = L.LoraDropoutArgs()
+    if isinstance(ext, torch.Tensor):
+        ld_ext = ld_ext or ext.stride(0)
+        ext = ext.data_ptr()
+    a.ext, a.ld_ext = ext, ld_ext
+    if len(Ut) == 3:
+        a.Ut_hi, a.Ut_lo, a.ld_ut = Ut
+    else:
+        a.Ut_hi, a.Ut_lo, a.ld_ut = Ut[0].data_ptr(), Ut[1].data_ptr(), Ut[0].stride(0)
+    a.M, a.R, a.group_R, a.group_stride, a.rows_per_batch = M, R, (R if group_R is None else group_R), group_stride, rows_per_batch
+    sites = list(sites)
+    if not 1 <= len(sites) <= 3:
+        raise ValueError("lora_dropout_args: one to three site keys")
+    for i, s in enumerate(sites):
+        a.site[i] = int(s) & 0xFFFFFFFF
+    return a
+
+
+def lora_dropout_apply(problems, state):
+    """problems (lora_dropout_args, up to QFX_MAX_BATCH per launch) are multiplied in place by the factors that `state` (int32 [8]
+    on the device) yields; nothing happens on the device while state.active == 0 or both probabilities are 0."""
+    if state.dtype != torch.int32 or state.numel() < LORA_DROPOUT_WORDS or not state.is_contiguous():
+        raise ValueError("lora_dropout_apply: state must be a contiguous int32 tensor of 8 words")
+    problems = list(problems)
+    for i in range(0, len(problems), L.MAX_BATCH):
+        chunk = problems[i:i + L.MAX_BATCH]
+        arr = (L.LoraDropoutArgs * len(chunk))(*chunk)
+        L.check(lib.qfx_lora_dropout_apply(arr, len(chunk), _p(state), stream_ptr()), "qfx_lora_dropout_apply")
+
+
+def lora_dropout_advance(state):
+    """state.step += 1 on the device when state.active != 0 (what a forward program does first)."""
+    L.check(lib.qfx_lora_dropout_advance(_p(state), stream_ptr()), "qfx_lora_dropout_advance")
+
+
+def lora_dropout_factors_host(words, site, b, t, r):
+    """The factors f[0..r) of token t of local sample b of adapter `site` under the 8 host words `words`: a float32 tensor [r],
+    computed on the host by the inline function the kernel calls (no GPU)."""
+    st = (C.c_uint32 * LORA_DROPOUT_WORDS)(*[int(w) & 0xFFFFFFFF for w in words])
+    out = (C.c_float * int(r))() if r > 0 else (C.c_float * 1)()
+    L.check(lib.qfx_lora_dropout_factors_host(st, int(site) & 0xFFFFFFFF, int(b), int(t), int(r), out), "qfx_lora_dropout_factors_host")
+    return torch.tensor(list(out), dtype=torch.float32)
+
+
 MUON_ADJUST_LR = (None, "original", "match_rms_adamw")
 MUON_MAX_SHORT_SIDE = 96
 

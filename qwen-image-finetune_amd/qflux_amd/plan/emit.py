@@ -191,6 +191,18 @@ def _flush_batch(prog, pending, struct, fn, side=False):
     pending.clear()
 
 
+def _flush_dropout(prog, pending, state):
+    """Emit the collected dropout problems (ops.lora_dropout_args, one per rank-r producer call) as batched qfx_lora_dropout_apply
+    launches over the device state `state`: directly behind the producers' own flush and before the first launch that reads their
+    buffers (the K-extension GEMMs, the weight-gradient problems)."""
+    for i in range(0, len(pending), L.MAX_BATCH):
+        chunk = pending[i:i + L.MAX_BATCH]
+        arr = (L.LoraDropoutArgs * len(chunk))(*chunk)
+        prog.keep.append(arr)
+        prog.c(lib.qfx_lora_dropout_apply, arr, len(chunk), _ptr(state.words))
+    pending.clear()
+
+
 def _flush_mod_grad(prog, pending):
     for i in range(0, len(pending), L.MAX_LN_BATCH):
         chunk = pending[i:i + L.MAX_LN_BATCH]

@@ -163,6 +163,7 @@ class _FluxPlan(_QwenPlan):
         Ld, Ls = cfg.num_layers, cfg.num_single_layers
         rows, rpb, off = self.rows, self.rpb, self.off
         eps = 1e-6
+        self._emit_dropout_advance(p)
         # ---- temb = time_emb(+ guidance_emb) + pooled text emb   (CombinedTimestep(Guidance)TextProjEmbeddings)
         p.c(lib.qfx_timestep_embed, _ptr(A["t"]), B, 256, 1.0, 1000.0, _ptr(A["tproj"]))
         if self.cond:   # adapters on the conditioning head: base GEMVs + the banks' rank-r launches (cond_hip.py)
@@ -213,7 +214,7 @@ class _FluxPlan(_QwenPlan):
         sqk2 = bb["sqk"].view(M, 2 * D)
         e3 = A.get("ext3_j")
         fused = grp is not None and self._ln_down(p, [(_ln_fwd_args(x, mod[:, 0:D], mod[:, D:2 * D], 3 * D, xm, M, D, S, eps),
-                                                       dict(self._qkv_down_kw(grp, bb["Uqkv"], e3), W_fr=grp.get("A_fr")))])
+                                                       dict(self._qkv_down_kw(grp, bb["Uqkv"], e3, w["qkv"]), W_fr=grp.get("A_fr")))])
         if not fused:
             p.c(lib.qfx_ln_modulate_fwd, _ptr(x), _ptr(mod[:, 0:D]), _ptr(mod[:, D:2 * D]), 3 * D, _ptr(xm), M, D, S, eps)
         groups = []
@@ -340,6 +341,7 @@ class _FluxPlan(_QwenPlan):
             dl = []     # the q / k / v down projections of dqkv: one launch
             self._qkv_adapters_bwd(p, w["qkv"], grp, dq2, M, bb["xm"], bb["Uqkv"], A["Vt_j"], A["A2"][:, 4 * D:], down=dl, grads=gl)
             _flush_batch(p, dl, L.LoraDownArgs, lib.qfx_lora_down_batch)
+            self._flush_dropout(p)
             K2 = 4 * D + 3 * grp["Kext"]
         if ml.lora is not None:
             # proj_mlp's adapter: v = d(mlp pre-act) (sB)^T goes into the last K-extension columns of A2; dB / dA as for any site
@@ -410,5 +412,6 @@ class _FluxPlan(_QwenPlan):
         if guidance is not None:
             A["gd"].copy_(guidance.reshape(self.B).to(F32))
         self.model.refresh_lora_operands()
+        self._sync_dropout()
         self.fwd.run()
         return A["out"].view(self.B, self.S_i, -1)

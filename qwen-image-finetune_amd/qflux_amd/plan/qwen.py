@@ -10,10 +10,11 @@ from collections import namedtuple
 import torch
 
 from .. import _lib as L
+from .. import dropout as DR
 from .. import levers, ops
 from ..cond_hip import CondHeadHip
 from ..rope import normalize_img_shapes, qwen_joint_rope
-from .emit import (_down_args, _emit_or_defer, _flush_batch, _flush_head_reduce, _flush_ln, _flush_mod_grad, _gargs, _grad_args,
+from .emit import (_down_args, _emit_or_defer, _flush_batch, _flush_dropout, _flush_head_reduce, _flush_ln, _flush_mod_grad, _gargs, _grad_args,
                    _head_reduce_args, _kext, _ln_bwd_args, _ln_fwd_args, _mod_grad_args, emit_attn_backward)
 from .fp8 import _Fp8Trunk
 from .prog import _Prog, _ceil, _ptr
@@ -203,6 +204,13 @@ class _QwenPlan:
         self.A = {}
         self.lv = levers.read()   # the one look at the environment: every lever this plan consults
         self.fp8 = _Fp8Trunk(self)
+        # dropout on the adapters' rank-r activation (model.set_lora_dropout): the device state, None = off (nothing below emits)
+        self.dropout = model._dropout
+        self._dq = []             # dropout problems of deferred producers, flushed behind the producers' own flush
+        if self.dropout is not None:
+            if model._quant is not None:
+                raise NotImplementedError(DR.MXFP8_REFUSAL)
+            self._mod_names = {id(m): n for n, m in model.named_modules()}
         self.head_lora = False    # set by _alloc_double_scratch
         self.rope_bs = 0          # per-sample RoPE stride (multi-resolution plans set it)
         self.rmask = {"img": None, "txt": None, "joint": None}   # fp32 row masks of padded tokens (multi-resolution)
@@ -305,8 +313,48 @@ class _QwenPlan:
                 prog.c(lib.qfx_gemm_grouped, arr, len(groups))
         self.fp8.next_group()
 
-    def _down(self, prog, *, defer=None, **kw):
+    def _down(self, prog, *, defer=None, site=None, **kw):
+        """site: the dropout keys of the producer's adapters (_site_keys), one per group of its output columns."""
         _emit_or_defer(prog, _down_args(**kw), lib.qfx_lora_down, defer)
+        if self.dropout is not None and kw.get("Ut") is not None:
+            q = self._dq if defer is not None else []
+            self._drop_add(ext=kw.get("ext"), ld_ext=kw.get("ld_ext", 0), Ut=kw["Ut"], M=kw["M"], R=kw["R"], group_R=kw.get("group_R"),
+                           group_stride=kw.get("group_stride", 0), sites=site, queue=q)
+            if defer is None:      # a launch of its own: so is its dropout
+                self._flush_dropout(prog, q)
+
+    # ------------------------------------------------------------------ dropout on the rank-r activation (qflux_amd.dropout)
+    def _site_keys(self, *lws):
+        """The generator keys of the adapters of the prepared linears `lws` (0 for one without adapter); None with dropout off."""
+        if self.dropout is None:
+            return None
+        return tuple(0 if lw.lora is None else DR.site_key(self._mod_names[id(lw.mod)]) for lw in lws)
+
+    def _drop_add(self, *, ext, ld_ext, Ut, M, R, sites, group_R=None, group_stride=0, queue=None):
+        """Collect the dropout problem of one rank-r producer call: its transposed split Ut and K-extension image ext (the fields
+        of the producer's own arguments) are multiplied in place by f[token, rank] in the next _flush_dropout.  M rows = B samples of
+        M / B tokens each, forward and backward alike, so both passes regenerate the same mask."""
+        if self.dropout is None:
+            return
+        a = ops.lora_dropout_args(Ut=Ut, M=M, R=R, rows_per_batch=M // self.B, sites=sites, ext=ext, ld_ext=ld_ext,
+                                  group_R=group_R, group_stride=group_stride)
+        (self._dq if queue is None else queue).append(a)
+
+    def _flush_dropout(self, prog, queue=None):
+        if self.dropout is not None:
+            _flush_dropout(prog, self._dq if queue is None else queue, self.dropout)
+
+    def _emit_dropout_advance(self, prog):
+        """First call of a forward program: the state's step moves on the device, so eager and captured replays advance alike."""
+        if self.dropout is not None:
+            prog.c(lib.qfx_lora_dropout_advance, _ptr(self.dropout.words))
+
+    def _sync_dropout(self):
+        """Before a forward program runs: the state's `active` word follows the training-mode switch (nn.Dropout's rule).  Not
+        while a graph is being captured: the write would be replayed; the captured step sets the word before it replays."""
+        st = self.dropout
+        if st is not None and not torch.cuda.is_current_stream_capturing():
+            st.set_active(st.enabled and self.model.training)
 
     def _ln_down(self, prog, entries):
         """LayerNorm+modulate of up to two streams with the LoRA down projection of the adapted ones fused in (qfx_ln_down_fwd).
@@ -330,6 +378,13 @@ class _QwenPlan:
                 a.group_R, a.group_stride = d.get("group_R", d["R"]), d.get("group_stride", 0)
         prog.keep.append(arr)
         prog.c(lib.qfx_ln_down_fwd, arr, len(entries))
+        if self.dropout is not None:
+            q = []
+            for ln, d in entries:
+                if d is not None:
+                    self._drop_add(ext=d["ext"], ld_ext=d["ld_ext"], Ut=d["Ut"], M=ln.rows, R=d["R"], group_R=d.get("group_R"),
+                                   group_stride=d.get("group_stride", 0), sites=d["site"], queue=q)
+            self._flush_dropout(prog, q)
         return True
 
     def _grad(self, prog, *, defer=None, **kw):
@@ -357,7 +412,7 @@ class _QwenPlan:
         if lo is None:
             return {}
         self._down(p, X=X, ldx=ldx, M=M, K=lo.A_hi.shape[1], W_hi=lo.A_hi, W_lo=lo.A_lo, ldw=lo.A_hi.stride(0), R=lo.Rp, Ut=U,
-                   ext=ext, ld_ext=ext.stride(0), rpb=rmap[0], x_map=rmap[1], xq=xq, defer=defer)
+                   ext=ext, ld_ext=ext.stride(0), rpb=rmap[0], x_map=rmap[1], xq=xq, defer=defer, site=self._site_keys(lw))
         return _kext(ext, ext.stride(0), lo.We, lo.Kext)
 
     def _adapter_bwd(self, p, lw, dY, ldy, M, Xin, ldxin, U, V, ext, *, down=None, dB=None, dA=None, rmap=(None, (0, 0))):
@@ -370,7 +425,7 @@ class _QwenPlan:
             return {}
         K, Vt = lo.A_hi.shape[1], (V[0][:lo.Rp], V[1][:lo.Rp])
         self._down(p, X=dY, ldx=ldy, M=M, K=lw.N, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=lo.Rp, Ut=Vt,
-                   ext=ext, ld_ext=ext.stride(0), defer=down)
+                   ext=ext, ld_ext=ext.stride(0), defer=down, site=self._site_keys(lw))
         self._grad(p, Vt=U, R=lo.Rp, r_valid=lo.r, X=dY, ldx=ldy, M=M, K=lw.N, G=lo.gB, g_sr=1, g_sc=lo.r, out_scale=lo.scale, defer=dB)
         self._grad(p, Vt=Vt, R=lo.Rp, r_valid=lo.r, X=Xin, ldx=ldxin, M=M, K=K, G=lo.gA, g_sr=K, g_sc=1, rpb=rmap[0], x_map=rmap[1],
                    defer=dA)
@@ -382,14 +437,15 @@ class _QwenPlan:
         if grp is None:
             return [{}, {}, {}]
         if not fused:
-            self._down(p, X=xm, ldx=self.D, M=M, K=self.D, **self._qkv_down_kw(grp, U, ext3))
+            self._down(p, X=xm, ldx=self.D, M=M, K=self.D, **self._qkv_down_kw(grp, U, ext3, qkv))
         return [{} if lw.lora is None else _kext(ext3[:, sec * grp["Kext"]:], ext3.stride(0), lw.lora.We, lw.lora.Kext)
                 for sec, lw in enumerate(qkv)]
 
-    def _qkv_down_kw(self, grp, U, ext3):
-        """Weight and output keywords of the q/k/v group's down projection (qfx_lora_down; with W_fr: qfx_ln_down_fwd)."""
+    def _qkv_down_kw(self, grp, U, ext3, qkv):
+        """Weight and output keywords of the q/k/v group's down projection (qfx_lora_down; with W_fr: qfx_ln_down_fwd); site: the
+        dropout keys of the three prepared linears qkv."""
         return dict(W_hi=grp["A_hi"], W_lo=grp["A_lo"], ldw=self.D, R=3 * grp["Rp"], Ut=U, ext=ext3, ld_ext=ext3.stride(0),
-                    group_R=grp["Rp"], group_stride=grp["Kext"])
+                    group_R=grp["Rp"], group_stride=grp["Kext"], site=self._site_keys(*qkv))
 
     def _qkv_adapters_bwd(self, p, qkv, grp, dq2, M, xm, U, V, ext, *, down, grads, rmap=(None, (0, 0)), pq=None, reduced=False):
         """Backward of the grouped q/k/v adapters on dq2 [*, 3D] = d(q | k | v): per adapted section v = d(section) (sB)^T into its
@@ -407,7 +463,7 @@ class _QwenPlan:
             if not reduced:
                 self._down(p, X=dq2[:, sec * D:], ldx=3 * D, M=M, K=D, W_hi=lo.Bt_hi, W_lo=lo.Bt_lo, ldw=lo.Bt_hi.stride(0), R=Rp,
                            Ut=(Vth[sl], Vtl[sl]), ext=ext[:, sec * Kext:], ld_ext=ext.stride(0), rpb=rmap[0], x_map=rmap[1], defer=down,
-                           xq=None if pq is None else (_ptr(pq[0]) + sec * D, _ptr(pq[1]), 3 * D, M, sec * D // 32))
+                           site=self._site_keys(qkv[sec]), xq=None if pq is None else (_ptr(pq[0]) + sec * D, _ptr(pq[1]), 3 * D, M, sec * D // 32))
             self._grad(p, Vt=(Uth[sl], Utl[sl]), R=Rp, r_valid=lo.r, X=dq2[:, sec * D:], ldx=3 * D, M=M, K=D, G=lo.gB, g_sr=1,
                        g_sc=lo.r, rpb=rmap[0], x_map=rmap[1], out_scale=lo.scale, defer=grads)
         if all(lo is not None for lo in los):   # one pass over xm for dA of q, k and v
@@ -449,6 +505,7 @@ class _QwenPlan:
         Jd = cfg.joint_attention_dim
         rows = self.rows
         eps = 1e-6
+        self._emit_dropout_advance(p)
         # head: timestep embedding -> temb ; img_in ; txt_norm + txt_in ; all modulation vectors in one GEMV launch
         p.c(lib.qfx_timestep_embed, _ptr(A["t"]), B, 256, 1000.0, 1.0, _ptr(A["tproj"]))
         if self.cond:   # adapters on the conditioning head: base GEMVs + the banks' rank-r launches (cond_hip.py)
@@ -547,7 +604,7 @@ class _QwenPlan:
             if pq_ is not None:
                 ln.yq, ln.ys, ln.ldyq, ln.ys_rows = _ptr(pq_[0]), _ptr(pq_[1]), D, rows[s]
             lnl.append(ln)
-            ents.append((ln, None if grp is None else dict(self._qkv_down_kw(grp, bb["Uqkv." + s], e3[s]), W_fr=grp.get("A_fr"))))
+            ents.append((ln, None if grp is None else dict(self._qkv_down_kw(grp, bb["Uqkv." + s], e3[s], w[s + ".qkv"]), W_fr=grp.get("A_fr"))))
         # LayerNorm+modulate and the q/k/v down projection of its output in ONE pass over the row block (qfx_ln_down_fwd)
         fused = self._ln_down(p, ents)
         if not fused:
@@ -580,6 +637,7 @@ class _QwenPlan:
             if lo is not None and s in hl_o:
                 # u = ao A_o^T left the attention epilogue as per-head partial sums: reduce + pack (what qfx_lora_down wrote)
                 dho.append(_head_reduce_args(A["hl_o"], hl_o[s], lo.Rp, rows[s], rpb[s], S, off[s], e1[s], bb["Uo." + s], lo.Rp, 0))
+                self._drop_add(ext=e1[s], ld_ext=e1[s].stride(0), Ut=bb["Uo." + s], M=rows[s], R=lo.Rp, sites=self._site_keys(lw))
                 kw = _kext(e1[s], e1[s].stride(0), lo.We, lo.Kext)
             else:
                 # MX-FP8 trunk: the down projection reads every attention-output row of this stream anyway and leaves its
@@ -594,6 +652,7 @@ class _QwenPlan:
                                  rpb=rpb[s], a_map=(S, off[s]), **kw))
         _flush_batch(p, dfo, L.LoraDownArgs, lib.qfx_lora_down_batch)
         _flush_head_reduce(p, dho)
+        self._flush_dropout(p)
         self._gemm_group(p, groups)
         groups = []
         # feed-forward (+ LoRA on net.0.proj / net.2: the adapter's input is then kept per block instead of in scratch)
@@ -614,6 +673,7 @@ class _QwenPlan:
                                  bias=f1.b, epi=L.EPI_GELU, C2=gact[s], ldc2=4 * D,
                                  nxt=(gact[s], 4 * D, w[s + ".fc2"].lora is not None), **kw))   # gelu(h) feeds fc2 (and its adapter's dA, if any)
         _flush_batch(p, dfw, L.LoraDownArgs, lib.qfx_lora_down_batch)
+        self._flush_dropout(p)
         self._gemm_group(p, groups)
         groups = []
         for s in live:
@@ -625,6 +685,7 @@ class _QwenPlan:
                                  bias=f2.b, epi=L.EPI_GATE_RES, aux=bb["x1"][s], ldaux=D, gate=mods[s][:, 5 * D:6 * D],
                                  gate_bs=6 * D, rpb=rpb[s], c_map=x_out[s][1], aux_unmapped=1, row_mask=self.rmask[s], **kw))
         _flush_batch(p, dfw, L.LoraDownArgs, lib.qfx_lora_down_batch)
+        self._flush_dropout(p)
         self._gemm_group(p, groups)
 
     # ------------------------------------------------------------------ backward program
@@ -699,6 +760,7 @@ class _QwenPlan:
                                  ldc=4 * D, epi=L.EPI_DGELU, aux=bb["h"][s], ldaux=4 * D,
                                  nxt=(dh_[s], 4 * D, w[s + ".fc1"].lora is not None), **kw))   # dh feeds fc1's dX GEMM (and its adapter's v / dB)
         _flush_batch(p, dbw, L.LoraDownArgs, lib.qfx_lora_down_batch)
+        self._flush_dropout(p)
         self._gemm_group(p, groups)
         groups = []
         for s in live:
@@ -707,6 +769,7 @@ class _QwenPlan:
                                    down=dbw, dB=gl, dA=gl)
             groups.append(_gargs(A1=dh_[s], lda1=4 * D, B1=f1.WT, K1=4 * D, M=rows[s], N=D, C_=A["dxm"][s], ldc=D, **kw))
         _flush_batch(p, dbw, L.LoraDownArgs, lib.qfx_lora_down_batch)
+        self._flush_dropout(p)
         self._gemm_group(p, groups)
         _flush_batch(p, ge, L.LoraGradArgs, lib.qfx_lora_grad_batch)
         if dmods is not None:   # d(shift2, scale2, gate2): dy = d(xm2) (fc1 dX output), LN input x1, gate side dx2 * y2
@@ -735,6 +798,7 @@ class _QwenPlan:
             groups.append(_gargs(A1=dyg1[s], lda1=D, B1=lw.WT, K1=lw.N, M=rows[s], N=lw.K, C_=dao2, ldc=D, rpb=rpb[s],
                                  c_map=(S, off[s]), **kw))
         _flush_batch(p, dbo, L.LoraDownArgs, lib.qfx_lora_down_batch)
+        self._flush_dropout(p)
         self._gemm_group(p, groups)
         # ---- attention backward
         emit_attn_backward(p, a, A, self.lv.attn_bwd)      # two-pass pair, or the one-pass kernel (QFX_ATTN_BWD)
@@ -759,6 +823,8 @@ class _QwenPlan:
                 if s in hl_qkv:     # v = d(pre-norm q | k), dV times (sB)^T left the attention epilogues as per-head partial sums
                     dhq.append(_head_reduce_args(A["hl_qkv"], H, 3 * Rp, rows[s], rpb[s], S, off[s], e3[s],
                                                  (VtQ[s][0][:3 * Rp], VtQ[s][1][:3 * Rp]), Rp, grp["Kext"]))
+                    self._drop_add(ext=e3[s], ld_ext=e3[s].stride(0), Ut=(VtQ[s][0][:3 * Rp], VtQ[s][1][:3 * Rp]), M=rows[s], R=3 * Rp,
+                                   group_R=Rp, group_stride=grp["Kext"], sites=self._site_keys(*w[s + ".qkv"]))
                 kw = self._qkv_adapters_bwd(p, w[s + ".qkv"], grp, dq2, rows[s], bb["xm1." + s], bb["Uqkv." + s], VtQ[s], e3[s],
                                             down=dl, grads=gl, rmap=(rpb[s], (S, off[s])), pq=pq_, reduced=s in hl_qkv)
             if i > 0:   # nothing upstream of block 0 needs a gradient (frozen embedders, inputs without grad)
@@ -766,6 +832,7 @@ class _QwenPlan:
                                      rpb=rpb[s], a_map=(S, off[s]), **kw))
         _flush_batch(p, dl, L.LoraDownArgs, lib.qfx_lora_down_batch)
         _flush_head_reduce(p, dhq)
+        self._flush_dropout(p)
         if i > 0:
             self._gemm_group(p, groups)
             if dmods is not None:   # d(shift1, scale1, gate1): dy = d(xm1) (q/k/v dX output), LN input x_in, gate side dx1 * y1
@@ -851,6 +918,7 @@ class _QwenPlan:
         A["in_txt"].view(self.B, self.T, -1).copy_(encoder_hidden_states)
         A["t"].copy_(timestep.reshape(self.B).to(F32))
         self.model.refresh_lora_operands()
+        self._sync_dropout()
         self.fwd.run()
         return A["out"].view(self.B, self.S_i, -1)
 

@@ -100,7 +100,8 @@ class QwenSampler:
         schedule-free optimizer needs (its adapter weights are the gradient point y while training, the averaged x is what is
         sampled from); nothing changes for the other families or without the argument.
         Returns the final packed latents [B,S_t,64]."""
-        with (train_step.eval_mode() if train_step is not None else contextlib.nullcontext()):
+        # (no dropout masks while sampling: dit.lora_dropout_off, whatever mode the model and its train step are in)
+        with (train_step.eval_mode() if train_step is not None else contextlib.nullcontext()), self.dit.lora_dropout_off():
             return self._sample(embeddings)
 
     def _sample(self, embeddings):
@@ -165,7 +166,8 @@ class FluxSampler:
         true_cfg_scale and, for true CFG, negative_pooled_prompt_embeds / negative_prompt_embeds / negative_text_ids.
         train_step: as QwenSampler.sample -- the loop runs under train_step.eval_mode().
         Returns the final packed latents [B,S_t,64]."""
-        with (train_step.eval_mode() if train_step is not None else contextlib.nullcontext()):
+        # (no dropout masks while sampling: dit.lora_dropout_off, whatever mode the model and its train step are in)
+        with (train_step.eval_mode() if train_step is not None else contextlib.nullcontext()), self.dit.lora_dropout_off():
             return self._sample(embeddings)
 
     def _sample(self, embeddings):

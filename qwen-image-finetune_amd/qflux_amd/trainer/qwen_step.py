@@ -25,6 +25,7 @@ import re
 import torch
 import torch.distributed as dist
 
+from .. import dropout as DR
 from .. import ema as E
 from .. import regularize as RG
 from .. import ops
@@ -52,7 +53,8 @@ class QwenLoraTrainStep:
                  weight_dtype=BF, process_group=None, criterion="mse", forground_weight=2.0, background_weight=1.0,
                  bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None, ema_decay=None,
                  ema_args=None, weighting_scheme="none", logit_mean=0.0, logit_std=1.0, mode_scale=1.29, timestep_shift=1.0,
-                 loss_type="l2", huber_c=0.1, huber_schedule="constant", max_weight_norm=None):
+                 loss_type="l2", huber_c=0.1, huber_schedule="constant", max_weight_norm=None, network_dropout=None, rank_dropout=None,
+                 dropout_seed=0):
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
@@ -86,7 +88,16 @@ class QwenLoraTrainStep:
         scaled back onto it (inf: measured only).  last_weight_norms then holds the per-pair norms, ratios and the summary on the
         device (no host sync), weight_norm_stats() reads (keys_scaled, mean norm, max norm).  Refused with
         optimizer="adamw_schedulefree": the clamp would scale y and leave z, which breaks the average.  None: nothing is allocated
-        or launched."""
+        or launched.
+        network_dropout / rank_dropout / dropout_seed: kohya's dropout on the adapters' rank-r activation lx = lora_down(x) and its
+        per-sample rank dropout (qflux_amd.dropout), 0 <= p < 1, forwarded to dit.set_lora_dropout when either is given (None, None:
+        the model's setting stays).  Active while the step is in training mode (the default); eval() / eval_mode() and the samplers
+        switch the masks off, train() on again -- nn.Dropout's rule, through one device word, so a captured graph follows without
+        being captured again.  Every training forward (each micro-batch) draws new masks; with a process group rank k draws the
+        masks of samples k * B ... .  state_dict() / save_checkpoint carry {seed, step, network_dropout, rank_dropout} under the key
+        "lora_dropout" only while the feature is on, and loading restores them: a resumed run draws the masks the uninterrupted run
+        would have drawn.  Not with the MX-FP8 trunk (NotImplementedError); adapters on the conditioning head run without dropout.
+        Both 0: the plans emit exactly the launches they emit without the option."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
         self.optimizer_alias, self.optimizer, self._opt_cls, weight_decay, self.optimizer_args = resolve_family(optimizer, weight_decay,
@@ -122,6 +133,9 @@ class QwenLoraTrainStep:
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
         self.dit = dit
+        if network_dropout is not None or rank_dropout is not None:
+            pe, pr = DR.check_probability(network_dropout, "network_dropout"), DR.check_probability(rank_dropout, "rank_dropout")
+            dit.set_lora_dropout(pe, pr, dropout_seed)
         betas = OS.default_betas(self.optimizer) if betas is None else tuple(betas)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         if loraplus_lr_ratio is not None:
@@ -279,6 +293,7 @@ class QwenLoraTrainStep:
         self.dit.lora_store  # make sure the flat buffers / grads are attached
         self._refuse_in_ema_eval(E.EVAL_GRAD)
         self._ensure_synced()
+        self._stage_dropout(target.shape[0])
         pred = plan.run_forward(inputs, pe, t)
         if tok_w is None and self.criterion == "mask_edit":
             B = target.shape[0]
@@ -295,6 +310,23 @@ class QwenLoraTrainStep:
         self._mark_unexchanged()       # local gradients are added below: whatever exchange a drop-in backward did before is stale
         plan.run_backward(dpred, on_segment=self.sync.hook() if ((self.world > 1 or self.sync.force) and sync) else None)
         return loss
+
+    # ------------------------------------------------------------------ dropout on the adapters' rank-r activation
+    def _stage_dropout(self, batch, write_active=False):
+        """Before a forward: this replica's first global sample index (rank * batch) into the dropout state; write_active: also the
+        `active` word (a captured graph's forward program cannot: plan._sync_dropout)."""
+        st = getattr(self.dit, "_dropout", None)
+        if st is None:
+            return
+        rank = dist.get_rank(self.group) if self.world > 1 else 0
+        st.set_sample0(rank * batch)
+        if write_active:
+            st.set_active(st.enabled and self.dit.training)
+
+    def _set_dropout_mode(self, train):
+        st = getattr(self.dit, "_dropout", None)
+        if st is not None:
+            st.enabled = bool(train)
 
     # ------------------------------------------------------------------ hipGraph replay of the DiT part of the step
     def capture_graph(self, embeddings):
@@ -333,6 +365,9 @@ class QwenLoraTrainStep:
             plan.run_backward(dpred)
             return loss, per_sample
 
+        drop = getattr(dit, "_dropout", None)
+        drop_step = None if drop is None else drop.step()      # the warm-up pass below draws masks: its step is given back
+        self._stage_dropout(packed.shape[0], write_active=True)
         warm = torch.cuda.Stream(device=dit.device)     # one eager pass on a non-default stream (lazy module loads, pool warm-up)
         warm.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(warm):
@@ -343,6 +378,8 @@ class QwenLoraTrainStep:
         with torch.cuda.graph(graph):
             loss_static, per_sample_static = body()
         self.zero_grad()
+        if drop is not None:
+            drop.set_step(drop_step)
         shapes = [tuple(t.shape) for t in static]
 
         def step(emb, noise=None, u=None):
@@ -360,6 +397,7 @@ class QwenLoraTrainStep:
                     d.copy_(s_)
             self._ensure_synced()
             self._mark_unexchanged()
+            self._stage_dropout(shapes[0][0], write_active=True)
             graph.replay()
             self.sync.disarm()
             self.optimizer_step(grad_scale=self.allreduce_grads())
@@ -468,6 +506,7 @@ class QwenLoraTrainStep:
         each pass: no plan is rebuilt) go from y to the averaged x that is sampled from and saved -- the package's optimizer.eval().
         With ema_decay: EMA shadow `ema` is exchanged with the adapter weights.  Nothing happens in eval mode already (the same
         shadow), and for every other family without EMA."""
+        self._set_dropout_mode(False)
         if self.ema_decays is not None:
             self._ensure_ema().swap_in(self.dit.lora_store, ema)
         else:
@@ -476,6 +515,7 @@ class QwenLoraTrainStep:
     def train(self):
         """Back from x to y (the package's optimizer.train()), or the trained weights back in place of the EMA shadow, bit for bit;
         nothing happens in train mode already, and for every other family without EMA."""
+        self._set_dropout_mode(True)
         if self.ema_decays is not None:
             if self.ema is not None:
                 self.ema.swap_out(self.dit.lora_store)
@@ -486,12 +526,15 @@ class QwenLoraTrainStep:
     def eval_mode(self, ema=0):
         """`with step.eval_mode():` -- eval() on entry, train() on exit if the step was in train mode before."""
         was = self.train_mode
+        drop = getattr(self.dit, "_dropout", None)
+        drop_was = drop.enabled if drop is not None else True
         self.eval(ema)
         try:
             yield self
         finally:
             if was:
                 self.train()
+            self._set_dropout_mode(drop_was)
 
     def optimizer_step(self, grad_scale=1.0):
         self._refuse_in_ema_eval(E.EVAL_STEP)
@@ -545,14 +588,24 @@ class QwenLoraTrainStep:
         or bitsandbytes' (optim_state)."""
         st = self.dit.lora_store
         rows, members = self.param_groups_of(st)
-        return OS.state_dict(self._opt_cls, self.opt_state, st, self.global_step, self.optimizer_args, self.lr, self.betas,
-                             self.eps, self.weight_decay, groups=self._scheduled_rows(rows, initial=True), members=members)
+        sd = OS.state_dict(self._opt_cls, self.opt_state, st, self.global_step, self.optimizer_args, self.lr, self.betas,
+                           self.eps, self.weight_decay, groups=self._scheduled_rows(rows, initial=True), members=members)
+        drop = getattr(self.dit, "_dropout", None)
+        if drop is not None:      # only while the feature is on: no new key otherwise
+            sd[DR.STATE_KEY] = drop.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         """With param_groups the file must hold the same groups (torch's ValueError otherwise): every group takes the file's betas,
         eps and weight_decay, and its lr as the unscheduled one -- the file's "initial_lr" where it has one (the schedule's factor
         lr / initial_lr then comes back into self.lr), else its lr (factor 1)."""
         st = self.dit.lora_store
+        if DR.STATE_KEY in sd:      # seed, probabilities and the count of training forwards: the masks continue where the file left
+            d = sd[DR.STATE_KEY]
+            sd = {k: v for k, v in sd.items() if k != DR.STATE_KEY}
+            drop = self.dit.set_lora_dropout(d["network_dropout"], d["rank_dropout"], d["seed"])
+            if drop is not None:
+                drop.set_step(d["step"])
         rows, members = self.param_groups_of(st)
         hyper = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
         file_rows = None if rows is None else [dict(r, initial_lr=None) for r in rows]
