@@ -653,6 +653,63 @@ typedef struct qfx_adafactor_args {
 } qfx_adafactor_args;
 int qfx_adafactor_step(const qfx_adafactor_args* a, void* stream);
 
+/* ---- CAME (Luo et al., "CAME: Confidence-guided Adaptive Memory Efficient Optimization", 2023; third party came_pytorch.CAME, the
+ * optimizer LoRA fine-tuning stacks offer next to AdamW8bit, Adafactor and Prodigy; in the reference one YAML line through the generic
+ * optimizer.class_path at base_trainer.py:884-909, stepped at :531 after clip_gradients :449-455).  Adafactor's factored second
+ * moment, a full first moment, and a second factored pair over the instability (upd - m)^2 that rescales the momentum.  ONE launch
+ * steps every tensor of the flat fp32 LoRA buffers, one workgroup per tensor, driven by a device table the caller builds once per
+ * buffer layout.  Per tensor of rows x cols elements, with g' = g * clip (clip exactly as qfx_adamw_step computes it from gnorm_sq /
+ * max_norm / grad_scale), everything in fp32, every operation rounded on its own (never contracted into an FMA):
+ *   RMS = |p|_2 / sqrt(numel) (before the update, stored in rms[]; the package keeps it, the update does not read it)
+ *   u = g'^2 + eps1
+ *   factored:    row = beta2 row + (1 - beta2) mean(u, cols),  col = beta2 col + (1 - beta2) mean(u, rows)
+ *                upd = (rsqrt(row / mean(row)) [:, None] * rsqrt(col) [None, :]) * g'
+ *   unfactored:  v = beta2 v + (1 - beta2) u,  upd = rsqrt(v) * g'
+ *   upd = upd / max(1, rms(upd) / clip_threshold);  m = beta1 m + (1 - beta1) upd
+ *   factored:    res = (upd - m)^2 + eps2
+ *                rrow = beta3 rrow + (1 - beta3) mean(res, cols),  rcol = beta3 rcol + (1 - beta3) mean(res, rows)
+ *                out = (rsqrt(rrow / mean(rrow)) [:, None] * rsqrt(rcol) [None, :]) * m
+ *   unfactored:  out = m
+ *   weight_decay != 0: p += p * (-weight_decay * lr);  p -= lr * out
+ * There is no relative step and no parameter scaling: lr is always external, beta2 is a constant, and lr multiplies `out` at the
+ * end, not the update that enters m.  The caller forms 1 - beta1, 1 - beta2, 1 - beta3 in double and rounds to fp32.  A tensor whose
+ * g' holds a non-finite value is skipped whole: p, its five statistics, m and rms[] stay as they were; the other tensors step.
+ * Every reduction runs inside the tensor's workgroup in an order fixed by its shape (per-lane strided sums over groups of four
+ * columns, xor-shuffle trees, fixed folds through LDS), no atomics: same inputs -> same bits.  16-byte accesses where the tensor
+ * starts on a 16-byte boundary in p, g and m and cols is a multiple of 4; the order of every sum is the same without.  p, g and m
+ * are indexed by `off`; every buffer must be non-NULL (allocate one element for an unused one).  Rejected with QFX_EINVAL before
+ * any launch: n_tensors < 0, with n_tensors > 0 a NULL table or buffer, a negative lr, a beta or its complement outside [0, 1],
+ * clip_threshold <= 0, negative eps1 / eps2 / weight_decay.  n_tensors == 0 does nothing.  The table itself lives on the device and
+ * cannot be checked here: its builder bounds rows * cols by 2^30 and every offset by its buffer. ---- */
+typedef struct qfx_came_tensor {
+  int64_t off;           /* first element of the tensor in p / g / m */
+  int64_t row;           /* factored: first of its `rows` elements in row */
+  int64_t col;           /* factored: first of its `cols` elements in col */
+  int64_t rrow;          /* factored: first of its `rows` elements in rrow */
+  int64_t rcol;          /* factored: first of its `cols` elements in rcol */
+  int64_t v;             /* unfactored: first of its `cols` elements in v */
+  int32_t rows, cols;    /* the matrix; an unfactored tensor is 1 x numel */
+  int32_t rms;           /* index into rms */
+  int32_t factored;      /* 1: two dimensions */
+} qfx_came_tensor;
+typedef struct qfx_came_args {
+  float* p;              /* parameters, updated in place */
+  const float* g;        /* gradient (summed over ranks / micro-steps; scaled by grad_scale and the clip factor on the fly) */
+  float* row;            /* exp_avg_sq_row of every factored tensor */
+  float* col;            /* exp_avg_sq_col */
+  float* rrow;           /* exp_avg_res_row */
+  float* rcol;           /* exp_avg_res_col */
+  float* v;              /* exp_avg_sq of every unfactored tensor */
+  float* m;              /* exp_avg, indexed like p */
+  float* rms;            /* one RMS per tensor */
+  const qfx_came_tensor* table;   /* device array of n_tensors entries */
+  int32_t n_tensors;
+  float lr, beta1, one_minus_beta1, beta2, one_minus_beta2, beta3, one_minus_beta3, eps1, eps2, clip_threshold, weight_decay;
+  const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq_det) for the global-norm clip */
+  float max_norm, grad_scale;
+} qfx_came_args;
+int qfx_came_step(const qfx_came_args* a, void* stream);
+
 /* ---- Lion (Chen et al., "Symbolic Discovery of Optimization Algorithms", 2023; third party lion_pytorch.Lion and
  * bitsandbytes.optim.Lion / Lion8bit / PagedLion8bit, the one-moment optimizer LoRA fine-tuning stacks offer next to the ones above;
  * in the reference one YAML line through the generic optimizer.class_path at base_trainer.py:884-909, stepped at :531 after

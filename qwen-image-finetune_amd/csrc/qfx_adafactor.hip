@@ -5,19 +5,11 @@
 // no atomics, same inputs -> same bits.  A tensor is 0.2 - 3 MB of fp32 and is swept several times; after the first sweep it is
 // read from L2.
 #include "qfx_common.h"
+#include "qfx_optim.h"      // block_sum
 
 namespace {
 
 constexpr int NT = 256;
-
-// sum over the 256 threads, the same bits on every thread.  `red` may still be read by the previous call: barrier first.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __global__ __launch_bounds__(256) void adafactor_kernel(const qfx_adafactor_args a) {
   __shared__ float red[4];

@@ -25,6 +25,16 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// sum over the 256 threads of a workgroup, the same bits on every thread (qfx_adafactor.hip, qfx_came.hip).  `red` (4 floats of
+// LDS) may still be read by the previous call: barrier first.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // number of midpoints below x (mid[255] = +inf): the nearest code, a tie (x == midpoint) going to the lower one
 __device__ __forceinline__ int nearest_code(const float* mid, float x) {
   int c = 0;

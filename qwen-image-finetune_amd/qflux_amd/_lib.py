@@ -151,6 +151,20 @@ class AdafactorArgs(C.Structure):
                 ("grad_scale", C.c_float)]
 
 
+class CameTensor(C.Structure):
+    _fields_ = [("off", C.c_int64), ("row", C.c_int64), ("col", C.c_int64), ("rrow", C.c_int64), ("rcol", C.c_int64), ("v", C.c_int64),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("rms", C.c_int32), ("factored", C.c_int32)]
+
+
+class CameArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("row", C.c_void_p), ("col", C.c_void_p), ("rrow", C.c_void_p), ("rcol", C.c_void_p),
+                ("v", C.c_void_p), ("m", C.c_void_p), ("rms", C.c_void_p), ("table", C.c_void_p), ("n_tensors", C.c_int32),
+                ("lr", C.c_float), ("beta1", C.c_float), ("one_minus_beta1", C.c_float), ("beta2", C.c_float),
+                ("one_minus_beta2", C.c_float), ("beta3", C.c_float), ("one_minus_beta3", C.c_float), ("eps1", C.c_float),
+                ("eps2", C.c_float), ("clip_threshold", C.c_float), ("weight_decay", C.c_float), ("gnorm_sq", C.c_void_p),
+                ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
 class Lion8bitArgs(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("q1", C.c_void_p), ("absmax1", C.c_void_p), ("m32", C.c_void_p),
                 ("table", C.c_void_p), ("n_blocks", C.c_int32), ("blocksize", C.c_int32), ("qmap1", C.c_void_p),
@@ -322,6 +336,7 @@ SYMBOLS = {
     "qfx_adam8bit_step": (C.c_int, [C.POINTER(Adam8bitArgs), _vp]),
     "qfx_adam8bit_step_grouped": (C.c_int, [C.POINTER(Adam8bitArgs), _vp, C.POINTER(Adam8bitGroup), _i32, _vp]),
     "qfx_adafactor_step": (C.c_int, [C.POINTER(AdafactorArgs), _vp]),
+    "qfx_came_step": (C.c_int, [C.POINTER(CameArgs), _vp]),
     "qfx_lion_step": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _vp, _f, _f, _vp]),
     "qfx_lion8bit_step": (C.c_int, [C.POINTER(Lion8bitArgs), _vp]),
     "qfx_lion_step_grouped": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.POINTER(LionGroup), _i32, _vp, _f, _f, _vp]),

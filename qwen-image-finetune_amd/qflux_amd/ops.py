@@ -928,6 +928,83 @@ def adafactor_step(p, g, row, col, v, m, rms, layout, step, lr=None, eps=(1e-30,
     L.check(lib.qfx_adafactor_step(a, stream_ptr()), "qfx_adafactor_step")
 
 
+class CameLayout:
+    """Descriptor table of one flat-buffer layout for qfx_came_step, built once per layout.  `tensors[i]` = (off, rows, cols,
+    factored, first element in row / rrow, in col / rcol, in v) of entry i (-1 where the entry has none); n_row / n_col / n_v:
+    elements the row and rrow / col and rcol / v buffers need; extent: elements p / g / m need."""
+
+    def __init__(self, table, tensors, n_row, n_col, n_v, extent):
+        self.table, self.tensors, self.n_row, self.n_col, self.n_v, self.extent = table, tensors, n_row, n_col, n_v, extent
+        self.n_tensors = len(tensors)
+
+
+def came_table(entries, device=None):
+    """entries: (offset, shape) of every tensor in the flat buffers.  A 2-D tensor is factored (rows + cols statistics of the squared
+    gradient and of the instability, packed in entry order), a 1-D one keeps an elementwise second moment in v; more dimensions are
+    refused.  exp_avg is indexed like the parameters.  The bounds are adafactor_table's."""
+    rows_, tensors, n_row, n_col, n_v, extent = [], [], 0, 0, 0, 0
+    for i, (off, shape) in enumerate(entries):
+        off, shape = int(off), tuple(int(d) for d in shape)
+        if len(shape) not in (1, 2):
+            raise ValueError(f"came table: entry {i} has {len(shape)} dimensions (adapter matrices are 2-D; only 1-D and 2-D are implemented)")
+        numel = 1
+        for d in shape:
+            numel *= d
+        if off < 0 or numel <= 0 or numel > 1 << 30:
+            raise ValueError(f"came table: entry {i}: offset {off} / shape {shape}")
+        if len(shape) == 2:
+            tensors.append((off, shape[0], shape[1], True, n_row, n_col, -1))
+            rows_.append((off, n_row, n_col, n_row, n_col, 0, shape[0], shape[1], i, 1))
+            n_row, n_col = n_row + shape[0], n_col + shape[1]
+        else:
+            tensors.append((off, 1, numel, False, -1, -1, n_v))
+            rows_.append((off, 0, 0, 0, 0, n_v, 1, numel, i, 0))
+            n_v += numel
+        extent = max(extent, off + numel)
+    if not rows_:
+        raise ValueError("came table: no tensors")
+    arr = (L.CameTensor * len(rows_))(*[L.CameTensor(*r) for r in rows_])
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return CameLayout(table, tensors, n_row, n_col, n_v, extent)
+
+
+def came_check(lr, betas, eps, clip_threshold, weight_decay=0.0):
+    """What a CAME launch needs of its scalars: a betas triple and an eps pair, every beta in [0, 1] (came_pytorch.CAME's constructor
+    check), a learning rate >= 0 (the package asks > 0 of its constructor; a schedule may pass through 0)."""
+    if not isinstance(betas, (tuple, list)) or len(betas) != 3:
+        raise ValueError(f"CAME's betas is a triple (beta1, beta2, beta3), not {betas!r}")
+    if not isinstance(eps, (tuple, list)) or len(eps) != 2:
+        raise ValueError(f"CAME's eps is a pair (eps1, eps2), not {eps!r}")
+    if lr is None or not float(lr) >= 0.0:
+        raise ValueError(f"CAME needs a learning rate >= 0, not {lr!r}")
+    if not all(0.0 <= float(b) <= 1.0 for b in betas):
+        raise ValueError(f"Invalid betas value: {tuple(betas)} (each in [0, 1])")
+    if not float(clip_threshold) > 0 or float(eps[0]) < 0 or float(eps[1]) < 0 or float(weight_decay) < 0:
+        raise ValueError(f"CAME: clip_threshold must be positive, eps and weight_decay non-negative ({clip_threshold}, {eps}, {weight_decay})")
+
+
+def came_step(p, g, row, col, rrow, rcol, v, m, rms, layout, lr, betas=(0.9, 0.999, 0.9999), eps=(1e-30, 1e-16), clip_threshold=1.0,
+              weight_decay=0.0, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """One CAME step (came_pytorch.CAME) over the flat buffers p / g; see qfx.h.  row, rrow / col, rcol / v: fp32 with >= layout.n_row
+    / n_col / n_v elements (one when unused); m: fp32 like p; rms: fp32[layout.n_tensors]."""
+    came_check(lr, betas, eps, clip_threshold, weight_decay)
+    f32 = torch.float32
+    for name, t, need in (("p", p, layout.extent), ("g", g, layout.extent), ("m", m, layout.extent), ("row", row, max(1, layout.n_row)),
+                          ("col", col, max(1, layout.n_col)), ("rrow", rrow, max(1, layout.n_row)), ("rcol", rcol, max(1, layout.n_col)),
+                          ("v", v, max(1, layout.n_v)), ("rms", rms, layout.n_tensors)):
+        if t is None or t.dtype != f32 or not t.is_cuda or not t.is_contiguous() or t.numel() < need or t.device != p.device:
+            raise ValueError(f"came_step: {name} must be a contiguous float32 tensor on {p.device} with >= {need} elements")
+    if layout.table.device != p.device:
+        raise ValueError("came_step: the descriptor table lives on another device")
+    b1, b2, b3 = (float(b) for b in betas)
+    a = L.CameArgs(_p(p), _p(g), _p(row), _p(col), _p(rrow), _p(rcol), _p(v), _p(m), _p(rms), _p(layout.table), layout.n_tensors,
+                   float(lr), b1, 1.0 - b1, b2, 1.0 - b2, b3, 1.0 - b3, float(eps[0]), float(eps[1]), float(clip_threshold),
+                   float(weight_decay), _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_came_step(a, stream_ptr()), "qfx_came_step")
+
+
 # ---------------------------------------------------------------------------------------------- MX-FP8 (low-precision trunk)
 def quant_mxfp8(x, M=None, rows_per_batch=None, x_map=(0, 0), out=None):
     """x [*, K] bf16 (row stride x.stride(0)) -> (q uint8 [M, K], s uint8 [K/128, M, 4] tile-major scales) in the OCP MX-FP8

@@ -1,7 +1,7 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
@@ -9,7 +9,7 @@ the two ways of driving the model and with the original packages'.
 
 `params` must be exactly the adapter parameters of ONE model: a plain list, or torch's list of group dicts whose union is that set,
 each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit and PagedLion8bit step several groups
-in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); Prodigy, Adafactor,
+in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); Prodigy, Adafactor, CAME,
 Muon and AdamWScheduleFree refuse a second group.  loraplus_param_groups builds the two LoRA+ groups.  The loop has clipped already
 (accelerator.clip_grad_norm_, base_trainer.py:449-455), so step() launches without the fused clip; lr, betas, eps, weight_decay and
 the family's own fields are read from every param_groups[k] at every step (schedulers write there).  step() never synchronises
@@ -22,7 +22,7 @@ import torch
 from .trainer import optim_state as OS
 from .trainer.optim_config import optimizer_kwargs_from_config
 
-__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree",
+__all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "CAME", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree",
            "loraplus_param_groups"]
 
 
@@ -233,6 +233,15 @@ class Adafactor(_FlatOptimizer):
                  scale_parameter=True, relative_step=True, warmup_init=False):
         super().__init__(params, lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
                          weight_decay=weight_decay, scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init)
+
+
+class CAME(_FlatOptimizer):
+    """came_pytorch.CAME (Adafactor's factored second moments, a full first moment rescaled by a factored estimate of its
+    instability).  betas is the package's triple, eps its pair; lr is required and > 0."""
+    _PATH = "qflux_amd.optim.CAME"
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-16), clip_threshold=1.0, betas=(0.9, 0.999, 0.9999), weight_decay=0.0):
+        super().__init__(params, lr=lr, eps=eps, clip_threshold=clip_threshold, betas=betas, weight_decay=weight_decay)
 
 
 class Lion(_FlatOptimizer):

@@ -18,6 +18,7 @@ _FAMILY = {
     "qflux_amd.optim.Lion8bit": _LION8[0], "qflux_amd.optim.PagedLion8bit": _LION8[0],
     "prodigyopt.Prodigy": "prodigy", "qflux_amd.optim.Prodigy": "prodigy", "qflux_amd.optim.SGD": "sgd",
     "transformers.optimization.Adafactor": "adafactor", "transformers.Adafactor": "adafactor", "qflux_amd.optim.Adafactor": "adafactor",
+    "came_pytorch.CAME": "came", "came_pytorch.CAME.CAME": "came", "qflux_amd.optim.CAME": "came",
     "torch.optim.Muon": "muon", "qflux_amd.optim.Muon": "muon",
     "schedulefree.AdamWScheduleFree": "adamw_schedulefree", "qflux_amd.optim.AdamWScheduleFree": "adamw_schedulefree",
 }
@@ -63,6 +64,10 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         schedulefree.AdamWScheduleFree / qflux_amd.optim.AdamWScheduleFree -> optimizer="adamw_schedulefree" + optimizer_args
     (warmup_steps, r, weight_lr_power); lr and weight decay left out are the class's 0.0025 and 0; foreach is dropped.  Keep the
     reference's lr_scheduler at `constant`: the warm-up is the optimizer's own warmup_steps.
+        came_pytorch.CAME / came_pytorch.CAME.CAME / qflux_amd.optim.CAME -> optimizer="came" + optimizer_args (eps pair,
+    clip_threshold); betas is the package's triple (left out: (0.9, 0.999, 0.9999)); lr is required and > 0 (the package's assert),
+    weight decay left out is 0; a betas that is no triple, an eps that is no pair, a beta outside [0, 1] and any other keyword are
+    refused.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -88,6 +93,14 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
             OS.MuonState.validate(dict(OS.MuonState.DEFAULTS, **args))
             if "ns_coefficients" in args:
                 args["ns_coefficients"] = tuple(float(c) for c in args["ns_coefficients"])
+        out["optimizer_args"] = args
+    elif fam == "came":
+        # eps is the family's own pair, read before the common keywords below; betas is its triple and travels as betas
+        args = _take(a, OS.CameState)
+        if "eps" in args and isinstance(args["eps"], (tuple, list)):
+            args["eps"] = tuple(float(e) for e in args["eps"])
+        betas = tuple(float(b) for b in a["betas"]) if isinstance(a.get("betas"), (tuple, list)) else a.get("betas")
+        OS.CameState.validate(dict(OS.CameState.DEFAULTS, **args), a.get("lr"), OS.CameState.BETAS if betas is None else betas)
         out["optimizer_args"] = args
     for k in ("lr", "eps", "weight_decay"):
         if k in a:

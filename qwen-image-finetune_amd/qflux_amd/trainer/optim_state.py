@@ -1,6 +1,6 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
 file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
-AdafactorState (transformers.optimization.Adafactor's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
+AdafactorState (transformers.optimization.Adafactor's), CameState (came_pytorch.CAME's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
 Lion8bit), MuonState (torch.optim.Muon's) and ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
@@ -539,6 +539,105 @@ class AdafactorState(FlatState):
         return state, step
 
 
+class CameState(FlatState):
+    """came_pytorch.CAME: Adafactor's factored second moments of every adapter matrix (row, col), a second factored pair over the
+    instability (rrow, rcol: exp_avg_res_row / exp_avg_res_col), an elementwise second moment (v) for 1-D tensors, the RMS of every
+    tensor as of its last step (kept as the package keeps it; the update does not read it), and exp_avg (m) indexed like pflat.
+    Zeros are the package's initial state.  `eps` is the package's pair (added to the squared gradient, to the instability) and
+    lives in the optimizer_args: the train step's own eps is unused.  `betas` is the package's TRIPLE and travels where the other
+    families' pair does (the train steps' betas=, the group's "betas"): default_betas("came")."""
+    NAMES = ("row", "col", "rrow", "rcol", "v", "rms", "m")
+    FAMILY = "CAME"
+    DEFAULTS = dict(eps=(1e-30, 1e-16), clip_threshold=1.0)
+    BETAS = (0.9, 0.999, 0.9999)
+    # per-parameter keys of came_pytorch's state_dict, restated from the published source (came_pytorch/CAME.py, step()); NOT checked
+    # against an installed package
+    FACTORED_KEYS = ("step", "RMS", "exp_avg", "exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_res_row", "exp_avg_res_col")
+    UNFACTORED_KEYS = ("step", "RMS", "exp_avg", "exp_avg_sq")
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        dev = store.pflat.device
+        self.layout = ops.came_table([(off, p.shape) for _, p, off, _ in store.entries], device=dev)
+        z = lambda n: torch.zeros(max(1, n), dtype=torch.float32, device=dev)
+        self.row, self.col, self.rrow, self.rcol = z(self.layout.n_row), z(self.layout.n_col), z(self.layout.n_row), z(self.layout.n_col)
+        self.v, self.rms = z(self.layout.n_v), z(self.layout.n_tensors)
+        self.m = torch.zeros_like(store.pflat)
+
+    @classmethod
+    def _base_key(cls, store, args):
+        return super()._base_key(store, args) + (tuple(tuple(p.shape) for _, p, _, _ in store.entries),)
+
+    @staticmethod
+    def validate(args, lr=False, betas=None):
+        """The package's constructor checks; lr=False / betas=None: not known here."""
+        eps = args["eps"]
+        if not isinstance(eps, (tuple, list)) or len(eps) != 2:
+            raise ValueError(f"CAME's eps is a pair (eps1, eps2), not {eps!r}")
+        args["eps"] = (float(eps[0]), float(eps[1]))
+        if not args["clip_threshold"] > 0:
+            raise ValueError(f"Invalid clip_threshold value: {args['clip_threshold']}")
+        if args["eps"][0] < 0 or args["eps"][1] < 0:
+            raise ValueError(f"Invalid eps value: {args['eps']}")
+        if lr is not False and (lr is None or not float(lr) > 0.0):        # the constructor's rule; a schedule may pass through 0 later
+            raise ValueError(f"CAME needs a learning rate > 0, not {lr!r}")
+        if betas is not None:
+            ops.came_check(1.0, betas, args["eps"], args["clip_threshold"])
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args):
+        self.validate(args, betas=betas)
+        ops.came_step(store.pflat, store.gflat, self.row, self.col, self.rrow, self.rcol, self.v, self.m, self.rms, self.layout, lr,
+                      betas=betas, eps=args["eps"], clip_threshold=args["clip_threshold"], weight_decay=weight_decay, gnorm_sq=gnorm_sq,
+                      max_norm=max_norm, grad_scale=grad_scale)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """came_pytorch's layout: per parameter FACTORED_KEYS (two dimensions: exp_avg_sq_row / exp_avg_res_row [rows], exp_avg_sq_col
+        / exp_avg_res_col [cols]) or UNFACTORED_KEYS (one); the group carries eps (the pair) and clip_threshold next to lr, betas (the
+        triple) and weight_decay."""
+        group = {n: args[n] for n in cls.DEFAULTS}
+        if state is None or step == 0:
+            return group, {}
+        per = {}
+        for i, (_, p, off, k) in enumerate(entries):
+            _, rows, cols, factored, r0, c0, v0 = state.layout.tensors[i]
+            e = {"step": step, "RMS": state.rms[i].detach().cpu().clone(), "exp_avg": _out(state.m, off, k, p.shape)}
+            if factored:
+                e["exp_avg_sq_row"], e["exp_avg_sq_col"] = _out(state.row, r0, rows), _out(state.col, c0, cols)
+                e["exp_avg_res_row"], e["exp_avg_res_col"] = _out(state.rrow, r0, rows), _out(state.rcol, c0, cols)
+            else:
+                e["exp_avg_sq"] = _out(state.v, v0, k, p.shape)
+            per[i] = e
+        return group, per
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """Every statistic must have the shape the parameter implies."""
+        cls.group_args(sd, args)
+        if not sd["state"]:
+            return None, 0
+        state, step, rms = cls(store, args), 0, [0.0] * len(store.entries)
+        for i, p, off, k, e in cls.file_entries(store, sd):
+            _, rows, cols, factored, r0, c0, v0 = state.layout.tensors[i]
+            want = {"exp_avg": tuple(p.shape)}
+            if factored:
+                want.update(exp_avg_sq_row=(rows,), exp_avg_sq_col=(cols,), exp_avg_res_row=(rows,), exp_avg_res_col=(cols,))
+            else:
+                want["exp_avg_sq"] = tuple(p.shape)
+            for n, shape in want.items():
+                cls.field(i, p, e, n, shape=shape)
+            state.m[off:off + k].copy_(e["exp_avg"].reshape(-1))
+            if factored:
+                state.row[r0:r0 + rows].copy_(e["exp_avg_sq_row"]); state.col[c0:c0 + cols].copy_(e["exp_avg_sq_col"])
+                state.rrow[r0:r0 + rows].copy_(e["exp_avg_res_row"]); state.rcol[c0:c0 + cols].copy_(e["exp_avg_res_col"])
+            else:
+                state.v[v0:v0 + k].copy_(e["exp_avg_sq"].reshape(-1))
+            rms[i] = float(e.get("RMS", 0.0))
+            step = max(step, int(float(e["step"])))
+        state.rms.copy_(torch.tensor(rms, dtype=torch.float32))
+        return state, step
+
+
 class LionState(FlatState):
     """lion_pytorch.Lion / bitsandbytes.optim.Lion: the one moment exp_avg in fp32, indexed like pflat.  eps is unused."""
     NAMES = ("exp_avg",)
@@ -754,6 +853,7 @@ class ScheduleFreeAdamWState(FlatState):
 LION = ("lion",) + A8.LION_BLOCKWISE
 # optimizer= name -> (state class, the weight decay that weight_decay=None stands for: the stood-in optimizer class's own default)
 FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": (SgdState, 0.0), "adafactor": (AdafactorState, 0.0),
+            "came": (CameState, 0.0),
             "lion": (LionState, 0.0), "muon": (MuonState, 0.1), "adamw_schedulefree": (ScheduleFreeAdamWState, 0.0),
             "adam8bit_blockwise": (BlockwiseState, 0.0), "adamw8bit_blockwise": (BlockwiseState, 0.01),
             "lion8bit_blockwise": (LionBlockwiseState, 0.0)}
@@ -761,8 +861,10 @@ FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": 
 
 def default_betas(optimizer):
     """The betas a train step uses when its caller gives none: the optimizer class's own default -- (0.9, 0.99) for Lion (both
-    packages), (0.9, 0.999) for every other family (torch.optim.AdamW's and schedulefree.AdamWScheduleFree's, the train steps' default
-    so far)."""
+    packages), came_pytorch.CAME's triple (0.9, 0.999, 0.9999) for CAME, (0.9, 0.999) for every other family (torch.optim.AdamW's and
+    schedulefree.AdamWScheduleFree's, the train steps' default so far)."""
+    if optimizer == "came":
+        return CameState.BETAS
     return (0.9, 0.99) if optimizer in LION else (0.9, 0.999)
 
 
@@ -782,6 +884,10 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     scaled by the step's learning rate, default 0); optimizer_args: eps ((1e-30, 1e-3)), clip_threshold (1.0), decay_rate (-0.8),
     beta1 (None), scale_parameter (True), relative_step (True), warmup_init (False).  lr must be None with relative_step (the
     default) and a float without it; betas / eps unused.
+    "came": came_pytorch.CAME (Luo et al. 2023: Adafactor's factored second moments, a full first moment, and a second factored pair
+    over the instability (update - moment)^2 that rescales the moment; no relative step, lr is required and > 0; weight decay scaled
+    by lr, default 0); optimizer_args: eps ((1e-30, 1e-16)) and clip_threshold (1.0); betas is the package's TRIPLE (0.9, 0.999,
+    0.9999), each in [0, 1]; the train step's scalar eps is unused.
     "lion": lion_pytorch.Lion / bitsandbytes.optim.Lion (one fp32 moment, the update is lr times the sign of the interpolated
     moment; weight decay decoupled, before the update, default 0); no optimizer_args; eps unused.  "lion8bit_blockwise":
     bitsandbytes.optim.Lion8bit / PagedLion8bit with the moment in blockwise 8-bit codes and bnb's one-state layout;
@@ -796,7 +902,7 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     optimizer's own linear warm-up), r (0.0) and weight_lr_power (2.0): the averaging weight of step k is (k + 1)^r lr_max^power.
     The adapter weights hold y while training: eval() / train() / eval_mode() swap them to x and back, save_checkpoint writes x,
     and the samplers take train_step= to sample from x.
-    betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, (0.9, 0.999) --
+    betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, CAME's triple, (0.9, 0.999) --
     torch.optim.AdamW's, the train step constructor's default before Lion -- for every other one; betas given explicitly are never
     reinterpreted."""
     if optimizer not in ("adam", "adam8bit") and optimizer not in FAMILIES:
@@ -875,7 +981,7 @@ def load_state_dict(cls, store, sd, args, hyper, groups=None, members=None):
         sd = dict(sd, state={entry[n]: e for n, e in sd["state"].items()})
     g = sd["param_groups"][0]
     eps = g.get("eps", hyper["eps"])
-    if isinstance(eps, (tuple, list)):      # Adafactor's pair is one of its optimizer_args (cls.load reads it), not the scalar eps
+    if isinstance(eps, (tuple, list)):      # Adafactor's / CAME's pair is one of its optimizer_args (cls.load reads it), not the scalar eps
         eps = hyper["eps"]
     hyper.update(lr=g["lr"], betas=tuple(g.get("betas", hyper["betas"])), eps=eps, weight_decay=g["weight_decay"])
     state, step = cls.load(store, sd, args)

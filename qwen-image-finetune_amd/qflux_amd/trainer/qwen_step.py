@@ -58,7 +58,7 @@ class QwenLoraTrainStep:
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
-        without it.
+        without it; with CAME betas is the package's triple and lr must be > 0.
         param_groups: parameter groups by name -- a list of dicts, each a "match" regex (re.search on the adapter parameter's name)
         plus any of lr, weight_decay, betas, eps; the first matching rule wins, unmatched parameters form the default group with
         this constructor's values (the last group).  The families with grouped kernels (optim_state: AdamW / Adam, SGD, Lion, the
@@ -104,6 +104,8 @@ class QwenLoraTrainStep:
                                                                                                                 optimizer_args)
         if self.optimizer == "adafactor":
             self._opt_cls.validate(self.optimizer_args, lr)
+        if self.optimizer == "came":        # lr > 0 and a betas triple, as the package's constructor asks
+            self._opt_cls.validate(self.optimizer_args, lr, OS.default_betas("came") if betas is None else tuple(betas))
         if weighting_scheme not in WEIGHTING_SCHEMES:
             raise ValueError(f"weighting_scheme is one of {WEIGHTING_SCHEMES}, not {weighting_scheme!r}")
         if loss_type not in ops.LOSS_KINDS:
