@@ -886,9 +886,18 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
           const int64_t crow = DMA ? (int64_t)(m + row_delta) : remap_row(m, p.rows_per_batch, p.c_batch_rows, p.c_row_off);
           if (!DMA && p.row_mask != nullptr && p.row_mask[m] == 0.f) {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            *(u32x4*)(p.C + crow * p.ldc + n) = z;
+            // cq_only: the bf16 copy of the output the next GEMM contracts over (C2 of GELU, C otherwise) is not written, masked rows included
+            // The guard is spelled out per instantiation ON PURPOSE -- do not fold the arms into one runtime `if (... || !cq_only)`.  That
+            // form is equivalent (cq_only is the constant false outside FP8), but with it hipcc (ROCm 7.2) emitted a different, wrong
+            // zero / value select for the masked-row store of the bf16 EPI_NONE instantiations of all three geometries: the PERSIST_CASES
+            // with a row mask of tests/test_gemm_gpu.py (test_persistent_kernel[*-0-*]) failed on the GPU, thousands of elements off.
+            // The differing select sequence was seen in the assembly; why the compiler forms it is only supposed (an if-conversion of
+            // the two stores to C).  Spelled this way the bf16 instantiations assemble to the instructions they had before the guard.
+            if constexpr (FP8 && EPI != QFX_EPI_GELU) { if (!cq_only) *(u32x4*)(p.C + crow * p.ldc + n) = z; }
+            else *(u32x4*)(p.C + crow * p.ldc + n) = z;
             if constexpr (FP8 && EPI != QFX_EPI_GATE_RES) { if (cq) quant_store(z, crow, n, ch); }
-            if constexpr (EPI == QFX_EPI_GELU) *(u32x4*)(p.C2 + crow * p.ldc2 + n) = z;
+            if constexpr (FP8 && EPI == QFX_EPI_GELU) { if (!cq_only) *(u32x4*)(p.C2 + crow * p.ldc2 + n) = z; }
+            else if constexpr (EPI == QFX_EPI_GELU) *(u32x4*)(p.C2 + crow * p.ldc2 + n) = z;
             if constexpr (EPI == QFX_EPI_GATE_RES) { if (p.C2) *(u32x4*)(p.C2 + (int64_t)m * p.ldc2 + n) = z; }
             continue;
           }
@@ -1249,7 +1258,7 @@ extern "C" int qfx_gemm_mxfp8_grouped(const qfx_gemm_fp8_args* list, int32_t n, 
     if (g.epi != list[0].g.epi || !ok256(&g)) return QFX_EINVAL;
     if (list[i].cq) {   // quantised output image: whole 128-column tiles (4 MX blocks), 8-byte stores, scale rows cover every C row
       if (!list[i].cs || g.epi == QFX_EPI_GATE_RES || (g.N % 128) || (list[i].ldcq % 8) || list[i].ldcq < g.N ||
-          list[i].cq_rows < (g.c_batch_rows ? (g.M / g.rows_per_batch) * g.c_batch_rows : g.M))
+          list[i].cq_rows < (g.c_batch_rows ? ((g.M + g.rows_per_batch - 1) / g.rows_per_batch) * g.c_batch_rows : g.M))      // (a ragged last sample counts)
         return QFX_EINVAL;
     } else if (list[i].cq_only) {
       return QFX_EINVAL;
