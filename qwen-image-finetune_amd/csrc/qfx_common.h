@@ -72,13 +72,16 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // MX-FP8 quantisation of 8 consecutive elements of a 32-element block held by 4 lanes (the caller passes the block maximum over
-// those lanes): OCP MX, shared exponent floor(log2(amax)) - 8, e4m3 elements RNE, saturated at +-448 -- the arithmetic of
-// quant_mxfp8_kernel, so that producers that quantise on the fly emit the same bytes as a separate pass over their bf16 output.
+// those lanes): OCP MX, shared exponent floor(log2(amax)) - 8, e4m3 elements RNE, saturated at +-448.  e_biased is the E8M0 scale
+// byte.  This is the ONLY place the arithmetic is written: quant_mxfp8_kernel (the separate pass) and every producer that quantises
+// on the fly (row kernels, skinny kernels, the epilogue of the MX-FP8 gemm256_kernel) call it on the bf16-rounded values, each with
+// its own amax reduction and scale-byte store -- that is what makes their bytes identical.
 __device__ __forceinline__ u32x2 mx_quant8(const float (&v)[8], float amax, int& e_biased) {
+  // from the fp32 exponent field (amax is a bf16 value: normal or zero)
   int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
   if (amax == 0.f) e = -127;
   e = e < -127 ? -127 : e;
-  const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
+  const float inv = __uint_as_float((uint32_t)(127 - e) << 23);     // 2^-e  (e in [-127, 119] -> exponent field 8..254)
   float q[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) q[i] = fminf(fmaxf(v[i] * inv, -448.f), 448.f);

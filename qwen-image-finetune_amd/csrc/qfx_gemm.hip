@@ -8,14 +8,13 @@
 // projection split in two bf16), B2 = [sB_hi|sB_hi|sB_lo], i.e. an fp32-accurate rank-r update
 // for 3r extra K columns of MFMA work instead of a separate HBM-bound pass over y.
 //
-// Tile 128x128x64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 fragments.
+// Small problems: tile 128x128x64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 fragments.
 // Global->LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction), double buffered,
 // one barrier per K tile.  LDS image is lane-linear (DMA constraint) so the bank swizzle
 // chunk' = chunk ^ ((row>>1)&7) is applied on the SOURCE address and again on the ds_read_b128.
-// MFMA operands are swapped (D' = B A^T) so each lane ends up with 4 consecutive N for one M row:
-// 8-byte bf16x4 stores / bias / gate / residual accesses in the epilogue.
-// blockIdx -> tile mapping is XCD-aware (each XCD walks a contiguous chunk of the tile list).
-#include "qfx_common.h"
+// The body of that tile, shared with the MX-FP8 small kernel, and the argument checks of every entry
+// are in qfx_gemm_tile.h.  Large problems: gemm256_kernel below.
+#include "qfx_gemm_tile.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,13 +25,6 @@
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand tile
-
-__device__ __forceinline__ void glds16(const bf16_t* g, char* lds) {
-  __builtin_amdgcn_global_load_lds((const QFX_AS1 void*)g, (QFX_AS3 void*)lds, 16, 0, 0);
-}
-
 // LDS-DMA piece issued from an asm statement: invisible to hipcc's wait-count pass (with the builtin it guards EVERY later LDS read of
 // the wave with s_waitcnt vmcnt(0)); completion is tracked by hand-counted s_waitcnt vmcnt(N) (see the dGELU epilogue of gemm256_kernel)
 __device__ __forceinline__ void glds16_asm(const bf16_t* g, char* lds) {
@@ -41,186 +33,11 @@ __device__ __forceinline__ void glds16_asm(const bf16_t* g, char* lds) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(g), "s"(l) : "memory");
 }
 
+// the 128x128 small tile: body in qfx_gemm_tile.h (shared with gemm_fp8_kernel)
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const qfx_gemm_args p) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];  // [buf][A|B]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 1, wc = w & 1;
-
-  // ---- XCD-aware tile mapping (bijective for any grid size)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  const int m0 = (swz % tiles_m) * BM;
-  const int n0 = (swz / tiles_m) * BN;
-
-  // ---- staging addresses: wave w stages rows [w*32, w*32+32) of both tiles, 8 rows per DMA
-  const int srow = lane >> 3;  // 0..7 within the 8-row group
-  const int schunk = lane & 7;
-  const bf16_t* pa[4];
-  const bf16_t* pb[4];
-  int64_t a_row[4], b_row[4];
-  int sc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int lr = w * 32 + i * 8 + srow;
-    sc[i] = (schunk ^ ((lr >> 1) & 7)) * 8;  // source column (elements) inside the 64-wide K tile
-    int gm = m0 + lr; gm = gm < p.M ? gm : p.M - 1;
-    int gn = n0 + lr; gn = gn < p.N ? gn : p.N - 1;
-    a_row[i] = gm; b_row[i] = gn;
-    pa[i] = p.A1 + remap_row(gm, p.rows_per_batch, p.a_batch_rows, p.a_row_off) * p.lda1 + sc[i];
-    pb[i] = p.B1 + (int64_t)gn * p.ldb1 + sc[i];
-  }
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int nt1 = p.K1 / BK, nt2 = p.K2 / BK, nt = nt1 + nt2;
-  const int g = lane >> 4, li = lane & 15;
-
-  auto stage = [&](int t) {
-    char* sA = smem + (t & 1) * 2 * TILE_BYTES;
-    char* sB = sA + TILE_BYTES;
-    const int koff = (t < nt1 ? t : t - nt1) * BK;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      glds16(pa[i] + koff, sA + (w * 32 + i * 8) * (BK * 2));
-      glds16(pb[i] + koff, sB + (w * 32 + i * 8) * (BK * 2));
-    }
-  };
-
-  stage(0);
-  __syncthreads();
-
-  for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) {
-      if (t + 1 == nt1) {  // switch to the LoRA K segment
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          pa[i] = p.A2 + a_row[i] * p.lda2 + sc[i];
-          pb[i] = p.B2 + b_row[i] * p.ldb2 + sc[i];
-        }
-      }
-      stage(t + 1);
-    }
-    const char* sA = smem + (t & 1) * 2 * TILE_BYTES;
-    const char* sB = sA + TILE_BYTES;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 a[4], b[4];
-      const int chunk = kk * 4 + g;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        const int row = wr * 64 + mi * 16 + li;
-        a[mi] = *(const bf16x8*)(sA + row * (BK * 2) + ((chunk ^ ((row >> 1) & 7)) << 4));
-      }
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int row = wc * 64 + ni * 16 + li;
-        b[ni] = *(const bf16x8*)(sB + row * (BK * 2) + ((chunk ^ ((row >> 1) & 7)) << 4));
-      }
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ni], a[mi], acc[mi][ni], 0, 0, 0);
-    }
-    if (nt2 > 0 && !p.seg2_plain && t == nt1 - 1) {
-      // base nn.Linear output is a bf16 tensor in the reference: round (acc + bias) before the LoRA add
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int n = n0 + wc * 64 + ni * 16 + 4 * g;
-        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias != nullptr && n + 3 < p.N) {
-          const bf16x4 bb = *(const bf16x4*)(p.bias + n);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bv[r] = bf2f((bf16_t)bb[r]);
-        }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[mi][ni][r] = rbf(acc[mi][ni][r] + bv[r]);
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- epilogue: lane holds C[m = ..+li][n = ..+4g+r], r=0..3
-  const bool bias_pending = (p.bias != nullptr) && (nt2 == 0 || p.seg2_plain);
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
-    const int m = m0 + wr * 64 + mi * 16 + li;
-    if (m >= p.M) continue;
-    const int bidx = m / p.rows_per_batch;
-    const int64_t crow = remap_row(m, p.rows_per_batch, p.c_batch_rows, p.c_row_off);
-    const bool keep = p.row_mask == nullptr || p.row_mask[m] != 0.f;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      const int n = n0 + wc * 64 + ni * 16 + 4 * g;
-      if (n + 3 >= p.N) continue;
-      if (!keep) {
-        const bf16x4 z = {0, 0, 0, 0};
-        *(bf16x4*)(p.C + crow * p.ldc + n) = z;
-        if constexpr (EPI == QFX_EPI_GELU) *(bf16x4*)(p.C2 + crow * p.ldc2 + n) = z;
-        if constexpr (EPI == QFX_EPI_GATE_RES) { if (p.C2) *(bf16x4*)(p.C2 + (int64_t)m * p.ldc2 + n) = z; }
-        continue;
-      }
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[mi][ni][r];
-      if (bias_pending) {
-        const bf16x4 bb = *(const bf16x4*)(p.bias + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += bf2f((bf16_t)bb[r]);
-      }
-      bf16x4 o;
-      if constexpr (EPI == QFX_EPI_NONE) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (short)f2bf(v[r]);
-        *(bf16x4*)(p.C + crow * p.ldc + n) = o;
-      } else if constexpr (EPI == QFX_EPI_GELU) {
-        bf16x4 o2;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bf16_t h = f2bf(v[r]);
-          o[r] = (short)h;
-          o2[r] = (short)f2bf(gelu_tanh_f(bf2f(h)));
-        }
-        *(bf16x4*)(p.C + crow * p.ldc + n) = o;
-        *(bf16x4*)(p.C2 + crow * p.ldc2 + n) = o2;
-      } else if constexpr (EPI == QFX_EPI_GATE_RES) {
-        const bf16x4 gt = *(const bf16x4*)(p.gate + (int64_t)bidx * p.gate_bstride + n);
-        const bf16x4 rs = *(const bf16x4*)(p.aux + (p.aux_unmapped ? (int64_t)m : crow) * p.ldaux + n);
-        bf16x4 yo;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float y = rbf(v[r]);
-          yo[r] = (short)f2bf(y);
-          const float gy = rbf(bf2f((bf16_t)gt[r]) * y);
-          o[r] = (short)f2bf(bf2f((bf16_t)rs[r]) + gy);
-        }
-        *(bf16x4*)(p.C + crow * p.ldc + n) = o;
-        if (p.C2) *(bf16x4*)(p.C2 + (int64_t)m * p.ldc2 + n) = yo;   // pre-gate linear output (rows UNMAPPED), kept for d(gate)
-      } else {  // QFX_EPI_DGELU
-        const bf16x4 hx = *(const bf16x4*)(p.aux + (p.aux_unmapped ? (int64_t)m : crow) * p.ldaux + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float y = rbf(v[r]);
-          o[r] = (short)f2bf(y * gelu_tanh_grad_f(bf2f((bf16_t)hx[r])));
-        }
-        *(bf16x4*)(p.C + crow * p.ldc + n) = o;
-      }
-    }
-  }
+  gemm_tile_body<EPI, false>(p, nullptr, nullptr);
 }
-
 
 // =============================================================================================
 // gemm256: WARP-SPECIALISED and PERSISTENT tiles.  One 640-thread block per CU:
@@ -338,8 +155,6 @@ __device__ __forceinline__ void tile_coord(KGroupedArgs& ga, int nwg, int bid, i
   if (pin) *pin = in;
   if (pgsz) *pgsz = gsz;
 }
-
-typedef __attribute__((ext_vector_type(8))) int v8i32;
 
 template <int EPI, int BMT, int TN, bool FP8 = false, bool SPLIT = false>
 __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArgs ga_by_value) {
@@ -803,8 +618,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
 #pragma unroll
     for (int i = 0; i < NGC; ++i) last_b[i] = -1;
     // MX-FP8 instantiation: the output the next GEMM contracts over (gelu(h) / dh / y) can leave the epilogue quantised -- the 8
-    // lanes of a row hold 64 consecutive columns = 2 MX blocks of 4 lanes; same arithmetic as quant_mxfp8_kernel on the
-    // bf16-rounded values, so the result is bit-identical to quantising the bf16 tensor in a separate pass.
+    // lanes of a row hold 64 consecutive columns = 2 MX blocks of 4 lanes; mx_quant8 on the bf16-rounded values (see its contract
+    // in qfx_common.h).
     uint8_t* cq = nullptr; uint8_t* cs = nullptr; int64_t ldcq = 0; int cq_rows = 0; bool cq_only = false;
     if constexpr (FP8) { cq = ga.cq[gi]; cs = ga.cs[gi]; ldcq = ga.ldcq[gi]; cq_rows = ga.cq_rows[gi]; cq_only = ga.cq_only[gi] != 0; }
     auto quant_store = [&](const u32x4& packed, int64_t crow, int n, int ch) {
@@ -816,22 +631,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
       for (int q = 0; q < 8; ++q) amax = fmaxf(amax, fabsf(v[q]));
       amax = fmaxf(amax, __shfl_xor(amax, 1));
       amax = fmaxf(amax, __shfl_xor(amax, 2));
-      int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
-      if (amax == 0.f) e = -127;
-      e = e < -127 ? -127 : e;
-      const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
-      uint32_t w0 = 0, w1 = 0;
-      float qv[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) qv[q] = fminf(fmaxf(v[q] * inv, -448.f), 448.f);
-      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(qv[0], qv[1], w0, false);
-      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(qv[2], qv[3], w0, true);
-      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(qv[4], qv[5], w1, false);
-      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(qv[6], qv[7], w1, true);
-      const u32x2 o = {w0, w1};
-      *(u32x2*)(cq + crow * ldcq + n) = o;
+      int eb;
+      *(u32x2*)(cq + crow * ldcq + n) = mx_quant8(v, amax, eb);
       const int kb = n >> 5;
-      if ((ch & 3) == 0) cs[((int64_t)(kb >> 2) * cq_rows + crow) * 4 + (kb & 3)] = (uint8_t)(e + 127);
+      if ((ch & 3) == 0) cs[((int64_t)(kb >> 2) * cq_rows + crow) * 4 + (kb & 3)] = (uint8_t)eb;
     };
     // read-back slot of this lane in the two lane passes over a staged 16-row group: row, 16-byte chunk, LDS offset, first column
     int srow_[2], sch_[2], soff_[2], ncol_[2];
@@ -984,28 +787,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void gemm256_kernel(const GroupedArg
     }
   }
   asm volatile("" :: "v"(pf_sink));
-}
-
-bool ok256(const qfx_gemm_args* a) {
-  if ((a->N % 8) || (a->ldc % 8)) return false;
-  if (a->epi == QFX_EPI_GELU && (a->ldc2 % 8)) return false;
-  if (a->epi == QFX_EPI_GATE_RES && a->C2 && (a->ldc2 % 8)) return false;
-  if ((a->epi == QFX_EPI_GATE_RES || a->epi == QFX_EPI_DGELU) && (a->ldaux % 8)) return false;
-  if (a->epi == QFX_EPI_GATE_RES && (a->gate_bstride % 8)) return false;
-  return true;
-}
-
-int validate(const qfx_gemm_args* a) {
-  if (!a->A1 || !a->B1 || !a->C) return QFX_EINVAL;
-  if (a->M <= 0 || a->N <= 0 || a->K1 <= 0 || (a->K1 % BK) != 0 || (a->K2 % BK) != 0 || a->K2 < 0) return QFX_EINVAL;
-  if ((a->N % 4) != 0 || (a->lda1 % 8) || (a->ldb1 % 8) || (a->ldc % 4)) return QFX_EINVAL;
-  if (a->K2 > 0 && (!a->A2 || !a->B2 || (a->lda2 % 8) || (a->ldb2 % 8))) return QFX_EINVAL;
-  if (a->rows_per_batch <= 0) return QFX_EINVAL;
-  if (a->epi == QFX_EPI_GELU && (!a->C2 || (a->ldc2 % 4))) return QFX_EINVAL;
-  if (a->epi == QFX_EPI_GATE_RES && (!a->gate || !a->aux || (a->ldaux % 4))) return QFX_EINVAL;
-  if (a->epi == QFX_EPI_DGELU && (!a->aux || (a->ldaux % 4))) return QFX_EINVAL;
-  if (a->epi < 0 || a->epi > 3) return QFX_EUNSUPPORTED;
-  return QFX_OK;
 }
 
 // ---- tile geometry choice ------------------------------------------------------------------------------------------------
@@ -1248,12 +1029,9 @@ extern "C" int qfx_gemm_mxfp8_grouped(const qfx_gemm_fp8_args* list, int32_t n, 
   GroupedArgs ga;
   const qfx_gemm_args* probs[QFX_MAX_GROUPS];
   for (int i = 0; i < n; ++i) {
-    qfx_gemm_args g = list[i].g;
-    if (!g.A1 || !g.B1 || !g.C || !list[i].sa || !list[i].sb) return QFX_EINVAL;
-    if (g.M <= 0 || g.N <= 0 || g.K1 <= 0 || (g.K1 % 128) || (g.K2 % 64) || g.K2 < 0) return QFX_EINVAL;
-    if ((g.lda1 % 16) || (g.ldb1 % 16) || g.a_batch_rows != 0 || g.seg2_plain) return QFX_EINVAL;
-    g.lda1 /= 2; g.ldb1 /= 2; g.K1 /= 2;          // 2-byte units: the loaders see a bf16 operand of half the K extent
-    const int rc = validate(&g);
+    if (list[i].g.seg2_plain) return QFX_EINVAL;      // (before the checks below: wins over an epilogue out of range)
+    qfx_gemm_args g;                                  // 2-byte units: the loaders see a bf16 operand of half the K extent
+    const int rc = validate_fp8(list[i], g);
     if (rc) return rc;
     if (g.epi != list[0].g.epi || !ok256(&g)) return QFX_EINVAL;
     if (list[i].cq) {   // quantised output image: whole 128-column tiles (4 MX blocks), 8-byte stores, scale rows cover every C row

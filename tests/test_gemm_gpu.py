@@ -9,6 +9,8 @@ in NaN-filled wider buffers (row strides wider than K, column slices, the text r
 Worst errors per dispatch family and the wall time of this file: gemm_parity.json.
 
 Which case list reaches which instantiation, launcher branch or refusal arm:
+  (gemm_kernel<EPI> and gemm_fp8_kernel<EPI> are the two instantiations of ONE tile body, gemm_tile_body<EPI, FP8> of
+  csrc/qfx_gemm_tile.h: the tile map, staging, segment switch, mid-rounding and epilogue each case list below reaches are the same text)
   gemm_kernel<0..3>            qfx_gemm_bf16 below 160 tiles of 256x128: SMALL_CASES (M 1 .. 257, N 4 .. 260 incl. N % 8 != 0, K1 64 .. 320
                                = 1 .. 5 K tiles on the 2-stage buffer, K2 0 / 64 / 128), ARM_CASES, SWEEP_CASES
   gemm256_kernel<0..3, 256x128 | 256x256 | 160x192>
@@ -26,13 +28,16 @@ Which case list reaches which instantiation, launcher branch or refusal arm:
   gemm_fp8_kernel<0..3>        qfx_gemm_mxfp8 below the threshold: FP8_SMALL_CASES (K1 128 / 256 / 384, K2 0 / 64, c_* maps)
   gemm256_kernel<0..3, 256x128, FP8>   qfx_gemm_mxfp8_grouped: FP8_PERSIST_CASES, FP8_GROUPED_CASES (n = 3), FP8_QUANT_EPI_CASES (cq / cs bit-equal
                                to quant_mxfp8_ref of the bf16 output, cq_only 0 / 1, each epilogue with and without a row mask)
-  quant_mxfp8_kernel           QUANT_CASES: ldx > K, ldq > K, row remap, the edge blocks of gemm_ref.quant_input
+  quant_mxfp8_kernel           QUANT_CASES: ldx > K, ldq > K, row remap, the edge blocks of gemm_ref.quant_input (mx_quant8 of
+                               csrc/qfx_common.h, the quantiser of the epilogue above as well)
   refusals                     validate: NULL A1 / B1 / C; M, N, K1 <= 0; K1, K2 % 64; K2 < 0; N % 4; lda1, ldb1 % 8; ldc % 4; K2 > 0 with NULL
                                A2 / B2 or lda2, ldb2 % 8; rows_per_batch <= 0; GELU without C2, ldc2 % 4; GATE_RES without gate / aux,
                                ldaux % 4; DGELU without aux, ldaux % 4; epi 4 / -1 -> QFX_EUNSUPPORTED (test_refusals_validate)
                                qfx_gemm_grouped: n = 0, 7; mixed epilogues; ok256: N % 8, ldc % 8, ldc2 % 8 (GELU; GATE_RES with C2), ldaux % 8
                                (GATE_RES, DGELU), gate_bstride % 8 (test_refusals_grouped)
-                               MX-FP8: NULL sa / sb; K1 % 128; lda1, ldb1 % 16; a_batch_rows != 0; seg2_plain (grouped); cq without cs, with
+                               MX-FP8, both entries through validate_fp8: NULL sa / sb; K1 % 128; lda1, ldb1 % 16; a_batch_rows != 0; the arms of
+                               validate on the halved problem (N % 4, ldc % 4, rows_per_batch, A2, lda2, epi 5 / -1); two faults at once (QFX_EINVAL
+                               wins over the epilogue out of range); seg2_plain (grouped, also with epi 5); cq without cs, with
                                GATE_RES, N % 128, ldcq < N, cq_rows too small (whole and ragged last sample); cq_only without cq; cq / cq_only on the small path ->
                                QFX_EUNSUPPORTED (test_refusals_mxfp8)
 The same-XCD split-K lever stays off (its default); tests/test_kernels_gpu.py::test_gemm_same_xcd_split_k_lever covers it."""
@@ -518,9 +523,15 @@ def test_refusals_mxfp8():
     plain = build(base, "exact")
     both = [(dict(sa=None), EINVAL), (dict(sb=None), EINVAL), (dict(K1=192), EINVAL), (dict(K1=64), EINVAL), (dict(K2=32), EINVAL),
             (dict(lda1=plain.g.lda1 + 8), EINVAL), (dict(ldb1=plain.g.ldb1 + 8), EINVAL), (dict(a_batch_rows=24, a_row_off=1), EINVAL),
-            (dict(A1=None), EINVAL), (dict(C=None), EINVAL), (dict(M=0), EINVAL), (dict(epi=5), EUNSUPPORTED)]
+            (dict(A1=None), EINVAL), (dict(C=None), EINVAL), (dict(M=0), EINVAL), (dict(epi=5), EUNSUPPORTED), (dict(epi=-1), EUNSUPPORTED),
+            (dict(N=130), EINVAL), (dict(ldc=plain.g.ldc + 2), EINVAL), (dict(rows_per_batch=0), EINVAL), (dict(A2=None), EINVAL),
+            (dict(lda2=plain.g.lda2 + 4), EINVAL)]
+    # two faults at once: every QFX_EINVAL arm wins over the epilogue out of range, whichever check states it
+    both += [(dict(epi=5, sa=None), EINVAL), (dict(epi=5, K1=192), EINVAL), (dict(epi=5, lda1=plain.g.lda1 + 8), EINVAL),
+             (dict(epi=5, a_batch_rows=24, a_row_off=1), EINVAL), (dict(epi=5, N=130), EINVAL), (dict(epi=5, rows_per_batch=0), EINVAL),
+             (dict(epi=5, K2=32), EINVAL), (dict(epi=5, cq_only=1), EUNSUPPORTED)]
     _mutations(plain, both, single, fp8=True)
-    _mutations(plain, both + [(dict(seg2_plain=1), EINVAL), (dict(cq_only=1), EINVAL)], grouped, fp8=True)
+    _mutations(plain, both + [(dict(seg2_plain=1), EINVAL), (dict(cq_only=1), EINVAL), (dict(epi=5, seg2_plain=1), EINVAL)], grouped, fp8=True)
     rows = b.outs["C"].buf_rows
     _mutations(b, [(dict(cs=None), EINVAL), (dict(N=136), EINVAL), (dict(ldcq=120), EINVAL), (dict(ldcq=b.ldcq + 4), EINVAL), (dict(cq_rows=16), EINVAL)],
                grouped, fp8=True)
