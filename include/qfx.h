@@ -387,6 +387,9 @@ int qfx_transpose_heads(const uint16_t* in, int64_t ld_in, uint16_t* out, int32_
  * kernels take their transposed MFMA operands from the row-major LDS tiles with ds_read_b64_tr_b16, so no transposed
  * copy is read any more; the fields keep the struct layout stable and may be NULL.
  * O [B,S,H*dh] (row stride ldo). lse2 [B,H,S_pad] fp32 = log2-domain logsumexp. key_mask [B,S] fp32 additive or NULL.
+ * At least one key of every sample must have a finite key_mask value.  The kernels write rows s < S and columns < H*dh only: the
+ * pad columns [S, S_pad) of lse2 and dsum are never written (the backward reads but never uses them), and neither are the part
+ * rows of a stream whose w_pk is NULL or the columns of a part row outside [c0, c0 + R).
  */
 /* ABI 6: a rank-r LoRA down projection fused into an attention epilogue (north_star: "LoRA side branches ... inside the kernels").
  * The kernel that holds a row of X = O / d(pre-norm q) / d(pre-norm k) / dV in registers also emits, per head h,
