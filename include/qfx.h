@@ -475,11 +475,17 @@ int qfx_flowmatch_prepare(const uint16_t* x0, const uint16_t* noise, const uint1
 
 /* ---- fused global-norm clip + AdamW over the flat LoRA parameter buffer ----------------------
  * (base_trainer.py:449-455 clip_grad_norm_ ; optimizer.step :531 with torch.optim.AdamW semantics) */
-int qfx_sumsq(const float* g, int64_t n, float* out /* zeroed by caller */, void* stream);
+/* qfx_sumsq ADDS the sum of squares into out[0] (one fp32 atomic per workgroup, in any order): the caller zeroes out, or keeps a
+ * running total there.  Rejected with QFX_EINVAL: a NULL g or out, n <= 0. */
+int qfx_sumsq(const float* g, int64_t n, float* out /* added into */, void* stream);
 /* Deterministic form (ABI 3): block partial sums into `partials` (fp32[nslots], caller workspace, e.g. 1024), folded by one block in
  * a fixed order into out[0] (overwritten).  Same inputs -> same bits: data-parallel replicas (identical gradients after the
- * all-reduce) compute the SAME clip coefficient; qfx_sumsq's fp32 atomics let them drift apart by ~1e-10 per step. */
+ * all-reduce) compute the SAME clip coefficient; qfx_sumsq's fp32 atomics let them drift apart by ~1e-10 per step.  Rejected with
+ * QFX_EINVAL: a NULL g, out or partials, n <= 0, nslots <= 0. */
 int qfx_sumsq_det(const float* g, int64_t n, float* out, float* partials, int32_t nslots, void* stream);
+/* qfx_adamw_step rejects only a NULL p / g / m / v and n <= 0; its scalars are NOT validated (the grouped entry validates its rows):
+ * bias_corr1 = 1 - beta1^t and bias_corr2 = 1 - beta2^t come from the caller, and the kernel forms lr / bias_corr1 and
+ * 1 / sqrt(bias_corr2) once per launch.  gnorm_sq == NULL or max_norm <= 0: clip = grad_scale. */
 int qfx_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, float bias_corr1, float bias_corr2,
                    const float* gnorm_sq /* may be NULL */, float max_norm, float grad_scale, void* stream);
@@ -513,7 +519,8 @@ int qfx_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, floa
  * blockwise 8-bit families: block_group = device uint8[n_blocks], the group of every block-table entry (an entry never leaves its
  * tensor); the scalar hyperparameters of the args struct are ignored, `step` is the one count of all groups.
  * A map entry >= n_groups cannot be seen from the host without a synchronisation: the builder of the maps checks the range before
- * upload (ops.tile_group_map / ops.block_group_map); the kernels clamp the index to the table.
+ * upload (ops.tile_group_map / ops.block_group_map); the kernels clamp the index to the rows they were given: an entry >= n_groups
+ * steps its tile (block) with the LAST row, groups[n_groups - 1].
  * Rejected with QFX_EINVAL before any launch: what the ungrouped entry rejects, a NULL map or groups pointer, n_groups outside
  * 1..QFX_MAX_PARAM_GROUPS, a row with a negative lr, a beta outside [0, 1), a negative weight_decay or eps (SGD: a negative momentum, a NULL
  * buf with a row whose momentum != 0, nesterov with momentum <= 0 or dampening != 0).  No atomics: same inputs -> same bits.
@@ -555,7 +562,10 @@ typedef struct qfx_prodigy_args {
   const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq) for the global-norm clip */
   float max_norm, grad_scale;
 } qfx_prodigy_args;
-int qfx_prodigy_init_state(double* state, double d0, void* stream);   /* d = d_max = d_hat = d0, everything else 0; synchronises */
+/* d = d_max = d_hat = d0, everything else 0; synchronises.  d0 is the double the caller holds; the step's qfx_prodigy_args.d0 is a
+ * float, and the package's `d == d0` (the first jump is not capped by growth_rate) is decided on their float images, so the two
+ * spellings of one d0 (1e-6 and (float)1e-6) are equal. */
+int qfx_prodigy_init_state(double* state, double d0, void* stream);
 int qfx_prodigy_step(const qfx_prodigy_args* a, void* stream);
 
 /* ---- blockwise 8-bit Adam / AdamW with bitsandbytes' state layout (third party bitsandbytes.optim.Adam8bit / AdamW8bit and their

@@ -76,7 +76,7 @@ __device__ __forceinline__ void adam8bit_body(const qfx_adam8bit_args& a, float 
   int parity = 0;
   for (int64_t bi = first; bi < a.n_blocks; bi += stride) {      // WG: bi is uniform over the workgroup, every thread reaches the barrier
     const qfx_adam8bit_block e = a.table[bi];
-    if (GROUPED) k = ks[group_index(block_group, bi)];
+    if (GROUPED) k = ks[group_index(block_group, bi, n_groups)];
     const int64_t base = e.off + (int64_t)lane * E;
     const int n = e.len - lane * E;
     float p[E], g[E], m[E], v[E];

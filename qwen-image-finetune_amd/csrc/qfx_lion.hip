@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void lion_grouped_kernel(float* __restrict__ p
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = VEC ? n / 4 : 0;
   for (int64_t i = tid; i < nv; i += nt) {
-    const LionConst k = ks[group_index(tile_group, i >> 4)];
+    const LionConst k = ks[group_index(tile_group, i >> 4, n_groups)];
     f32x4 pv = *(const f32x4*)(p + 4 * i);
     const f32x4 gv = *(const f32x4*)(g + 4 * i);
     f32x4 mv = *(const f32x4*)(m + 4 * i);
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void lion_grouped_kernel(float* __restrict__ p
     *(f32x4*)(m + 4 * i) = mv;
   }
   for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const LionConst k = ks[group_index(tile_group, i >> 6)];
+    const LionConst k = ks[group_index(tile_group, i >> 6, n_groups)];
     float pi = p[i], mi = m[i];
     lion_elem(pi, g[i], mi, k);
     p[i] = pi; m[i] = mi;
@@ -130,7 +130,7 @@ __device__ __forceinline__ void lion8bit_body(const qfx_lion8bit_args& a, const 
   int parity = 0;
   for (int64_t bi = first; bi < a.n_blocks; bi += stride) {      // WG: bi is uniform over the workgroup, every thread reaches the barrier
     const qfx_adam8bit_block e = a.table[bi];
-    if (GROUPED) k = ks[group_index(block_group, bi)];
+    if (GROUPED) k = ks[group_index(block_group, bi, n_groups)];
     const int64_t base = e.off + (int64_t)lane * E;
     const int n = e.len - lane * E;
     float p[E], g[E], m[E];

@@ -116,7 +116,8 @@ inline unsigned blockwise_grid(int64_t n_blocks, int blocksize) {
 // ---- parameter groups (include/qfx.h): the grouped kernels take their hyperparameter rows by value in the argument block, the
 // first n_groups lanes of every workgroup turn them into the family's per-group constants in LDS, and every 64-element tile (fp32
 // kernels) or block-table entry (blockwise kernels) names its row with one byte.  An index the builder did not range-check is
-// clamped to the table here, so that it can never read LDS outside it.
+// clamped to the rows the launch filled (an entry >= n_groups takes the last row, n_groups - 1), so that it can never read LDS
+// outside the table or a row of it that nobody wrote.
 template <typename Row>
 struct GroupTable { Row g[QFX_MAX_PARAM_GROUPS]; };
 
@@ -127,9 +128,9 @@ inline GroupTable<Row> group_table(const Row* groups, int n_groups) {
   return t;
 }
 
-__device__ __forceinline__ int group_index(const uint8_t* __restrict__ map, int64_t i) {
+__device__ __forceinline__ int group_index(const uint8_t* __restrict__ map, int64_t i, int n_groups) {
   const int gi = map[i];
-  return gi < QFX_MAX_PARAM_GROUPS ? gi : QFX_MAX_PARAM_GROUPS - 1;
+  return gi < n_groups ? gi : n_groups - 1;      // only rows 0 .. n_groups-1 of the LDS table are filled
 }
 
 inline bool groups_count_ok(const void* groups, int n_groups) { return groups != nullptr && n_groups >= 1 && n_groups <= QFX_MAX_PARAM_GROUPS; }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ 
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = VEC ? n / 4 : 0;
   for (int64_t i = tid; i < nv; i += nt) {
-    const AdamWRow r = rows[group_index(tile_group, i >> 4)];
+    const AdamWRow r = rows[group_index(tile_group, i >> 4, n_groups)];
     f32x4 pv = *(const f32x4*)(p + 4 * i);
     const f32x4 gv = *(const f32x4*)(g + 4 * i);
     f32x4 mv = *(const f32x4*)(m + 4 * i);
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ 
     *(f32x4*)(v + 4 * i) = vv;
   }
   for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const AdamWRow r = rows[group_index(tile_group, i >> 6)];
+    const AdamWRow r = rows[group_index(tile_group, i >> 6, n_groups)];
     float pi = p[i], mi = m[i], vi = v[i];
     adamw_elem(pi, g[i], mi, vi, clip, r.lr, r.b1, r.b2, r.eps, r.wd, r.step, r.rs2);
     p[i] = pi; m[i] = mi; v[i] = vi;
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p,
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = VEC ? n / 4 : 0;
   for (int64_t i = tid; i < nv; i += nt) {
-    const SgdRow r = rows[group_index(tile_group, i >> 4)];
+    const SgdRow r = rows[group_index(tile_group, i >> 4, n_groups)];
     f32x4 pv = *(const f32x4*)(p + 4 * i);
     const f32x4 gv = *(const f32x4*)(g + 4 * i);
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p,
     *(f32x4*)(p + 4 * i) = pv;
   }
   for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const SgdRow r = rows[group_index(tile_group, i >> 6)];
+    const SgdRow r = rows[group_index(tile_group, i >> 6, n_groups)];
     float pi = p[i], bi = 0.f;
     if (r.mom != 0.f && !first) bi = buf[i];
     sgd_elem(pi, g[i], bi, clip, r.lr, r.mom, r.keep, r.wd, r.nesterov, first);
@@ -245,7 +245,9 @@ __global__ void prodigy_d_kernel(double* __restrict__ st, double b3, double d0, 
   double d = st[PS_D];
   const double num = st[PS_NUM] * b3 + (d / d0) * st[PS_DLR] * st[PS_ACC_NUM];
   const double d_hat = d_coef * num / den;
-  if (d == d0) d = d > d_hat ? d : d_hat;
+  // the package's `d == d0` (first jump not capped by growth): d0 reaches the step as the struct's float and the state as the double
+  // qfx_prodigy_init_state was given, so 1e-6 and (float)1e-6 must compare equal -- in float, where both are one number
+  if ((float)d == (float)d0) d = d > d_hat ? d : d_hat;
   double d_max = st[PS_DMAX];
   d_max = d_max > d_hat ? d_max : d_hat;
   const double dg = d * growth;

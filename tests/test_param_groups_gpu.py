@@ -207,6 +207,55 @@ def test_lion8bit_grouped_stitches_bit_exactly(bs, big):
     assert all(torch.equal(one[k], runs[0][k]) for k in one)
 
 
+# ---------------------------------------------------------------- map entries past n_groups (include/qfx.h: they take the last row)
+def _out_of_range(valid):
+    """The map with two entries of the last group (1 of 2) replaced by 2 and by 255."""
+    bad = valid.clone()
+    ones = (valid == 1).nonzero().flatten()
+    assert ones.numel() >= 2
+    bad[ones[0]], bad[ones[-1]] = 2, 255
+    return bad
+
+
+def test_lion_grouped_map_entries_past_n_groups_take_the_last_row():
+    from qflux_amd import ops
+    entries, assign, n = _layout()
+    assign = [min(a, 1) for a in assign]
+    p0, g, gsq = _flat_inputs(n)
+    m0 = _rand(n, 3, 0.1)
+    tg = ops.tile_group_map(entries, assign, 2, numel=n, device=DEV)
+    outs = []
+    for tmap in (tg, _out_of_range(tg)):
+        p, m = p0.clone(), m0.clone()
+        ops.lion_step_grouped(p, g, m, tmap, LION_ROWS[:2], gnorm_sq=gsq, max_norm=1.0, grad_scale=0.5)
+        pu, gu, mu = (torch.cat([x.new_zeros(1), x])[1:] for x in (p0, g, m0))          # the scalar form
+        ops.lion_step_grouped(pu, gu, mu, tmap, LION_ROWS[:2], gnorm_sq=gsq, max_norm=1.0, grad_scale=0.5)
+        assert torch.equal(pu, p) and torch.equal(mu, m)
+        outs.append((p, m))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and not torch.equal(outs[0][1], m0)
+
+
+@pytest.mark.parametrize("family,bs", [("adam8bit", 256), ("adam8bit", 2048), ("lion8bit", 256), ("lion8bit", 2048)])
+def test_blockwise_grouped_map_entries_past_n_groups_take_the_last_row(family, bs):
+    from qflux_amd import ops
+    entries, assign, n = _layout()
+    assign = [min(a, 1) for a in assign]
+    _, g, gsq = _flat_inputs(n)
+    S = _Blockwise(entries, n, bs, 2 if family == "adam8bit" else 1)
+    bg = ops.block_group_map(S.lay, assign, 2, device=DEV)
+    outs = []
+    for bmap in (bg, _out_of_range(bg)):
+        b = S.copy()
+        if family == "adam8bit":
+            ops.adam8bit_step_grouped(b["p"], g, b["q1"], b["q2"], b["a1"], b["a2"], b["f1"], b["f2"], S.lay, S.qm[0], S.qm[1], bmap, ADAM_ROWS[:2], 2,
+                                      gnorm_sq=gsq, max_norm=1.0, grad_scale=0.5)
+        else:
+            ops.lion8bit_step_grouped(b["p"], g, b["q1"], b["a1"], b["f1"], S.lay, S.qm[0], bmap, LION_ROWS[:2], gnorm_sq=gsq, max_norm=1.0,
+                                      grad_scale=0.5)
+        outs.append(b)
+    assert all(torch.equal(outs[0][k], outs[1][k]) for k in outs[0]) and not torch.equal(outs[0]["q1"], S.bufs["q1"])
+
+
 # ---------------------------------------------------------------- against torch, on the tiny Qwen model of test_optim_classes_gpu.py
 def _cpu_groups(groups):
     """The same groups over fp32 CPU copies of the parameters."""
