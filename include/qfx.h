@@ -1036,6 +1036,61 @@ int qfx_lora_dropout_apply(const qfx_lora_dropout_args* list, int32_t n, const u
 int qfx_lora_dropout_advance(uint32_t* state, void* stream);
 int qfx_lora_dropout_factors_host(const uint32_t* state, uint32_t site, int32_t b, int32_t t, int32_t r, float* out);
 
+/* ---- torch.optim.RAdam / NAdam / Adamax over the flat fp32 LoRA buffers (csrc/qfx_adamx.hip): ONE entry, ONE launch, the variant
+ * chosen per launch.  The specification is torch's single-tensor implementation (_single_tensor_radam, _single_tensor_nadam,
+ * _single_tensor_adamax): its fp32 tensor operations in its order, one rounding each (the file is built without FMA contraction;
+ * lerp_, add(alpha=) and addcmul_ are the fused multiply-adds torch's CPU kernels issue).  Every per-step scalar torch forms as a
+ * Python float is formed by the CALLER in double and passed in the group's row as a float: nothing synchronises.  With
+ * t = the step count (from 1), b1 = beta1, b2 = beta2, g' = g * clip (the clip prologue of qfx_adamw_step: gnorm_sq / max_norm /
+ * grad_scale, applied before weight decay) and lerp(a, b, w) = a + w (b - a) for |w| < 0.5, b - (b - a)(1 - w) otherwise:
+ *   all      weight_decay != 0:  decoupled (RAdam, NAdam only):  p *= decay          decay = 1 - lr weight_decay
+ *                                 otherwise (L2):                 g' += weight_decay p
+ *            exp_avg = lerp(exp_avg, g', one_minus_beta1)
+ *   RAdam    state2 = exp_avg_sq = beta2 exp_avg_sq + (one_minus_beta2 g') g'
+ *            u = (exp_avg / bias_corr1) lr                                             bias_corr1 = 1 - b1^t
+ *            rectified:  u = (u ((1 / (sqrt(exp_avg_sq) + eps)) sqrt_bias_corr2)) rect   sqrt_bias_corr2 = sqrt(1 - b2^t)
+ *            p -= u
+ *              rho_inf = 2 / (1 - b2) - 1,  rho_t = rho_inf - 2 t b2^t / (1 - b2^t),  rectified = rho_t > 5,
+ *              rect = sqrt((rho_t - 4)(rho_t - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho_t))
+ *   NAdam    state2 = exp_avg_sq as RAdam's;  den = sqrt(exp_avg_sq / bias_corr2) + eps      bias_corr2 = 1 - b2^t
+ *            p += (c_grad g') / den;  p += (c_avg exp_avg) / den
+ *              mu_t = b1 (1 - 0.5 * 0.96^(t momentum_decay)),  mu_product_t = mu_product_{t-1} mu_t (torch keeps it in fp32),
+ *              c_grad = -lr (1 - mu_t) / (1 - mu_product_t),  c_avg = -lr mu_{t+1} / (1 - mu_product_t mu_{t+1})
+ *   Adamax   state2 = exp_inf = max(beta2 exp_inf, |g'| + eps);  p += (neg_clr exp_avg) / exp_inf     neg_clr = -lr / (1 - b1^t)
+ * A row holds every field; a variant reads its own (the others are ignored).  The entry is always grouped (parameter groups, see
+ * qfx_adamw_step_grouped): groups = HOST array of 1..QFX_MAX_PARAM_GROUPS rows, tile_group = device uint8[ceil(n / 64)], which may be
+ * NULL when n_groups == 1; a map entry >= n_groups steps its tile with the last row.  16-byte accesses when p, g, exp_avg and
+ * state2 are 16-byte aligned, scalar ones otherwise; a grid-stride loop; no atomics: same inputs -> same bits, and every tensor gets
+ * the bits a one-group launch with its row gives it.  maximize / differentiable / capturable are not implemented (the callers
+ * refuse them).
+ * QFX_EINVAL before any launch: NULL args / p / g / exp_avg / state2 / groups, n <= 0, an unknown variant, n_groups outside
+ * 1..QFX_MAX_PARAM_GROUPS, a NULL tile_group with n_groups > 1, a row with a negative lr, eps or weight_decay or a beta outside
+ * [0, 1), RAdam with bias_corr1 <= 0, NAdam with bias_corr2 <= 0. ---- */
+enum { QFX_ADAMX_RADAM = 0, QFX_ADAMX_NADAM = 1, QFX_ADAMX_ADAMAX = 2 };
+typedef struct qfx_adamx_group {
+  float lr, beta1, beta2, eps, weight_decay;
+  float one_minus_beta1, one_minus_beta2;      /* float(1 - b1), float(1 - b2): the weights torch hands lerp_ / addcmul_ */
+  float decay;                                 /* float(1 - lr weight_decay); read with decoupled != 0 */
+  float bias_corr1, bias_corr2;                /* RAdam: bias_corr1; NAdam: bias_corr2 */
+  float sqrt_bias_corr2, rect;                 /* RAdam, read with rectified != 0 */
+  float c_grad, c_avg;                         /* NAdam */
+  float neg_clr;                               /* Adamax */
+  int32_t decoupled;                           /* decoupled_weight_decay (RAdam, NAdam) */
+  int32_t rectified;                           /* RAdam: rho_t > 5 */
+  int32_t reserved;
+} qfx_adamx_group;
+typedef struct qfx_adamx_args {
+  float* p; const float* g; float* exp_avg; float* state2;      /* state2: exp_avg_sq (RAdam, NAdam) or exp_inf (Adamax) */
+  int64_t n;
+  int32_t variant;                             /* QFX_ADAMX_* */
+  int32_t n_groups;
+  const qfx_adamx_group* groups;               /* HOST */
+  const uint8_t* tile_group;                   /* device; may be NULL when n_groups == 1 */
+  const float* gnorm_sq;                       /* may be NULL */
+  float max_norm, grad_scale;
+} qfx_adamx_args;
+int qfx_adamx_step(const qfx_adamx_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,23 @@ class Adam8bitGroup(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
+ADAMX_RADAM, ADAMX_NADAM, ADAMX_ADAMAX = 0, 1, 2       # QFX_ADAMX_*
+
+
+class AdamxGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("decay", C.c_float), ("bias_corr1", C.c_float),
+                ("bias_corr2", C.c_float), ("sqrt_bias_corr2", C.c_float), ("rect", C.c_float), ("c_grad", C.c_float),
+                ("c_avg", C.c_float), ("neg_clr", C.c_float), ("decoupled", C.c_int32), ("rectified", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AdamxArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("exp_avg", C.c_void_p), ("state2", C.c_void_p), ("n", C.c_int64),
+                ("variant", C.c_int32), ("n_groups", C.c_int32), ("groups", C.POINTER(AdamxGroup)), ("tile_group", C.c_void_p),
+                ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
 class MuonTensor(C.Structure):
     _fields_ = [("off", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("lr_ratio", C.c_float), ("reserved", C.c_int32)]
 
@@ -343,6 +360,7 @@ SYMBOLS = {
     "qfx_lion8bit_step_grouped": (C.c_int, [C.POINTER(Lion8bitArgs), _vp, C.POINTER(LionGroup), _i32, _vp]),
     "qfx_sfadamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i32, _vp, _f, _f, _vp]),
     "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
+    "qfx_adamx_step": (C.c_int, [C.POINTER(AdamxArgs), _vp]),
     "qfx_ema_update": (C.c_int, [_vp, _i64, C.POINTER(EmaArgs), _vp]),
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
     "qfx_maxnorm_check_table": (C.c_int, [C.POINTER(MaxnormPair), _i32, _i64]),

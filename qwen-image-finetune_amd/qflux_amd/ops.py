@@ -596,6 +596,105 @@ def lion8bit_step_grouped(p, g, q1, absmax1, m32, layout, qmap1, block_group, gr
     L.check(lib.qfx_lion8bit_step_grouped(a, _p(block_group), rows, len(groups), stream_ptr()), "qfx_lion8bit_step_grouped")
 
 
+# ---- torch.optim.RAdam / NAdam / Adamax (qfx.h: qfx_adamx_step).  The per-step scalars torch forms as Python floats, formed here as
+# torch forms them (the same double expressions, statement for statement) and rounded to the row's floats
+ADAMX_VARIANTS = {"radam": L.ADAMX_RADAM, "nadam": L.ADAMX_NADAM, "adamax": L.ADAMX_ADAMAX}
+
+
+def adamx_check(lr, betas, eps, weight_decay, momentum_decay=0.0):
+    """The constructor checks torch.optim.RAdam / NAdam / Adamax share, with their messages."""
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    if len(betas) != 2:
+        raise ValueError(f"betas is a pair (beta1, beta2), not {betas!r}")
+    for i in (0, 1):
+        if not 0.0 <= betas[i] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index {i}: {betas[i]}")
+    if not 0.0 <= weight_decay:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    if not 0.0 <= momentum_decay:
+        raise ValueError(f"Invalid momentum_decay value: {momentum_decay}")
+
+
+def radam_scalars(step, beta1, beta2):
+    """_single_tensor_radam's Python floats at step `step` (from 1): (bias_correction1, bias_correction2 ** 0.5, rho_t > 5, the
+    rectification factor or 0.0 where it does not apply)."""
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    rho_inf = 2 / (1 - beta2) - 1
+    rho_t = rho_inf - 2 * step * (beta2 ** step) / bias_correction2
+    if not rho_t > 5.0:
+        return bias_correction1, bias_correction2 ** 0.5, False, 0.0
+    rect = ((rho_t - 4) * (rho_t - 2) * rho_inf / ((rho_inf - 4) * (rho_inf - 2) * rho_t)) ** 0.5
+    return bias_correction1, bias_correction2 ** 0.5, True, rect
+
+
+def nadam_mu(step, beta1, momentum_decay):
+    """(mu_t, mu_{t+1}) of _single_tensor_nadam."""
+    mu = beta1 * (1.0 - 0.5 * (0.96 ** (step * momentum_decay)))
+    mu_next = beta1 * (1.0 - 0.5 * (0.96 ** ((step + 1) * momentum_decay)))
+    return mu, mu_next
+
+
+def nadam_scalars(step, lr, beta1, beta2, momentum_decay, mu_product):
+    """_single_tensor_nadam's Python floats at step `step`: mu_product, torch's 0-dim fp32 CPU tensor (the product through step - 1),
+    is advanced IN PLACE as torch advances it (`mu_product *= mu`: one fp32 rounding per step, no device involved); returns
+    (bias_correction2, the value= of the gradient's addcdiv_, the value= of exp_avg's)."""
+    bias_correction2 = 1 - beta2 ** step
+    mu, mu_next = nadam_mu(step, beta1, momentum_decay)
+    mu_product *= mu
+    mp = mu_product.item()
+    mu_product_next = mp * mu_next
+    return bias_correction2, -lr * (1.0 - mu) / (1.0 - mp), (-lr * mu_next) / (1.0 - mu_product_next)
+
+
+def adamx_rows(variant, groups, step, mu_products=None):
+    """The rows of qfx_adamx_step: groups = [dict(lr, betas, eps, weight_decay[, decoupled_weight_decay][, momentum_decay])] -> a list
+    of field tuples in AdamxGroup's order.  "nadam": mu_products = one 0-dim fp32 CPU tensor per group, advanced in place."""
+    rows = []
+    for k, r in enumerate(groups):
+        lr, (beta1, beta2), eps, wd = float(r["lr"]), r["betas"], r["eps"], r["weight_decay"]
+        decoupled = bool(r.get("decoupled_weight_decay", False)) and variant != "adamax"
+        bc1 = bc2 = sq2 = rect = c_grad = c_avg = neg_clr = 0.0
+        rectified = False
+        if variant == "radam":
+            bc1, sq2, rectified, rect = radam_scalars(step, beta1, beta2)
+        elif variant == "nadam":
+            bc2, c_grad, c_avg = nadam_scalars(step, lr, beta1, beta2, r.get("momentum_decay", 4e-3), mu_products[k])
+        else:
+            neg_clr = -(lr / (1 - beta1 ** step))
+        rows.append((lr, beta1, beta2, eps, wd, 1 - beta1, 1 - beta2, 1 - lr * wd, bc1, bc2, sq2, rect, c_grad, c_avg, neg_clr,
+                     int(decoupled), int(rectified), 0))
+    return rows
+
+
+def adamx_step(variant, p, g, exp_avg, state2, groups, step, tile_group=None, mu_products=None, gnorm_sq=None, max_norm=0.0,
+               grad_scale=1.0):
+    """One torch.optim.RAdam / NAdam / Adamax step (variant "radam" | "nadam" | "adamax") over the flat fp32 buffers p / g with
+    exp_avg and state2 (exp_avg_sq, Adamax: exp_inf); see qfx.h.  groups: one dict per parameter group (adamx_rows); tile_group from
+    tile_group_map, None with one group; step: the count this step brings the state to (from 1)."""
+    if variant not in ADAMX_VARIANTS:
+        raise ValueError(f"adamx_step: unknown variant {variant!r}")
+    what = f"adamx_step({variant})"
+    if not 1 <= len(groups) <= MAX_PARAM_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} parameter groups, 1 to {MAX_PARAM_GROUPS} are supported")
+    if tile_group is None and len(groups) != 1:
+        raise ValueError(f"{what}: {len(groups)} parameter groups need a group map")
+    for r in groups:
+        adamx_check(r["lr"], r["betas"], r["eps"], r["weight_decay"], r.get("momentum_decay", 0.0))
+    _check_tensors(what, p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p), ("g", g), ("exp_avg", exp_avg),
+                                                                                       ("state2", state2))])
+    if tile_group is not None:
+        _check_tensors(what, p, (("the group map", tile_group, torch.uint8, (p.numel() + 63) // 64),))
+    rows = adamx_rows(variant, groups, step, mu_products)
+    arr = (L.AdamxGroup * len(rows))(*[L.AdamxGroup(*r) for r in rows])
+    a = L.AdamxArgs(_p(p), _p(g), _p(exp_avg), _p(state2), p.numel(), ADAMX_VARIANTS[variant], len(rows), arr, _p(tile_group),
+                    _p(gnorm_sq), max_norm, grad_scale)
+    L.check(lib.qfx_adamx_step(a, stream_ptr()), "qfx_adamx_step")
+
+
 def sfadamw_schedule(k, lr, beta2, warmup_steps, r, weight_lr_power, lr_max, weight_sum):
     """The group scalars of Schedule-Free AdamW's step k (counted from 0), in Python doubles as schedulefree.AdamWScheduleFree forms
     them: (lr_t, bias_corr2, ckp1, lr_max, weight_sum) with the two running values updated."""

@@ -1,14 +1,14 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree, RAdam, NAdam, Adamax) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
 the two ways of driving the model and with the original packages'.
 
 `params` must be exactly the adapter parameters of ONE model: a plain list, or torch's list of group dicts whose union is that set,
-each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit and PagedLion8bit step several groups
+each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit, PagedLion8bit, RAdam, NAdam and Adamax step several groups
 in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); Prodigy, Adafactor, CAME,
 Muon and AdamWScheduleFree refuse a second group.  loraplus_param_groups builds the two LoRA+ groups.  The loop has clipped already
 (accelerator.clip_grad_norm_, base_trainer.py:449-455), so step() launches without the fused clip; lr, betas, eps, weight_decay and
@@ -23,7 +23,7 @@ from .trainer import optim_state as OS
 from .trainer.optim_config import optimizer_kwargs_from_config
 
 __all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "CAME", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree",
-           "loraplus_param_groups"]
+           "RAdam", "NAdam", "Adamax", "loraplus_param_groups"]
 
 
 def _find_store(param_groups):
@@ -287,6 +287,37 @@ class Muon(_FlatOptimizer):
             raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
         super().__init__(params, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, ns_coefficients=ns_coefficients,
                          eps=eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn)
+
+
+class RAdam(_FlatOptimizer):
+    """torch.optim.RAdam (variance rectification: Adam without the second moment until rho_t > 5; L2 or decoupled weight decay)."""
+    _PATH = "qflux_amd.optim.RAdam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, decoupled_weight_decay=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay,
+                         maximize=maximize, capturable=capturable, differentiable=differentiable)
+
+
+class NAdam(_FlatOptimizer):
+    """torch.optim.NAdam (Adam with the Nesterov momentum schedule mu_t; L2 or decoupled weight decay)."""
+    _PATH = "qflux_amd.optim.NAdam"
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, momentum_decay=4e-3, decoupled_weight_decay=False,
+                 *, foreach=None, maximize=False, capturable=False, differentiable=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum_decay=momentum_decay,
+                         decoupled_weight_decay=decoupled_weight_decay, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable)
+
+
+class Adamax(_FlatOptimizer):
+    """torch.optim.Adamax (Adam under the infinity norm: exp_inf = max(beta2 exp_inf, |g| + eps); L2 weight decay)."""
+    _PATH = "qflux_amd.optim.Adamax"
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, foreach=None, *, maximize=False,
+                 differentiable=False, capturable=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable)
 
 
 class AdamWScheduleFree(_FlatOptimizer):

@@ -21,7 +21,11 @@ _FAMILY = {
     "came_pytorch.CAME": "came", "came_pytorch.CAME.CAME": "came", "qflux_amd.optim.CAME": "came",
     "torch.optim.Muon": "muon", "qflux_amd.optim.Muon": "muon",
     "schedulefree.AdamWScheduleFree": "adamw_schedulefree", "qflux_amd.optim.AdamWScheduleFree": "adamw_schedulefree",
+    "torch.optim.RAdam": "radam", "qflux_amd.optim.RAdam": "radam", "torch.optim.NAdam": "nadam", "qflux_amd.optim.NAdam": "nadam",
+    "torch.optim.Adamax": "adamax", "qflux_amd.optim.Adamax": "adamax",
 }
+# the lr of torch.optim.RAdam / NAdam / Adamax when the config gives none
+_ADAMX_LR = {"radam": 1e-3, "nadam": 2e-3, "adamax": 2e-3}
 # init_args of the 8-bit bnb classes the blockwise step refuses: name -> (the one value it accepts, what any other value asks for)
 _REFUSED_8BIT = {"percentile_clipping": (100, "percentile clipping"), "max_unorm": (0.0, "update-norm clipping (max_unorm)"),
                  "block_wise": (True, "non-blockwise 8-bit state"), "skip_zeros": (False, "skip_zeros"), "amsgrad": (False, "amsgrad")}
@@ -68,6 +72,11 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     clip_threshold); betas is the package's triple (left out: (0.9, 0.999, 0.9999)); lr is required and > 0 (the package's assert),
     weight decay left out is 0; a betas that is no triple, an eps that is no pair, a beta outside [0, 1] and any other keyword are
     refused.
+        torch.optim.RAdam / NAdam / Adamax and qflux_amd.optim.RAdam / NAdam / Adamax -> optimizer="radam" / "nadam" / "adamax" (lr,
+    betas, eps, weight_decay; left out: the class's own lr 1e-3 / 2e-3 / 2e-3, weight decay 0) + optimizer_args
+    (decoupled_weight_decay for RAdam and NAdam, momentum_decay for NAdam; none for Adamax); foreach is dropped; maximize,
+    capturable and differentiable =True are refused, and so is every keyword the class itself does not take (amsgrad, fused, ...);
+    torch's constructor checks apply with torch's messages (ValueError).
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -140,6 +149,21 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         OS.ScheduleFreeAdamWState.validate(dict(OS.ScheduleFreeAdamWState.DEFAULTS, **out["optimizer_args"]))
     elif fam == "prodigy":
         out["optimizer_args"] = _take(a, OS.ProdigyState)
+    elif fam in OS.ADAMX:
+        cls = OS.ADAMX[fam]
+        on = [k for k in cls.REFUSED if a.pop(k, False)]
+        if on:
+            raise NotImplementedError(f"{class_path}: {' / '.join(on)}=True is not implemented by the fused step")
+        out.setdefault("lr", _ADAMX_LR[fam])
+        out.setdefault("weight_decay", 0.0)
+        args = _take(a, cls)
+        cls.validate(dict(cls.DEFAULTS, **args))
+        OS.ops.adamx_check(out["lr"], out.get("betas", (0.9, 0.999)), out.get("eps", 1e-8), out["weight_decay"])
+        if cls.DEFAULTS:
+            out["optimizer_args"] = args
+        a.pop("foreach", None)         # how torch loops over its tensors
+        if a:      # before the common knobs below are dropped: none of them is a keyword of these classes
+            raise NotImplementedError(f"unsupported optimizer init_args for {class_path}: {sorted(a)}")
     for k in ("min_8bit_size", "percentile_clipping", "block_wise", "optim_bits", "is_paged", "amsgrad", "foreach", "fused"):
         a.pop(k, None)       # knobs of the 8-bit state / torch dispatch: no meaning for the fused fp32 step
     if a:

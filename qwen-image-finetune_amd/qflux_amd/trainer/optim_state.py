@@ -1,7 +1,8 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
 file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
 AdafactorState (transformers.optimization.Adafactor's), CameState (came_pytorch.CAME's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
-Lion8bit), MuonState (torch.optim.Muon's) and ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's).
+Lion8bit), MuonState (torch.optim.Muon's), ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's) and RAdamState / NAdamState /
+AdamaxState (torch.optim.RAdam's / NAdam's / Adamax's).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
@@ -103,7 +104,7 @@ class FlatState:
         if n_groups > 1 and not cls.GROUPED:
             raise ParamGroupsNotImplemented(f"{cls.FAMILY}: {n_groups} parameter groups -- the fused {cls.FAMILY} step runs over ONE group (its "
                                       "global estimates / per-matrix steps are defined per group in the original package; the grouped "
-                                      "kernels cover AdamW / Adam, SGD, Lion and the blockwise 8-bit families)")
+                                      "kernels cover AdamW / Adam, SGD, Lion, RAdam, NAdam, Adamax and the blockwise 8-bit families)")
         if n_groups > ops.MAX_PARAM_GROUPS:
             raise ValueError(f"{n_groups} parameter groups: the grouped kernels take at most {ops.MAX_PARAM_GROUPS}")
 
@@ -850,13 +851,136 @@ class ScheduleFreeAdamWState(FlatState):
         return state, 0
 
 
+class _AdamXState(AdamWState):
+    """What torch.optim.RAdam, NAdam and Adamax share: exp_avg (m) and a second fp32 state (v: exp_avg_sq, Adamax's exp_inf) indexed
+    like pflat, stepped by the ONE launch of qfx_adamx_step -- always the grouped entry, one row with one group.  A group's row is
+    lr / betas / eps / weight_decay plus the class's own fields (DEFAULTS), read from the row where it carries them (the torch.optim
+    classes' param_groups) and from the optimizer_args otherwise.  The per-step Python floats of torch's single-tensor functions
+    are formed on the host (ops.adamx_rows); no step synchronises."""
+    VARIANT = None
+    SECOND = "exp_avg_sq"       # the file's name of v
+    GROUPED = True
+    REFUSED = ("maximize", "capturable", "differentiable")
+
+    @staticmethod
+    def validate(args):
+        if "momentum_decay" in args:
+            if not 0.0 <= args["momentum_decay"]:
+                raise ValueError(f"Invalid momentum_decay value: {args['momentum_decay']}")
+            args["momentum_decay"] = float(args["momentum_decay"])
+        if "decoupled_weight_decay" in args:
+            args["decoupled_weight_decay"] = bool(args["decoupled_weight_decay"])
+
+    def _group_rows(self, lr, betas, eps, weight_decay, args, groups):
+        rows = groups if groups is not None and len(groups) > 1 else [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
+        return [dict({n: args[n] for n in self.DEFAULTS}, **r) for r in rows]
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        rows = self._group_rows(lr, betas, eps, weight_decay, args, groups)
+        ops.adamx_step(self.VARIANT, store.pflat, store.gflat, self.m, self.v, rows, step, tile_group=self.group_map if len(rows) > 1 else None,
+                       mu_products=getattr(self, "mu", None), gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+
+    @classmethod
+    def _group_fields(cls, args):
+        """The class's own fields of a torch param_group (its constructor's defaults for what the fused step does not implement)."""
+        return dict({n: args[n] for n in cls.DEFAULTS}, maximize=False, foreach=None, capturable=False, differentiable=False)
+
+    def _param_state(self, i, p, off, k, step):
+        return {"step": torch.tensor(float(step)), "exp_avg": _out(self.m, off, k, p.shape), self.SECOND: _out(self.v, off, k, p.shape)}
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """torch's per-parameter {"step", "exp_avg", "exp_avg_sq" | "exp_inf"} (NAdam: and "mu_product"), step a 0-dim fp32 tensor
+        as torch keeps it; no state before the first step, as in torch."""
+        if state is None or step == 0:
+            return cls._group_fields(args), {}
+        return cls._group_fields(args), {i: state._param_state(i, p, off, k, step) for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        for g in sd["param_groups"]:
+            on = [n for n in cls.REFUSED if g.get(n, False)]
+            if on:
+                raise NotImplementedError(f"{cls.FAMILY} with {' / '.join(on)}=True is not implemented by the fused step")
+        cls.group_args(sd, args)
+        if not sd["state"]:
+            return None, 0
+        state, step = cls(store, args), 0
+        for i, p, off, k, e in cls.file_entries(store, sd):
+            for n, buf in (("exp_avg", state.m), (cls.SECOND, state.v)):
+                buf[off:off + k].copy_(cls.field(i, p, e, n, numel=k).reshape(-1).float())
+            step = max(step, int(float(cls.field(i, p, e, "step"))))
+            state._load_entry(i, p, e)
+        return state, step
+
+    def _load_entry(self, i, p, e):
+        pass
+
+
+class RAdamState(_AdamXState):
+    """torch.optim.RAdam: exp_avg and exp_avg_sq; rho_t, the rectification factor and which branch applies are host scalars."""
+    VARIANT, FAMILY = "radam", "RAdam"
+    DEFAULTS = dict(decoupled_weight_decay=False)
+
+
+class NAdamState(_AdamXState):
+    """torch.optim.NAdam: exp_avg, exp_avg_sq and the running product of the momentum schedule, mu_product -- per parameter in
+    torch, one value per group here (it depends on the group's beta1, momentum_decay and the step count alone): `mu`, a 0-dim fp32 CPU
+    tensor per group, advanced as torch advances its own (ops.nadam_scalars).  `sched` is its fp64 device image, written by
+    buffers() for a broadcast or a replica check and read back by sync_host() on the ranks that received it.  A grouping that
+    changes the number of groups mid-run hands every new group the product of group 0 (exact whenever the groups share beta1 and
+    momentum_decay, as LoRA+'s do)."""
+    VARIANT, FAMILY = "nadam", "NAdam"
+    NAMES = ("m", "v", "sched")
+    DEFAULTS = dict(momentum_decay=4e-3, decoupled_weight_decay=False)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.mu = [torch.tensor(1.0)]
+        self.sched = None
+        self._file_mu = None        # entry index -> the file's mu_product, until regroup() knows the groups
+
+    def regroup(self, store, members):
+        super().regroup(store, members)
+        firsts = [m[0] for m in self.members] if self.members is not None else [0]
+        if self._file_mu is not None:
+            self.mu = [torch.tensor(float(self._file_mu.get(i, 1.0))) for i in firsts]
+            self._file_mu = None
+        elif len(self.mu) != len(firsts):
+            self.mu = [self.mu[0].clone() for _ in firsts]
+
+    def buffers(self):
+        self.sched = torch.tensor([float(m) for m in self.mu] + [1.0] * (ops.MAX_PARAM_GROUPS - len(self.mu)), dtype=torch.float64,
+                                  device=self.m.device)
+        return super().buffers()
+
+    def sync_host(self):
+        self.mu = [torch.tensor(float(x)) for x in self.sched.cpu().tolist()[:len(self.mu)]]
+
+    def _param_state(self, i, p, off, k, step):
+        at = 0 if self.members is None else next(j for j, m in enumerate(self.members) if i in m)
+        return dict(super()._param_state(i, p, off, k, step), mu_product=self.mu[at].clone())
+
+    def _load_entry(self, i, p, e):
+        if self._file_mu is None:
+            self._file_mu = {}
+        self._file_mu[i] = float(self.field(i, p, e, "mu_product"))
+
+
+class AdamaxState(_AdamXState):
+    """torch.optim.Adamax: exp_avg and the exponentially weighted infinity norm exp_inf (v); weight decay in the L2 form only."""
+    VARIANT, FAMILY, SECOND = "adamax", "Adamax", "exp_inf"
+
+
+ADAMX = {"radam": RAdamState, "nadam": NAdamState, "adamax": AdamaxState}
 LION = ("lion",) + A8.LION_BLOCKWISE
 # optimizer= name -> (state class, the weight decay that weight_decay=None stands for: the stood-in optimizer class's own default)
 FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": (SgdState, 0.0), "adafactor": (AdafactorState, 0.0),
             "came": (CameState, 0.0),
             "lion": (LionState, 0.0), "muon": (MuonState, 0.1), "adamw_schedulefree": (ScheduleFreeAdamWState, 0.0),
             "adam8bit_blockwise": (BlockwiseState, 0.0), "adamw8bit_blockwise": (BlockwiseState, 0.01),
-            "lion8bit_blockwise": (LionBlockwiseState, 0.0)}
+            "lion8bit_blockwise": (LionBlockwiseState, 0.0),
+            "radam": (RAdamState, 0.0), "nadam": (NAdamState, 0.0), "adamax": (AdamaxState, 0.0)}
 
 
 def default_betas(optimizer):
@@ -902,6 +1026,11 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     optimizer's own linear warm-up), r (0.0) and weight_lr_power (2.0): the averaging weight of step k is (k + 1)^r lr_max^power.
     The adapter weights hold y while training: eval() / train() / eval_mode() swap them to x and back, save_checkpoint writes x,
     and the samplers take train_step= to sample from x.
+    "radam" / "nadam" / "adamax": torch.optim.RAdam / NAdam / Adamax, stepped by one launch whose arithmetic is torch's
+    single-tensor implementation operation for operation (include/qfx.h: qfx_adamx_step); weight decay default 0 (the classes'), in
+    the L2 form unless decoupled_weight_decay; optimizer_args: decoupled_weight_decay (False; RAdam and NAdam) and momentum_decay
+    (4e-3; NAdam); Adamax takes none.  The classes' own lr defaults (1e-3 / 2e-3 / 2e-3) are what optimizer_kwargs_from_config
+    fills in for a config without lr.  maximize, capturable and differentiable are refused.
     betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, CAME's triple, (0.9, 0.999) --
     torch.optim.AdamW's, the train step constructor's default before Lion -- for every other one; betas given explicitly are never
     reinterpreted."""
