@@ -1091,6 +1091,86 @@ typedef struct qfx_adamx_args {
 } qfx_adamx_args;
 int qfx_adamx_step(const qfx_adamx_args* a, void* stream);
 
+/* ---- AdEMAMix (Pagliardini et al., "The AdEMAMix Optimizer: Better, Faster, Older", 2024; third party bitsandbytes.optim.AdEMAMix /
+ * AdEMAMix32bit / AdEMAMix8bit and their Paged forms, one YAML line through the generic optimizer.class_path of the reference) over
+ * the flat LoRA buffers (csrc/qfx_ademamix.hip): Adam with a second, slow gradient average.  Three states -- the fast average m1,
+ * the slow average m2, Adam's nu -- and two hyperparameters that move every step.  THE LISTING BELOW IS THE SPECIFICATION, not the
+ * package: it restates what bitsandbytes' 32-bit AdEMAMix kernel is understood to compute (a decoupled multiplicative decay after
+ * the update, eps outside the corrected root) and was written without a copy of bitsandbytes at hand; tests/ademamix_ref.py
+ * restates it in numpy.  Per element, every operation rounding once in fp32, in this order (the file is built without FMA
+ * contraction), with g' = g * clip (the clip prologue of qfx_adamw_step: gnorm_sq / max_norm / grad_scale):
+ *   m1 = m1 beta1   + one_minus_beta1 g'
+ *   m2 = m2 beta3_t + one_minus_beta3_t g'
+ *   nu = nu beta2   + (one_minus_beta2 g') g'
+ *   p  = p - lr ((m1 / bias_corr1 + alpha_t m2) / (sqrtf(nu) / sqrt_bias_corr2 + eps))
+ *   p  = p decay                           only when weight_decay > 0;  decay = float(1 - lr weight_decay)
+ * bias_corr1 = 1 - beta1^t, sqrt_bias_corr2 = sqrt(1 - beta2^t), t the step count from 1; the slow average gets no bias correction.
+ * Every per-step scalar is formed by the CALLER in double and rounded to float in the group's row; nothing synchronises.  The two
+ * schedules, per group and per step (t_alpha / t_beta3 absent: the constants alpha / beta3):
+ *   alpha_t = min(t alpha / t_alpha, alpha)
+ *   beta3_t = min(exp(ln(beta1) ln(beta3) / ((1 - s) ln(beta3) + s ln(beta1))), beta3),  s = t / t_beta3
+ * An element whose g' is not finite keeps p and all three states (as in qfx_adam8bit_step).  No atomics: same inputs -> same bits,
+ * and every tensor gets the bits a one-group launch with its row gives it.
+ * qfx_ademamix_step: m1, m2, nu [n] in fp32; always grouped (parameter groups, see qfx_adamw_step_grouped): groups = HOST array of
+ * 1..QFX_MAX_PARAM_GROUPS rows, tile_group = device uint8[ceil(n / 64)], which may be NULL when n_groups == 1; a map entry >=
+ * n_groups steps its tile with the last row.  16-byte accesses when p, g, m1, m2 and nu are 16-byte aligned, scalar ones otherwise;
+ * a grid-stride loop.
+ * qfx_ademamix8bit_step / _grouped: bitsandbytes' blockwise 8-bit state, driven by the block table of qfx_adam8bit_step (same
+ * struct, same builder, same grid policy).  state1 holds BOTH averages as two planes of signed-map codes: q1[2][q1_plane] (plane 0 =
+ * m1, plane 1 = m2, each indexed like p) with absmax1[2][absmax1_plane]; nu is unsigned-map codes q2 with absmax2.  8-bit block:
+ * the three states decoded (qmap[code] * absmax), updated as above, then stored exactly as qfx_adam8bit_step stores its states --
+ * per plane absmax = max |state| over the block, the nearest code against the fp32 midpoints with a tie going to the lower one, the
+ * keep-the-sign rule for the two planes of state1; a block whose absmax is 0 stores the code of 0.0.  The parameter update uses the
+ * fp32 states, not their re-quantised images.  fp32 entries (tensors below min_8bit_size) keep m32[2][m32_plane] and v32.  Every
+ * pointer must be non-NULL (allocate for an unused buffer); `off`, `state`, q1_plane and m32_plane are multiples of 4.  The
+ * ungrouped entry reads the row a->hp; the grouped one ignores it and takes groups[block_group[bi]] for table entry bi.
+ * QFX_EINVAL before any launch: a NULL args / buffer / groups pointer (gnorm_sq and, with one group, tile_group may be NULL), n <= 0,
+ * n_groups outside 1..QFX_MAX_PARAM_GROUPS, a NULL tile_group with n_groups > 1, a row with a negative lr, eps, weight_decay or
+ * alpha_t, with beta1, beta2 or beta3_t outside [0, 1), or with bias_corr1 <= 0; for the 8-bit entries also n_blocks <= 0, a
+ * blocksize outside {256, 2048}, a NULL block_group (grouped) and a plane stride that is not positive or (q1, m32) no multiple of 4. ---- */
+typedef struct qfx_ademamix_group {           /* 64 bytes */
+  float lr, beta1, beta2, eps, weight_decay;
+  float one_minus_beta1, one_minus_beta2;      /* float(1 - beta1), float(1 - beta2) */
+  float beta3_t, one_minus_beta3_t;            /* the slow average's rate at this step and float(1 - beta3_t) */
+  float alpha_t;                               /* the slow average's weight at this step */
+  float bias_corr1, sqrt_bias_corr2;
+  float decay;                                 /* float(1 - lr weight_decay); read with weight_decay > 0 */
+  int32_t reserved[3];
+} qfx_ademamix_group;
+typedef struct qfx_ademamix_args {
+  float* p; const float* g; float* m1; float* m2; float* nu;
+  int64_t n;
+  int32_t n_groups;
+  int32_t reserved;
+  const qfx_ademamix_group* groups;            /* HOST */
+  const uint8_t* tile_group;                   /* device; may be NULL when n_groups == 1 */
+  const float* gnorm_sq;                       /* may be NULL */
+  float max_norm, grad_scale;
+} qfx_ademamix_args;
+int qfx_ademamix_step(const qfx_ademamix_args* a, void* stream);
+typedef struct qfx_ademamix8bit_args {
+  float* p;              /* parameters, updated in place */
+  const float* g;        /* gradient (summed over ranks / micro-steps; scaled by grad_scale and the clip factor on the fly) */
+  uint8_t* q1;           /* state1 codes (signed map), two planes: m1 at q1, m2 at q1 + q1_plane, each indexed like p */
+  uint8_t* q2;           /* state2 codes (unsigned map): nu */
+  float* absmax1;        /* per 8-bit block, two planes: absmax1 and absmax1 + absmax1_plane */
+  float* absmax2;
+  float* m32;            /* fp32 m1 / m2 of the tensors below the 8-bit size, two planes: m32 and m32 + m32_plane */
+  float* v32;            /* fp32 nu of those tensors */
+  int64_t q1_plane, absmax1_plane, m32_plane;      /* elements between the two planes */
+  const qfx_adam8bit_block* table;   /* device array of n_blocks entries */
+  int32_t n_blocks;
+  int32_t blocksize;     /* 256 or 2048: the largest `len` of the table */
+  const float* qmap1;    /* fp32[256] */
+  const float* qmap2;    /* fp32[256] */
+  qfx_ademamix_group hp; /* the one row of the ungrouped entry */
+  const float* gnorm_sq; /* may be NULL: sum of squares of g (qfx_sumsq_det) for the global-norm clip */
+  float max_norm, grad_scale;
+} qfx_ademamix8bit_args;
+int qfx_ademamix8bit_step(const qfx_ademamix8bit_args* a, void* stream);
+int qfx_ademamix8bit_step_grouped(const qfx_ademamix8bit_args* a, const uint8_t* block_group, const qfx_ademamix_group* groups,
+                                  int32_t n_groups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

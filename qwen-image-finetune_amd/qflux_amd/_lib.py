@@ -210,6 +210,26 @@ class AdamxArgs(C.Structure):
                 ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
+class AdemamixGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("beta3_t", C.c_float), ("one_minus_beta3_t", C.c_float),
+                ("alpha_t", C.c_float), ("bias_corr1", C.c_float), ("sqrt_bias_corr2", C.c_float), ("decay", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class AdemamixArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m1", C.c_void_p), ("m2", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
+                ("n_groups", C.c_int32), ("reserved", C.c_int32), ("groups", C.POINTER(AdemamixGroup)), ("tile_group", C.c_void_p),
+                ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
+class Ademamix8bitArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("q1", C.c_void_p), ("q2", C.c_void_p), ("absmax1", C.c_void_p),
+                ("absmax2", C.c_void_p), ("m32", C.c_void_p), ("v32", C.c_void_p), ("q1_plane", C.c_int64), ("absmax1_plane", C.c_int64),
+                ("m32_plane", C.c_int64), ("table", C.c_void_p), ("n_blocks", C.c_int32), ("blocksize", C.c_int32), ("qmap1", C.c_void_p),
+                ("qmap2", C.c_void_p), ("hp", AdemamixGroup), ("gnorm_sq", C.c_void_p), ("max_norm", C.c_float), ("grad_scale", C.c_float)]
+
+
 class MuonTensor(C.Structure):
     _fields_ = [("off", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("lr_ratio", C.c_float), ("reserved", C.c_int32)]
 
@@ -361,6 +381,9 @@ SYMBOLS = {
     "qfx_sfadamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i32, _vp, _f, _f, _vp]),
     "qfx_sf_swap": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
     "qfx_adamx_step": (C.c_int, [C.POINTER(AdamxArgs), _vp]),
+    "qfx_ademamix_step": (C.c_int, [C.POINTER(AdemamixArgs), _vp]),
+    "qfx_ademamix8bit_step": (C.c_int, [C.POINTER(Ademamix8bitArgs), _vp]),
+    "qfx_ademamix8bit_step_grouped": (C.c_int, [C.POINTER(Ademamix8bitArgs), _vp, C.POINTER(AdemamixGroup), _i32, _vp]),
     "qfx_ema_update": (C.c_int, [_vp, _i64, C.POINTER(EmaArgs), _vp]),
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
     "qfx_maxnorm_check_table": (C.c_int, [C.POINTER(MaxnormPair), _i32, _i64]),

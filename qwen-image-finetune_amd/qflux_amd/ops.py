@@ -695,6 +695,113 @@ def adamx_step(variant, p, g, exp_avg, state2, groups, step, tile_group=None, mu
     L.check(lib.qfx_adamx_step(a, stream_ptr()), "qfx_adamx_step")
 
 
+# ---- AdEMAMix (qfx.h: qfx_ademamix_step / qfx_ademamix8bit_step).  The listing in include/qfx.h is the specification; the two
+# schedules and every other per-step scalar are formed here in double, per group and per step, and rounded to the row's floats
+def ademamix_check(lr, betas, eps, weight_decay, alpha=5.0, t_alpha=None, t_beta3=None):
+    """The constructor checks of the AdEMAMix classes: lr, eps, weight_decay and alpha >= 0, three betas each in [0, 1), t_alpha /
+    t_beta3 None or > 0.  The beta3 schedule interpolates ln(beta): with t_beta3, beta1 and beta3 must be > 0."""
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    if not isinstance(betas, (tuple, list)) or len(betas) != 3:
+        raise ValueError(f"AdEMAMix's betas is a triple (beta1, beta2, beta3), not {betas!r}")
+    for i in (0, 1, 2):
+        if not 0.0 <= betas[i] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index {i}: {betas[i]}")
+    if not 0.0 <= weight_decay:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    if not 0.0 <= alpha:
+        raise ValueError(f"Invalid alpha value: {alpha}")
+    for n, t in (("t_alpha", t_alpha), ("t_beta3", t_beta3)):
+        if t is not None and not t > 0:
+            raise ValueError(f"Invalid {n} value: {t} (None or > 0)")
+    if t_beta3 is not None and not (betas[0] > 0.0 and betas[2] > 0.0):
+        raise ValueError(f"the beta3 schedule (t_beta3={t_beta3}) interpolates ln(beta): beta1 and beta3 must be > 0, not {betas!r}")
+
+
+def ademamix_alpha(step, alpha, t_alpha=None):
+    """alpha_t at step `step` (from 1): the linear warm-up of the slow average's weight, alpha from t_alpha on."""
+    return alpha if t_alpha is None else min(step * alpha / t_alpha, alpha)
+
+
+def ademamix_beta3(step, beta1, beta3, t_beta3=None):
+    """beta3_t at step `step` (from 1): the slow average's rate, warmed up from beta1 so that its half-life grows linearly."""
+    if t_beta3 is None:
+        return beta3
+    s = step / t_beta3
+    ln1, ln3 = math.log(beta1), math.log(beta3)
+    return min(math.exp(ln1 * ln3 / ((1 - s) * ln3 + s * ln1)), beta3)
+
+
+def ademamix_rows(groups, step):
+    """The rows of the AdEMAMix entries: groups = [dict(lr, betas (the triple), eps, weight_decay[, alpha][, t_alpha][, t_beta3])] -> a
+    list of field tuples in AdemamixGroup's order, every scalar formed in double."""
+    rows = []
+    for r in groups:
+        lr, (beta1, beta2, beta3), eps, wd = float(r["lr"]), r["betas"], r["eps"], r["weight_decay"]
+        b3t = ademamix_beta3(step, beta1, beta3, r.get("t_beta3"))
+        rows.append((lr, beta1, beta2, eps, wd, 1 - beta1, 1 - beta2, b3t, 1 - b3t, ademamix_alpha(step, r.get("alpha", 5.0), r.get("t_alpha")),
+                     1 - beta1 ** step, math.sqrt(1 - beta2 ** step), 1 - lr * wd))
+    return rows
+
+
+def _ademamix_groups(what, groups, need_map):
+    if not 1 <= len(groups) <= MAX_PARAM_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} parameter groups, 1 to {MAX_PARAM_GROUPS} are supported")
+    if need_map and len(groups) != 1:
+        raise ValueError(f"{what}: {len(groups)} parameter groups need a group map")
+    for r in groups:
+        ademamix_check(r["lr"], r["betas"], r["eps"], r["weight_decay"], r.get("alpha", 5.0), r.get("t_alpha"), r.get("t_beta3"))
+
+
+def ademamix_step(p, g, m1, m2, nu, groups, step, tile_group=None, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """One AdEMAMix step over the flat fp32 buffers p / g with the fast average m1, the slow average m2 and the second moment nu; see
+    qfx.h.  groups: one dict per parameter group (ademamix_rows); tile_group from tile_group_map, None with one group; step: the count
+    this step brings the state to (from 1) -- both schedules and the bias corrections depend on it."""
+    what = "ademamix_step"
+    _ademamix_groups(what, groups, tile_group is None)
+    _check_tensors(what, p, [(n, t, torch.float32, p.numel(), "float32") for n, t in (("p", p), ("g", g), ("m1", m1), ("m2", m2), ("nu", nu))])
+    if tile_group is not None:
+        _check_tensors(what, p, (("the group map", tile_group, torch.uint8, (p.numel() + 63) // 64),))
+    rows = ademamix_rows(groups, step)
+    arr = (L.AdemamixGroup * len(rows))(*[L.AdemamixGroup(*r) for r in rows])
+    a = L.AdemamixArgs(_p(p), _p(g), _p(m1), _p(m2), _p(nu), p.numel(), len(rows), 0, arr, _p(tile_group), _p(gnorm_sq), max_norm,
+                       grad_scale)
+    L.check(lib.qfx_ademamix_step(a, stream_ptr()), "qfx_ademamix_step")
+
+
+def ademamix8bit_step(p, g, q1, q2, absmax1, absmax2, m32, v32, layout, qmap1, qmap2, groups, step, block_group=None, gnorm_sq=None,
+                      max_norm=0.0, grad_scale=1.0):
+    """One blockwise 8-bit AdEMAMix step (bitsandbytes' AdEMAMix8bit state layout) over the flat buffers p / g; see qfx.h.  layout: an
+    adam8bit_block_table.  state1 holds both averages: q1 uint8[2, plane >= layout.extent] (plane 0 = m1, plane 1 = m2, each indexed
+    like p), absmax1 fp32[2, >= layout.n_absmax], m32 fp32[2, >= layout.n_fp32]; q2 / absmax2 / v32 hold nu as adam8bit_step's do;
+    the planes of q1 and m32 are multiples of 4 long.  groups / step as ademamix_step's; block_group (block_group_map) selects the
+    grouped entry and may be None with one group."""
+    what = "ademamix8bit_step"
+    f32, u8 = torch.float32, torch.uint8
+    _ademamix_groups(what, groups, block_group is None)
+    for n, t, need in (("q1", q1, layout.extent), ("absmax1", absmax1, max(1, layout.n_absmax)), ("m32", m32, max(1, layout.n_fp32))):
+        if t.dim() != 2 or t.shape[0] != 2 or t.shape[1] < need or (n != "absmax1" and t.shape[1] % 4):
+            raise ValueError(f"{what}: {n} must be shaped [2, plane] with plane >= {need}" + ("" if n == "absmax1" else " and a multiple of 4") +
+                             f", not {tuple(t.shape)}")
+    _check_tensors(what, p, (("p", p, f32, layout.extent), ("g", g, f32, layout.extent), ("q1", q1, u8, 2 * layout.extent),
+                             ("q2", q2, u8, layout.extent), ("absmax1", absmax1, f32, 2 * max(1, layout.n_absmax)),
+                             ("absmax2", absmax2, f32, max(1, layout.n_absmax)), ("m32", m32, f32, 2 * max(1, layout.n_fp32)),
+                             ("v32", v32, f32, max(1, layout.n_fp32)), ("qmap1", qmap1, f32, 256), ("qmap2", qmap2, f32, 256)))
+    if layout.table.device != p.device:
+        raise ValueError(f"{what}: the block table lives on another device")
+    rows = ademamix_rows(groups, step)
+    a = L.Ademamix8bitArgs(_p(p), _p(g), _p(q1), _p(q2), _p(absmax1), _p(absmax2), _p(m32), _p(v32), q1.shape[1], absmax1.shape[1],
+                           m32.shape[1], _p(layout.table), layout.n_blocks, layout.blocksize, _p(qmap1), _p(qmap2),
+                           L.AdemamixGroup(*rows[0]), _p(gnorm_sq), max_norm, grad_scale)
+    if block_group is None:
+        return L.check(lib.qfx_ademamix8bit_step(a, stream_ptr()), "qfx_ademamix8bit_step")
+    _check_tensors(what, p, (("the group map", block_group, torch.uint8, layout.n_blocks),))
+    arr = (L.AdemamixGroup * len(rows))(*[L.AdemamixGroup(*r) for r in rows])
+    L.check(lib.qfx_ademamix8bit_step_grouped(a, _p(block_group), arr, len(rows), stream_ptr()), "qfx_ademamix8bit_step_grouped")
+
+
 def sfadamw_schedule(k, lr, beta2, warmup_steps, r, weight_lr_power, lr_max, weight_sum):
     """The group scalars of Schedule-Free AdamW's step k (counted from 0), in Python doubles as schedulefree.AdamWScheduleFree forms
     them: (lr_t, bias_corr2, ckp1, lr_max, weight_sum) with the two running values updated."""

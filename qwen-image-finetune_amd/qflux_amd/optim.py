@@ -1,14 +1,14 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree, RAdam, NAdam, Adamax) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree, RAdam, NAdam, Adamax, AdEMAMix, AdEMAMix8bit) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
 the two ways of driving the model and with the original packages'.
 
 `params` must be exactly the adapter parameters of ONE model: a plain list, or torch's list of group dicts whose union is that set,
-each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit, PagedLion8bit, RAdam, NAdam and Adamax step several groups
+each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit, PagedLion8bit, RAdam, NAdam, Adamax, AdEMAMix and AdEMAMix8bit step several groups
 in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); Prodigy, Adafactor, CAME,
 Muon and AdamWScheduleFree refuse a second group.  loraplus_param_groups builds the two LoRA+ groups.  The loop has clipped already
 (accelerator.clip_grad_norm_, base_trainer.py:449-455), so step() launches without the fused clip; lr, betas, eps, weight_decay and
@@ -23,7 +23,7 @@ from .trainer import optim_state as OS
 from .trainer.optim_config import optimizer_kwargs_from_config
 
 __all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "CAME", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree",
-           "RAdam", "NAdam", "Adamax", "loraplus_param_groups"]
+           "RAdam", "NAdam", "Adamax", "AdEMAMix", "AdEMAMix8bit", "loraplus_param_groups"]
 
 
 def _find_store(param_groups):
@@ -318,6 +318,28 @@ class Adamax(_FlatOptimizer):
                  differentiable=False, capturable=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize, capturable=capturable,
                          differentiable=differentiable)
+
+
+class AdEMAMix(_FlatOptimizer):
+    """bitsandbytes.optim.AdEMAMix (Adam plus a slow gradient average that enters the update with weight alpha; fp32 states).  betas
+    is the triple (beta1, beta2, beta3); t_alpha / t_beta3: the lengths in steps of the warm-ups of alpha and beta3, None = none."""
+    _PATH = "qflux_amd.optim.AdEMAMix"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999, 0.9999), alpha=5.0, t_alpha=None, t_beta3=None, eps=1e-8, weight_decay=1e-2,
+                 optim_bits=32, min_8bit_size=4096, is_paged=False):
+        super().__init__(params, lr=lr, betas=betas, alpha=alpha, t_alpha=t_alpha, t_beta3=t_beta3, eps=eps, weight_decay=weight_decay,
+                         optim_bits=optim_bits, min_8bit_size=min_8bit_size, is_paged=is_paged)
+
+
+class AdEMAMix8bit(_FlatOptimizer):
+    """bitsandbytes.optim.AdEMAMix8bit: the three states in blockwise 8-bit codes, both averages in one two-plane state1
+    (trainer/optim_state.py).  blocksize (256 or 2048) is this class's own keyword; a file brings its own."""
+    _PATH = "qflux_amd.optim.AdEMAMix8bit"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999, 0.9999), alpha=5.0, t_alpha=None, t_beta3=None, eps=1e-8, weight_decay=1e-2,
+                 min_8bit_size=4096, is_paged=False, *, blocksize=256):
+        super().__init__(params, lr=lr, betas=betas, alpha=alpha, t_alpha=t_alpha, t_beta3=t_beta3, eps=eps, weight_decay=weight_decay,
+                         min_8bit_size=min_8bit_size, is_paged=is_paged, _own_args={"blocksize": blocksize})
 
 
 class AdamWScheduleFree(_FlatOptimizer):

@@ -9,6 +9,7 @@ import torch
 
 BLOCKWISE = ("adam8bit_blockwise", "adamw8bit_blockwise")
 LION_BLOCKWISE = ("lion8bit_blockwise",)      # bitsandbytes.optim.Lion8bit: ONE moment in the same layout (optim_state.LionBlockwiseState)
+ADEMAMIX_BLOCKWISE = ("ademamix8bit_blockwise",)      # bitsandbytes.optim.AdEMAMix8bit: state1 holds two planes (optim_state.AdEMAMixBlockwiseState)
 BLOCKSIZES = (256, 2048)
 
 

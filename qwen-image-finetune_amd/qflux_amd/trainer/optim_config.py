@@ -8,6 +8,7 @@ from . import optim_state as OS
 # class path -> the optimizer= family; a pair is (with state_bits=8, with state_bits=32).  The qflux_amd.optim classes map to the family
 # each of them runs whatever state_bits says; qflux_amd.optim.Lion and torch.optim.SGD are deliberately absent
 _ADAM8, _ADAMW8, _LION8 = ("adam8bit_blockwise", "adam8bit"), ("adamw8bit_blockwise", "adamw"), ("lion8bit_blockwise", "lion")
+_ADEMAMIX8 = ("ademamix8bit_blockwise", "ademamix")
 _FAMILY = {
     "torch.optim.AdamW": "adamw", "bitsandbytes.optim.AdamW": "adamw", "qflux_amd.optim.AdamW": "adamw",
     "torch.optim.Adam": "adam", "bitsandbytes.optim.Adam": "adam", "qflux_amd.optim.Adam": "adam",
@@ -23,6 +24,11 @@ _FAMILY = {
     "schedulefree.AdamWScheduleFree": "adamw_schedulefree", "qflux_amd.optim.AdamWScheduleFree": "adamw_schedulefree",
     "torch.optim.RAdam": "radam", "qflux_amd.optim.RAdam": "radam", "torch.optim.NAdam": "nadam", "qflux_amd.optim.NAdam": "nadam",
     "torch.optim.Adamax": "adamax", "qflux_amd.optim.Adamax": "adamax",
+    "bitsandbytes.optim.AdEMAMix": "ademamix", "bitsandbytes.optim.AdEMAMix32bit": "ademamix",
+    "bitsandbytes.optim.PagedAdEMAMix": "ademamix", "bitsandbytes.optim.PagedAdEMAMix32bit": "ademamix",
+    "qflux_amd.optim.AdEMAMix": "ademamix",
+    "bitsandbytes.optim.AdEMAMix8bit": _ADEMAMIX8, "bitsandbytes.optim.PagedAdEMAMix8bit": _ADEMAMIX8,
+    "qflux_amd.optim.AdEMAMix8bit": _ADEMAMIX8[0],
 }
 # the lr of torch.optim.RAdam / NAdam / Adamax when the config gives none
 _ADAMX_LR = {"radam": 1e-3, "nadam": 2e-3, "adamax": 2e-3}
@@ -77,6 +83,14 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     (decoupled_weight_decay for RAdam and NAdam, momentum_decay for NAdam; none for Adamax); foreach is dropped; maximize,
     capturable and differentiable =True are refused, and so is every keyword the class itself does not take (amsgrad, fused, ...);
     torch's constructor checks apply with torch's messages (ValueError).
+        bitsandbytes.optim.AdEMAMix / AdEMAMix32bit / PagedAdEMAMix / PagedAdEMAMix32bit and qflux_amd.optim.AdEMAMix ->
+    optimizer="ademamix" (lr, betas -- the triple beta1, beta2, beta3 --, eps, weight_decay; left out: lr 1e-3, betas (0.9, 0.999,
+    0.9999), weight decay 1e-2) + optimizer_args (alpha, t_alpha, t_beta3).  bitsandbytes.optim.AdEMAMix8bit / PagedAdEMAMix8bit ->
+    "ademamix" (fp32 states) with state_bits=32, "ademamix8bit_blockwise" (bnb's 8-bit layout with a two-plane state1,
+    min_8bit_size honoured) with state_bits=8 -- the Adam8bit rule; qflux_amd.optim.AdEMAMix8bit always maps to the blockwise form.
+    is_paged and optim_bits are dropped; percentile_clipping != 100, max_unorm != 0, block_wise=False, skip_zeros=True and
+    amsgrad=True are refused, and so is every other keyword; a betas that is no triple, a beta outside [0, 1), a negative lr, eps,
+    weight_decay or alpha and a t_alpha / t_beta3 that is neither None nor > 0 raise ValueError.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -119,7 +133,25 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     if fam is None:
         raise NotImplementedError(f"optimizer {class_path!r} has no fused counterpart (use the drop-in path with the torch optimizer)")
     out["optimizer"] = fam
-    if fam.endswith("_blockwise"):
+    if fam in OS.ADEMAMIX:
+        cls = OS.FAMILIES[fam][0]
+        out.setdefault("lr", 1e-3)
+        out.setdefault("weight_decay", 1e-2)
+        out.setdefault("betas", cls.BETAS)
+        for k, (ok, what) in _REFUSED_8BIT.items():
+            if k in a and a.pop(k) != ok:
+                raise NotImplementedError(f"{class_path}: {what} is not implemented by the fused AdEMAMix step ({k} must be {ok!r})")
+        args = {k: a.pop(k) for k in list(a) if k in cls.OWN}
+        OS.ops.ademamix_check(out["lr"], out["betas"], out.get("eps", 1e-8), out["weight_decay"], **dict(cls.OWN, **args))
+        m8 = a.pop("min_8bit_size", None)      # a keyword of every bnb class; only the 8-bit state reads it
+        if m8 is not None and fam.endswith("_blockwise"):
+            args["min_8bit_size"] = int(m8)
+        a.pop("is_paged", None)        # paged memory: where the state lives, not what is computed
+        a.pop("optim_bits", None)      # the class name decides the state's width
+        out["optimizer_args"] = args
+        if a:      # before the common knobs below are dropped: none of them is a keyword of these classes
+            raise NotImplementedError(f"unsupported optimizer init_args for {class_path}: {sorted(a)}")
+    elif fam.endswith("_blockwise"):
         out.setdefault("weight_decay", 0.01 if fam == "adamw8bit_blockwise" else 0.0)
         for k, (ok, what) in _REFUSED_8BIT.items():
             if k in a and a.pop(k) != ok:

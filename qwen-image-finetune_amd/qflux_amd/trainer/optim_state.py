@@ -1,8 +1,8 @@
 """Device state of the fused optimizers over the flat LoRA buffers, one class per family: AdamWState (fp32 moments, torch.optim.AdamW's
 file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
 AdafactorState (transformers.optimization.Adafactor's), CameState (came_pytorch.CAME's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
-Lion8bit), MuonState (torch.optim.Muon's), ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's) and RAdamState / NAdamState /
-AdamaxState (torch.optim.RAdam's / NAdam's / Adamax's).
+Lion8bit), MuonState (torch.optim.Muon's), ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's), RAdamState / NAdamState /
+AdamaxState (torch.optim.RAdam's / NAdam's / Adamax's) and AdEMAMixState / AdEMAMixBlockwiseState (bitsandbytes' AdEMAMix / AdEMAMix8bit).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
@@ -104,7 +104,7 @@ class FlatState:
         if n_groups > 1 and not cls.GROUPED:
             raise ParamGroupsNotImplemented(f"{cls.FAMILY}: {n_groups} parameter groups -- the fused {cls.FAMILY} step runs over ONE group (its "
                                       "global estimates / per-matrix steps are defined per group in the original package; the grouped "
-                                      "kernels cover AdamW / Adam, SGD, Lion, RAdam, NAdam, Adamax and the blockwise 8-bit families)")
+                                      "kernels cover AdamW / Adam, SGD, Lion, RAdam, NAdam, Adamax, AdEMAMix and the blockwise 8-bit families)")
         if n_groups > ops.MAX_PARAM_GROUPS:
             raise ValueError(f"{n_groups} parameter groups: the grouped kernels take at most {ops.MAX_PARAM_GROUPS}")
 
@@ -972,7 +972,161 @@ class AdamaxState(_AdamXState):
     VARIANT, FAMILY, SECOND = "adamax", "Adamax", "exp_inf"
 
 
+class _AdEMAMix:
+    """What the two AdEMAMix states share: the family's own fields (alpha, t_alpha, t_beta3), their checks and the rows of a step.
+    A group's row is lr / betas (the TRIPLE beta1, beta2, beta3) / eps / weight_decay plus those fields, read from the row where it
+    carries them (the torch.optim classes' param_groups) and from the optimizer_args otherwise.  The schedules alpha_t and beta3_t
+    and the bias corrections are functions of the step count alone and are formed on the host (ops.ademamix_rows): the count is the
+    only thing a resumed run needs beside the buffers."""
+    OWN = dict(alpha=5.0, t_alpha=None, t_beta3=None)
+    BETAS = (0.9, 0.999, 0.9999)
+
+    @classmethod
+    def _check_own(cls, args):
+        if not 0.0 <= args["alpha"]:
+            raise ValueError(f"Invalid alpha value: {args['alpha']}")
+        for n in ("t_alpha", "t_beta3"):
+            if args[n] is not None and not args[n] > 0:
+                raise ValueError(f"Invalid {n} value: {args[n]} (None or > 0)")
+        args["alpha"] = float(args["alpha"])
+
+    def _group_rows(self, lr, betas, eps, weight_decay, args, groups):
+        rows = groups if groups is not None and len(groups) > 1 else [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
+        return [dict({n: args[n] for n in self.OWN}, **r) for r in rows]
+
+    @classmethod
+    def _group_fields(cls, args):
+        return {n: args[n] for n in cls.OWN}
+
+
+class AdEMAMixState(_AdEMAMix, FlatState):
+    """bitsandbytes.optim.AdEMAMix / AdEMAMix32bit: the fast average m1, the slow average m2 and the second moment nu in fp32, indexed
+    like pflat, stepped by the ONE launch of qfx_ademamix_step -- always the grouped entry, one row with one group.  In a file m1
+    and m2 are ONE tensor "m1_m2" shaped [2, *p.shape] next to "nu" and "step"; the names follow the package's state_dict as far as
+    it is known here -- compatibility with a file the package wrote is intended and could NOT be checked (no copy of bitsandbytes
+    at hand)."""
+    NAMES = ("m1", "m2", "nu")
+    GROUPED, FAMILY = True, "AdEMAMix"
+    DEFAULTS = dict(_AdEMAMix.OWN)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.m1 = torch.zeros_like(store.pflat)
+        self.m2 = torch.zeros_like(store.pflat)
+        self.nu = torch.zeros_like(store.pflat)
+
+    @classmethod
+    def validate(cls, args):
+        cls._check_own(args)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        rows = self._group_rows(lr, betas, eps, weight_decay, args, groups)
+        ops.ademamix_step(store.pflat, store.gflat, self.m1, self.m2, self.nu, rows, step, tile_group=self.group_map if len(rows) > 1 else None,
+                          gnorm_sq=gnorm_sq, max_norm=max_norm, grad_scale=grad_scale)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """Per parameter {"step", "m1_m2" [2, *shape], "nu"}; the group carries alpha, t_alpha and t_beta3 next to lr, betas (the
+        triple), eps and weight_decay.  No state before the first step."""
+        if state is None or step == 0:
+            return cls._group_fields(args), {}
+        return cls._group_fields(args), {i: {"step": step, "m1_m2": torch.stack([_out(state.m1, off, k, p.shape), _out(state.m2, off, k, p.shape)]),
+                                             "nu": _out(state.nu, off, k, p.shape)} for i, (_, p, off, k) in enumerate(entries)}
+
+    @classmethod
+    def load(cls, store, sd, args):
+        cls.group_args(sd, args)
+        if not sd["state"]:
+            return None, 0
+        state, step = cls(store, args), 0
+        for i, p, off, k, e in cls.file_entries(store, sd):
+            mm = cls.field(i, p, e, "m1_m2", shape=(2,) + tuple(p.shape)).reshape(2, -1).float()
+            state.m1[off:off + k].copy_(mm[0]); state.m2[off:off + k].copy_(mm[1])
+            state.nu[off:off + k].copy_(cls.field(i, p, e, "nu", numel=k).reshape(-1).float())
+            step = max(step, int(float(cls.field(i, p, e, "step"))))
+        return state, step
+
+
+class AdEMAMixBlockwiseState(_AdEMAMix, _BlockwiseBase):
+    """bitsandbytes.optim.AdEMAMix8bit / PagedAdEMAMix8bit: state1 holds BOTH averages as two planes of signed-map codes (q1 [2, n],
+    absmax1 [2, blocks], m32 [2, ..] for the tensors below min_8bit_size), state2 is nu on the unsigned map (q2, absmax2, v32), over
+    the block table of the other 8-bit families.  In a file: state1 [2, *p.shape], absmax1 [2, blocks], state2, absmax2, qmap1,
+    qmap2, step -- key-compatible with the package's optimizer.bin by intent, NOT checked against one."""
+    MOMENTS = 2
+    FAMILY = "AdEMAMix8bit"
+    DEFAULTS = dict(_BlockwiseBase.DEFAULTS, **_AdEMAMix.OWN)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        dev = store.pflat.device
+        plane = (store.pflat.numel() + 15) // 16 * 16      # the planes of q1 and m32 start on multiples of 4 (qfx.h)
+        self.q1 = torch.zeros(2, plane, dtype=torch.uint8, device=dev)
+        self.absmax1 = torch.zeros(2, max(1, self.layout.n_absmax), dtype=torch.float32, device=dev)
+        self.m32 = torch.zeros(2, max(4, self.layout.n_fp32), dtype=torch.float32, device=dev)
+
+    @classmethod
+    def validate(cls, args, optimizer="blockwise 8-bit state"):
+        _BlockwiseBase.validate(args, optimizer)
+        cls._check_own(args)
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        rows = self._group_rows(lr, betas, eps, weight_decay, args, groups)
+        ops.ademamix8bit_step(store.pflat, store.gflat, self.q1, self.q2, self.absmax1, self.absmax2, self.m32, self.v32, self.layout,
+                              self.qmap1, self.qmap2, rows, step, block_group=self.group_map if len(rows) > 1 else None, gnorm_sq=gnorm_sq,
+                              max_norm=max_norm, grad_scale=grad_scale)
+
+    def param_state(self, i, shape, step):
+        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        two = lambda t, o, n, sh: t[:, o:o + n].reshape((2,) + tuple(sh)).detach().cpu().clone()
+        if not eight:
+            return {"step": step, "state1": two(self.m32, s0, k, shape), "state2": _out(self.v32, s0, k, shape)}
+        return {"step": step, "state1": two(self.q1, off, k, shape), "state2": _out(self.q2, off, k, shape),
+                "qmap1": self.qmap1.cpu().clone(), "qmap2": self.qmap2.cpu().clone(),
+                "absmax1": two(self.absmax1, a0, nb, (nb,)), "absmax2": _out(self.absmax2, a0, nb)}
+
+    def load_param_state(self, i, e):
+        off, k, eight, a0, nb, s0 = self.layout.tensors[i]
+        if (e["state1"].dtype == torch.uint8) != eight:
+            raise ValueError(f"optimizer state of parameter {i} ({k} elements) is {'8-bit' if not eight else 'fp32'} in the file: it was "
+                             f"saved with another min_8bit_size than {self.layout.min_8bit_size}")
+        if e["state1"].numel() != 2 * k or e["state2"].numel() != k:
+            raise ValueError(f"optimizer state of parameter {i}: state1 / state2 have {e['state1'].numel()} / {e['state2'].numel()} elements, "
+                             f"{2 * k} / {k} expected")
+        if not eight:
+            self.m32[:, s0:s0 + k].copy_(e["state1"].reshape(2, -1))
+            self.v32[s0:s0 + k].copy_(e["state2"].reshape(-1))
+            return
+        if e["absmax1"].numel() != 2 * nb or e["absmax2"].numel() != nb:
+            raise ValueError(f"optimizer state of parameter {i}: {e['absmax1'].numel()} / {e['absmax2'].numel()} absmax blocks, {2 * nb} / {nb} expected")
+        self.q1[:, off:off + k].copy_(e["state1"].reshape(2, -1))
+        self.absmax1[:, a0:a0 + nb].copy_(e["absmax1"].reshape(2, -1))
+        self.q2[off:off + k].copy_(e["state2"].reshape(-1))
+        self.absmax2[a0:a0 + nb].copy_(e["absmax2"].reshape(-1))
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """bnb's layout with a two-plane state1 (param_state); the group carries alpha, t_alpha and t_beta3."""
+        return cls._group_fields(args), super().save(state, entries, step, args)[1]
+
+    @classmethod
+    def load(cls, store, sd, args):
+        """The block size is inferred from the file's absmax2 sizes (absmax1 holds two planes)."""
+        cls.group_args(sd, args)
+        one = {i: (dict(e, absmax1=e["absmax2"]) if "absmax2" in e else e) for i, e in sd["state"].items()}
+        bs, q1, q2 = A8.file_layout(one, store.entries)
+        if bs is not None:
+            args["blocksize"] = bs
+        state, step = cls(store, args), 0
+        if q1 is not None:
+            state.qmap1.copy_(q1); state.qmap2.copy_(q2)
+        for i, p, off, k, e in cls.file_entries(store, sd):
+            state.load_param_state(i, e)
+            step = max(step, int(float(e["step"])))
+        return state, step
+
+
 ADAMX = {"radam": RAdamState, "nadam": NAdamState, "adamax": AdamaxState}
+ADEMAMIX = ("ademamix",) + A8.ADEMAMIX_BLOCKWISE
 LION = ("lion",) + A8.LION_BLOCKWISE
 # optimizer= name -> (state class, the weight decay that weight_decay=None stands for: the stood-in optimizer class's own default)
 FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": (SgdState, 0.0), "adafactor": (AdafactorState, 0.0),
@@ -980,15 +1134,19 @@ FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": 
             "lion": (LionState, 0.0), "muon": (MuonState, 0.1), "adamw_schedulefree": (ScheduleFreeAdamWState, 0.0),
             "adam8bit_blockwise": (BlockwiseState, 0.0), "adamw8bit_blockwise": (BlockwiseState, 0.01),
             "lion8bit_blockwise": (LionBlockwiseState, 0.0),
-            "radam": (RAdamState, 0.0), "nadam": (NAdamState, 0.0), "adamax": (AdamaxState, 0.0)}
+            "radam": (RAdamState, 0.0), "nadam": (NAdamState, 0.0), "adamax": (AdamaxState, 0.0),
+            "ademamix": (AdEMAMixState, 0.01), "ademamix8bit_blockwise": (AdEMAMixBlockwiseState, 0.01)}
 
 
 def default_betas(optimizer):
     """The betas a train step uses when its caller gives none: the optimizer class's own default -- (0.9, 0.99) for Lion (both
-    packages), came_pytorch.CAME's triple (0.9, 0.999, 0.9999) for CAME, (0.9, 0.999) for every other family (torch.optim.AdamW's and
+    packages), came_pytorch.CAME's triple (0.9, 0.999, 0.9999) for CAME, AdEMAMix's triple (0.9, 0.999, 0.9999: beta1, beta2 and the
+    slow average's beta3) for the two AdEMAMix families, (0.9, 0.999) for every other family (torch.optim.AdamW's and
     schedulefree.AdamWScheduleFree's, the train steps' default so far)."""
     if optimizer == "came":
         return CameState.BETAS
+    if optimizer in ADEMAMIX:
+        return _AdEMAMix.BETAS
     return (0.9, 0.99) if optimizer in LION else (0.9, 0.999)
 
 
@@ -1031,7 +1189,13 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     the L2 form unless decoupled_weight_decay; optimizer_args: decoupled_weight_decay (False; RAdam and NAdam) and momentum_decay
     (4e-3; NAdam); Adamax takes none.  The classes' own lr defaults (1e-3 / 2e-3 / 2e-3) are what optimizer_kwargs_from_config
     fills in for a config without lr.  maximize, capturable and differentiable are refused.
-    betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, CAME's triple, (0.9, 0.999) --
+    "ademamix": bitsandbytes.optim.AdEMAMix (Pagliardini et al. 2024: Adam plus a slow gradient average m2 that enters the update
+    with weight alpha; include/qfx.h: qfx_ademamix_step, whose listing is the specification); betas is the TRIPLE (0.9, 0.999,
+    0.9999), each in [0, 1); weight decay decoupled, after the update, default the class's 1e-2; optimizer_args: alpha (5.0),
+    t_alpha (None) and t_beta3 (None), the lengths in steps of the warm-ups of alpha and beta3.  "ademamix8bit_blockwise":
+    bitsandbytes.optim.AdEMAMix8bit / PagedAdEMAMix8bit with the three states in blockwise 8-bit codes (both averages in one
+    two-plane state1); optimizer_args: those three plus min_8bit_size (4096) and blocksize (256 or 2048).
+    betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, CAME's and AdEMAMix's triples, (0.9, 0.999) --
     torch.optim.AdamW's, the train step constructor's default before Lion -- for every other one; betas given explicitly are never
     reinterpreted."""
     if optimizer not in ("adam", "adam8bit") and optimizer not in FAMILIES:

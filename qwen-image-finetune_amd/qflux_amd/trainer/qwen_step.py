@@ -62,7 +62,7 @@ class QwenLoraTrainStep:
         param_groups: parameter groups by name -- a list of dicts, each a "match" regex (re.search on the adapter parameter's name)
         plus any of lr, weight_decay, betas, eps; the first matching rule wins, unmatched parameters form the default group with
         this constructor's values (the last group).  The families with grouped kernels (optim_state: AdamW / Adam, SGD, Lion, RAdam,
-        NAdam, Adamax, the blockwise 8-bit ones) step all groups in their one launch; every other family refuses a second group.  An lr schedule
+        NAdam, Adamax, AdEMAMix, the blockwise 8-bit ones) step all groups in their one launch; every other family refuses a second group.  An lr schedule
         written to `self.lr` scales every group's lr by the same factor self.lr / (the constructor's lr), as torch's schedulers do
         with the groups' initial_lr.  loraplus_lr_ratio: shorthand for the two LoRA+ groups of
         qflux_amd.optim.loraplus_param_groups -- lora_A at lr, lora_B at lr * ratio.
