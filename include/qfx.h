@@ -1171,6 +1171,43 @@ int qfx_ademamix8bit_step(const qfx_ademamix8bit_args* a, void* stream);
 int qfx_ademamix8bit_step_grouped(const qfx_ademamix8bit_args* a, const uint8_t* block_group, const qfx_ademamix_group* groups,
                                   int32_t n_groups, void* stream);
 
+/* ---- Per-adapter training telemetry over the flat LoRA buffers (csrc/qfx_adapter_stats.hip): what a training log asks of every
+ * adapter tensor -- its gradient norm, its weight norm, how far the last optimizer step moved it and whether anything in it is
+ * not finite -- in two launches that bracket the optimizer's, instead of a host loop of .norm().item() over ~1400 views.
+ * `table` (device) names the tensors: entry e covers elements off .. off + numel - 1 of p, g and prev; `out` (device) takes one
+ * 32-byte row per entry.  One 256-lane workgroup per entry (blockIdx.x is the entry; more than 4096 entries are walked by stride).
+ *   phase 0, before the optimizer's launch: with g' = g * clip, clip the prologue of qfx_adamw_step (gnorm_sq / max_norm /
+ *     grad_scale: the reported gradient is the one the optimizer steps with; gnorm_sq NULL and grad_scale 1 give clip = 1 exactly),
+ *       grad_sq = sum g'^2, grad_absmax = max |g'|, grad_nonfinite = the number of g' that are NaN or +-inf,
+ *     and prev[off ..] = p[off ..] bit for bit, in the same sweep (elements of prev between the tensors are not written).  Phase 0
+ *     writes the WHOLE row: weight_sq, update_sq, weight_nonfinite, r0 and r1 are set to 0.
+ *   phase 1, behind the optimizer's launch: weight_sq = sum p^2, weight_nonfinite = the number of p that are NaN or +-inf,
+ *     update_sq = sum (p - prev)^2 with the difference rounded to fp32; the other fields of the row are not written.
+ * An element that is not finite (g' in phase 0; p, respectively p - prev, in phase 1) is counted, adds 0 to the sums and is passed
+ * over by the maximum: one NaN leaves the rest of its row readable.  (A finite element whose square overflows makes the sum +inf.)
+ * Order of every sum, whatever the alignment: lane L of the workgroup owns the elements i = L (mod 256) of the tensor and adds
+ * their squares in index order -- one fp32 multiply and one fp32 add per element, the file is built without FMA contraction --
+ * then the 64 lanes of each wave are folded by an xor-shuffle tree (offsets 32, 16, ... 1) and the four wave sums as
+ * (w0 + w1) + (w2 + w3).  tests/adapter_stats_ref.py restates it.  No atomics, nothing crosses a workgroup: same inputs -> same
+ * bits, and a tensor gets the same bits at any address.  16-byte accesses when p + off, prev + off and (phase 0) g + off are
+ * 16-byte aligned (LoraStore starts every tensor on a multiple of 64 elements), scalar ones otherwise.
+ * The kernel skips an entry with numel <= 0 or off < 0 (its row: all zeros in phase 0, the phase-1 fields zero in phase 1); it
+ * does not check extents: every other entry must lie inside the three buffers.  Rejected with QFX_EINVAL before any launch: a NULL
+ * p, prev, table or out, a NULL g in phase 0 (g is not read in phase 1 and may be NULL there), n_entries <= 0, a phase outside
+ * {0, 1}, a max_norm that is negative or NaN, a grad_scale that is not finite. ---- */
+typedef struct qfx_stats_entry {      /* 16 bytes */
+  int64_t off;                        /* first element of the tensor in p / g / prev */
+  int32_t numel;
+  int32_t pad;
+} qfx_stats_entry;
+typedef struct qfx_stats_row {        /* 32 bytes */
+  float   grad_sq, weight_sq, update_sq, grad_absmax;
+  int32_t grad_nonfinite, weight_nonfinite;
+  float   r0, r1;                     /* reserved: 0 */
+} qfx_stats_row;
+int qfx_adapter_stats(const float* p, const float* g, float* prev, const qfx_stats_entry* table, int32_t n_entries,
+                      qfx_stats_row* out, int32_t phase, const float* gnorm_sq, float max_norm, float grad_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

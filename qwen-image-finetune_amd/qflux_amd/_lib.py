@@ -259,6 +259,15 @@ class MaxnormArgs(C.Structure):
                 ("ratios", C.c_void_p), ("summary", C.c_void_p)]
 
 
+class StatsEntry(C.Structure):
+    _fields_ = [("off", C.c_int64), ("numel", C.c_int32), ("pad", C.c_int32)]
+
+
+class StatsRow(C.Structure):
+    _fields_ = [("grad_sq", C.c_float), ("weight_sq", C.c_float), ("update_sq", C.c_float), ("grad_absmax", C.c_float),
+                ("grad_nonfinite", C.c_int32), ("weight_nonfinite", C.c_int32), ("r0", C.c_float), ("r1", C.c_float)]
+
+
 LOSS_L2, LOSS_HUBER, LOSS_SMOOTH_L1 = 0, 1, 2       # QFX_LOSS_*
 
 
@@ -388,6 +397,7 @@ SYMBOLS = {
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
     "qfx_maxnorm_check_table": (C.c_int, [C.POINTER(MaxnormPair), _i32, _i64]),
     "qfx_maxnorm_apply": (C.c_int, [C.POINTER(MaxnormArgs), _vp]),
+    "qfx_adapter_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f, _f, _vp]),
     "qfx_lora_dropout_apply": (C.c_int, [C.POINTER(LoraDropoutArgs), _i32, _vp, _vp]),
     "qfx_lora_dropout_advance": (C.c_int, [_vp, _vp]),
     "qfx_lora_dropout_factors_host": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, _i32, _i32, _i32, C.POINTER(C.c_float)]),

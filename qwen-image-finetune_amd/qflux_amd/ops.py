@@ -906,6 +906,94 @@ def maxnorm_apply(pflat, table, max_norm, norms, ratios, summary):
     L.check(lib.qfx_maxnorm_apply(a, stream_ptr()), "qfx_maxnorm_apply")
 
 
+STATS_ROW_FIELDS = tuple(n for n, _ in L.StatsRow._fields_)
+STATS_ROW_DTYPE = [(n, "<i4" if t is C.c_int32 else "<f4") for n, t in L.StatsRow._fields_]      # numpy view of the 32-byte rows
+
+
+class StatsLayout:
+    """Descriptor table of one flat-buffer layout for qfx_adapter_stats, built once per layout.  `entries[i]` = (off, numel) of
+    table entry i, names[i] its name, kinds[i] "A" / "B" (lora_A / lora_B) or None; extent: elements p / g / prev need."""
+
+    def __init__(self, table, entries, names, kinds, extent):
+        self.table, self.entries, self.names, self.kinds, self.extent = table, entries, names, kinds, extent
+        self.n_entries = len(entries)
+
+
+def stats_table_entries(entries, device=None, names=None, kinds=None):
+    """entries: (off, numel) of every tensor in the flat buffers, in any order.  An entry with numel <= 0 or a negative offset is
+    kept (the kernel skips it and reports a row of zeros); it does not count towards the extent."""
+    rows = [(int(off), int(k)) for off, k in entries]
+    if not rows:
+        raise ValueError("stats table: no tensors")
+    for i, (off, k) in enumerate(rows):
+        if k >= 1 << 31 or k < -(1 << 31):
+            raise ValueError(f"stats table: entry {i} has {k} elements (an entry holds fewer than 2^31)")
+    extent = max([off + k for off, k in rows if k > 0 and off >= 0], default=0)
+    arr = (L.StatsEntry * len(rows))(*[L.StatsEntry(off, k, 0) for off, k in rows])
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    names = [f"entry{i}" for i in range(len(rows))] if names is None else list(names)
+    kinds = [None] * len(rows) if kinds is None else list(kinds)
+    if len(names) != len(rows) or len(kinds) != len(rows):
+        raise ValueError("stats table: one name and one kind per entry")
+    return StatsLayout(table, rows, names, kinds, extent)
+
+
+def stats_table(store, device=None):
+    """The descriptor table of a LoraStore: one entry per adapter tensor of store.params(), in that order, at the offset and with
+    the element count the store packed it with (the padding up to the next multiple of 64 belongs to no entry).  A tensor is named
+    by the key save_lora_weights writes it under (the diffusers style: `transformer.<module>.lora.down.weight` / `.lora.up.weight`
+    for the attention projections, `.lora_A.weight` / `.lora_B.weight` elsewhere); the tensor of an adapter that is not the
+    module's active one -- save_lora_weights leaves it out -- keeps its parameter name."""
+    from .lora_io import _DIFFUSERS_RENAMED
+    from .modules import QfxLoraLinear
+    if store.pflat is None:
+        raise ValueError("stats table: the model has no adapters")
+    where = {id(p): (off, k) for _, p, off, k in store.entries}
+    keys = {}
+    for name, m in store.model.named_modules():
+        if isinstance(m, QfxLoraLinear):
+            down, up = ("lora.down", "lora.up") if name.endswith(_DIFFUSERS_RENAMED) else ("lora_A", "lora_B")
+            keys[id(m.A)] = f"transformer.{name}.{down}.weight"
+            keys[id(m.B)] = f"transformer.{name}.{up}.weight"
+    entries, names, kinds = [], [], []
+    for n, p in store.params():
+        if id(p) not in where:
+            raise ValueError(f"stats table: adapter parameter {n!r} is not in the flat LoRA store")
+        entries.append(where[id(p)])
+        names.append(keys.get(id(p), n))
+        kinds.append("A" if ".lora_A." in n else "B" if ".lora_B." in n else None)
+    return stats_table_entries(entries, device=store.pflat.device if device is None else device, names=names, kinds=kinds)
+
+
+def adapter_stats(p, g, prev, table, out, phase, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
+    """One launch of qfx_adapter_stats on the current stream (qfx.h).  phase 0, before the optimizer's launch: the squared norm,
+    the largest magnitude and the non-finite count of the clipped gradient of every tensor of `table` (a stats_table) into the rows
+    of `out` (uint8 [n_entries * 32]), and prev = p over the tensors.  phase 1, behind it: the squared weight norm, its non-finite
+    count and the squared norm of p - prev.  g may be None in phase 1.  Nothing synchronises."""
+    if phase not in (0, 1):
+        raise ValueError(f"adapter_stats: phase is 0 or 1, not {phase!r}")
+    need = [("p", p), ("prev", prev)] + ([("g", g)] if phase == 0 or g is not None else [])
+    for name, t in need:
+        if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < table.extent or t.device != p.device:
+            raise ValueError(f"adapter_stats: {name} must be a contiguous float32 tensor on {p.device} with >= {table.extent} elements")
+    if out is None or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < 32 * table.n_entries or out.device != p.device:
+        raise ValueError(f"adapter_stats: out must be a contiguous uint8 tensor on {p.device} with >= {32 * table.n_entries} bytes")
+    if table.table.device != p.device:
+        raise ValueError("adapter_stats: the descriptor table lives on another device")
+    if gnorm_sq is not None and (gnorm_sq.dtype != torch.float32 or gnorm_sq.device != p.device):
+        raise ValueError(f"adapter_stats: gnorm_sq must be a float32 tensor on {p.device}")
+    L.check(lib.qfx_adapter_stats(_p(p), _p(g), _p(prev), _p(table.table), table.n_entries, _p(out), phase, _p(gnorm_sq),
+                                  float(max_norm), float(grad_scale), stream_ptr()), "qfx_adapter_stats")
+
+
+def stats_rows(out, n_entries):
+    """The rows of an `out` buffer as a numpy structured array (fields: STATS_ROW_FIELDS): the ONE device-to-host copy."""
+    import numpy as np
+    return np.frombuffer(out[:32 * n_entries].cpu().numpy().tobytes(), dtype=np.dtype(STATS_ROW_DTYPE))
+
+
 LORA_DROPOUT_WORDS = 8      # seed_lo, seed_hi, step, active, thr_elem, thr_rank, scale (fp32 bits), sample0 (include/qfx.h)
 
 

@@ -28,6 +28,7 @@ import torch.distributed as dist
 from .. import dropout as DR
 from .. import ema as E
 from .. import regularize as RG
+from .. import telemetry as TM
 from .. import ops
 from ..dp import LoraGradSync, check_replicas, init_distributed_from_env  # noqa: F401  (the last: bench.py and tools/ import it from here)
 from ..schedules import HUBER_SCHEDULES, WEIGHTING_SCHEMES, flowmatch_tables, huber_threshold, loss_weighting, timestep_density
@@ -54,7 +55,7 @@ class QwenLoraTrainStep:
                  bucket_mb=24.0, optimizer="adamw", optimizer_args=None, param_groups=None, loraplus_lr_ratio=None, ema_decay=None,
                  ema_args=None, weighting_scheme="none", logit_mean=0.0, logit_std=1.0, mode_scale=1.29, timestep_shift=1.0,
                  loss_type="l2", huber_c=0.1, huber_schedule="constant", max_weight_norm=None, network_dropout=None, rank_dropout=None,
-                 dropout_seed=0):
+                 dropout_seed=0, adapter_stats_every=0):
         """optimizer / optimizer_args / weight_decay / betas: the optimizer family, the extra init_args of its class and the defaults
         that None stands for -- every family is described at optim_state.resolve_family, which reads them.  With Prodigy `lr` is the
         schedule multiplier the reference sets to 1.0; with Adafactor lr must be None with relative_step (the default) and a float
@@ -97,7 +98,15 @@ class QwenLoraTrainStep:
         masks of samples k * B ... .  state_dict() / save_checkpoint carry {seed, step, network_dropout, rank_dropout} under the key
         "lora_dropout" only while the feature is on, and loading restores them: a resumed run draws the masks the uninterrupted run
         would have drawn.  Not with the MX-FP8 trunk (NotImplementedError); adapters on the conditioning head run without dropout.
-        Both 0: the plans emit exactly the launches they emit without the option."""
+        Both 0: the plans emit exactly the launches they emit without the option.
+        adapter_stats_every: 0 (off, the default: nothing is allocated or launched) or N > 0 -- per-adapter telemetry
+        (qflux_amd.telemetry): on every optimizer step whose number is a multiple of N two launches bracket the optimizer's and
+        leave, for every adapter tensor, the norm of the clipped gradient the optimizer stepped with, the weight norm, the norm of
+        the update, ||update|| / ||weight||, the gradient's largest magnitude and the non-finite counts on the device.
+        last_adapter_stats reads them (the only host synchronisation; None before the first collected step),
+        adapter_stats_summary() condenses them.  The weights train bit-identically with and without it.  Every optimizer family is
+        served: only the flat weight and gradient buffers are read.  Measured in front of the max-norm clamp and the EMA update.
+        Not with capture_graph (the every-N gate is host control flow)."""
         if criterion not in ("mse", "mask_edit"):
             raise ValueError(f"unknown criterion {criterion!r}")
         self.optimizer_alias, self.optimizer, self._opt_cls, weight_decay, self.optimizer_args = resolve_family(optimizer, weight_decay,
@@ -131,6 +140,10 @@ class QwenLoraTrainStep:
         if self.max_weight_norm is not None and self.optimizer == "adamw_schedulefree":
             raise ValueError("max_weight_norm with optimizer='adamw_schedulefree': scaling y and not z breaks the schedule-free average")
         self.last_weight_norms = None     # qflux_amd.regularize.MaxNormState, from the first step on (max_weight_norm given)
+        if isinstance(adapter_stats_every, bool) or not isinstance(adapter_stats_every, int) or adapter_stats_every < 0:
+            raise ValueError(f"adapter_stats_every must be an int >= 0, not {adapter_stats_every!r}")
+        self.adapter_stats_every = adapter_stats_every
+        self._adapter_stats = None        # qflux_amd.telemetry.AdapterStats, from the first collected step on
         self.blockwise = optimizer in A8.BLOCKWISE
         self.opt_state = None       # the family's optim_state object, from the first step or load_state_dict on
         self.criterion, self.fg, self.bg = criterion, float(forground_weight), float(background_weight)
@@ -342,6 +355,9 @@ class QwenLoraTrainStep:
         replay)."""
         if self.criterion == "mask_edit":
             raise NotImplementedError("capture_graph: the mask_edit criterion takes per-step token weights; use train_step")
+        if self.adapter_stats_every > 0:
+            raise NotImplementedError("capture_graph with adapter_stats_every > 0: collecting on every N-th step is host control "
+                                      "flow; use train_step, or set adapter_stats_every=0")
         dit = self.dit
         packed, target, pe, t_in, S_t = self._prepare(embeddings)
         self._ensure_mod_table()
@@ -551,8 +567,15 @@ class QwenLoraTrainStep:
             self._gparts = torch.zeros(1024, dtype=torch.float32, device=st.pflat.device)
         ops.sumsq_det(st.gflat, self._gnorm, self._gparts)     # fixed reduction order: every replica computes the same clip coefficient
         rows, _ = self.param_groups_of(st)
+        collect = self.adapter_stats_every > 0 and self.global_step % self.adapter_stats_every == 0
+        if collect:      # around the optimizer's launch, same stream: the gradient it steps with, the update it makes
+            if self._adapter_stats is None:
+                self._adapter_stats = TM.AdapterStats(self.dit)
+            self._adapter_stats.before_step(self._gnorm, self.max_grad_norm, grad_scale)
         self.opt_state.step(st, self.lr, self.betas, self.eps, self.weight_decay, self.global_step, self._gnorm, self.max_grad_norm,
                             grad_scale, self.optimizer_args, **({"groups": self._scheduled_rows(rows)} if rows else {}))
+        if collect:
+            self._adapter_stats.after_step()
         if self.max_weight_norm is not None:      # behind the optimizer, before the EMA: the shadows average the clamped weights
             self.last_weight_norms = RG.ensure_state(self.last_weight_norms, st)
             self.last_weight_norms.apply(st, self.max_weight_norm)
@@ -563,6 +586,18 @@ class QwenLoraTrainStep:
         """(keys_scaled, mean norm, max norm) of the last optimizer step's max-norm launch (max_weight_norm given); synchronises.
         None before the first step and without max_weight_norm."""
         return None if self.last_weight_norms is None else self.last_weight_norms.stats()
+
+    @property
+    def last_adapter_stats(self):
+        """{adapter tensor name: {grad_norm, weight_norm, update_norm, update_ratio, grad_absmax, grad_nonfinite, weight_nonfinite}}
+        of the last step that collected (adapter_stats_every), keyed as save_lora_weights keys the tensors; reads on access (one
+        device-to-host copy, the only synchronisation of the feature).  None before the first collected step and with the option off."""
+        return None if self._adapter_stats is None else self._adapter_stats.read()
+
+    def adapter_stats_summary(self):
+        """telemetry.summarize of the last collected step: the global gradient norm, the maximum and median update ratio over the
+        lora_A and over the lora_B tensors, the first tensor with a non-finite gradient.  None where last_adapter_stats is."""
+        return None if self._adapter_stats is None else self._adapter_stats.summary()
 
     @property
     def _m(self):
