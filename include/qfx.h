@@ -1208,6 +1208,68 @@ typedef struct qfx_stats_row {        /* 32 bytes */
 int qfx_adapter_stats(const float* p, const float* g, float* prev, const qfx_stats_entry* table, int32_t n_entries,
                       qfx_stats_row* out, int32_t phase, const float* gnorm_sq, float max_norm, float grad_scale, void* stream);
 
+/* ---- Riemannian-preconditioned ("scaled") AdamW for LoRA pairs (Zhang & Pilanci, "Riemannian Preconditioned LoRA", ICML 2024)
+ * over the flat LoRA buffers (csrc/qfx_scaled_adamw.hip).  Every trainable tensor here is half of a pair W = scaling * B A, and
+ * for any invertible Q the tensors B Q and Q^-1 A are the same adapter, on which AdamW takes different steps; an r x r
+ * preconditioner per pair, taken from the other half's Gram matrix, removes most of that dependence.  The authors' package was not
+ * at hand: THIS LISTING IS THE SPECIFICATION (tests/scaled_adamw_ref.py restates it).  For one pair A [r, in], B [out, r]
+ * (row-major fp32 at off_a / off_b of p, g, exp_avg, exp_avg_sq), step counter t from 1, c = the clip factor exactly as
+ * qfx_adamw_step forms it from gnorm_sq, max_norm and grad_scale:
+ *   gA = c * g_A                      gB = c * g_B                      fp32, as qfx_adamw_step scales g
+ *   G_B = B^T B + reg I   [r, r]      G_A = A A^T + reg I   [r, r]      fp64 sums over fp32 inputs, fixed order; reg is the fp32
+ *                                                                       argument widened
+ *   P_B = G_B^-1                      P_A = G_A^-1                      fp64, Cholesky (reg > 0 makes both SPD), then L Y = I and
+ *                                                                       L^T X = Y; one fp64 rounding per operation
+ *   g^A = fp32(P_B gA)                g^B = fp32(gB P_A)                fp64 dot over the r terms in index order (each product and
+ *                                                                       each sum rounded to fp64), rounded to fp32 once
+ *   AdamW(A, g^A; lr_A, wd_A)         AdamW(B, g^B; lr_B, wd_B)         the operations of qfx_adamw_step in its order, with
+ *                                                                       lr_X = lr * lr_ratio_X (one fp32 multiply), lr_X / bias_corr1
+ *                                                                       and 1 / sqrt(bias_corr2) formed per tensor as it forms them
+ * Both Gram matrices are taken from the weights before either tensor of the pair is written.  bias_corr1 = 1 - beta1^t and
+ * bias_corr2 = 1 - beta2^t are formed on the host, as for qfx_adamw_step.  precondition = 0: no Gram matrix and no inverse is
+ * formed, g^ = c * g, and p, exp_avg and exp_avg_sq of every pair get the bits qfx_adamw_step gives them with the tensor's lr and
+ * weight decay.  Skip rule (the Muon step's): a pair with a non-finite element in its g (either mode), or with a Cholesky pivot
+ * that is not positive and finite, keeps its p, exp_avg and exp_avg_sq unchanged; *skipped (device int32, set to 0 by a memset
+ * node ahead of the launch) counts such pairs.
+ * ONE launch, one 256-lane workgroup per pair, any number of pairs.  A, B and g stream through LDS tiles, both r x r fp64 matrices
+ * live in LDS, the factorisation and the solves run inside the workgroup, a second sweep forms g^ and applies AdamW.  No value
+ * crosses a workgroup but the skip counter (an integer atomic add, order-independent) and every sum runs in an order fixed by the
+ * shape: same inputs -> same bits.  16-byte accesses for a tensor whose p, g, exp_avg and exp_avg_sq addresses are 16-byte
+ * aligned and whose row length (in_features for A, r for B) is a multiple of 4; scalar accesses for any other tensor.
+ * 1 <= r <= 64, 1 <= in, out <= 2^24, any offsets.
+ * qfx_scaled_adamw_check_table runs on a HOST copy of the table: QFX_EINVAL for n_pairs < 0, n_elems < 0, a NULL table with
+ * n_pairs > 0, r outside 1..64, in or out outside 1..2^24, a negative offset, a matrix that reaches past n_elems, two matrices of
+ * the table that overlap, an lr_ratio or a weight decay that is negative or not finite.  The kernel skips a pair with such
+ * dimensions or offsets without counting it; it does not check extents: launch only tables that passed.
+ * qfx_scaled_adamw_step rejects with QFX_EINVAL before any launch: a NULL args, n_pairs < 0, lr or eps negative or NaN, a beta
+ * outside [0, 1), a bias correction that is not > 0, precondition outside {0, 1}, with precondition = 1 a reg that is not finite
+ * and > 0, a NaN max_norm, a grad_scale that is not finite, and with n_pairs > 0 a NULL p, g, exp_avg, exp_avg_sq, table or
+ * skipped.  n_pairs == 0 returns QFX_OK without a launch. ---- */
+typedef struct qfx_scaled_adamw_pair {    /* 48 bytes */
+  int64_t off_a, off_b;                   /* first element of A [r, in] / B [out, r], row-major, in the flat buffers */
+  int32_t r, in_features, out_features;
+  float   lr_ratio_a, lr_ratio_b;         /* the tensor's learning rate over args.lr (LoRA+: 1 and the ratio) */
+  float   wd_a, wd_b;                     /* the tensor's weight decay */
+  int32_t reserved;
+} qfx_scaled_adamw_pair;
+typedef struct qfx_scaled_adamw_args {
+  float* p;                               /* flat adapter weights, stepped in place */
+  const float* g;                         /* flat gradient */
+  float* exp_avg;
+  float* exp_avg_sq;
+  const qfx_scaled_adamw_pair* table;     /* device array */
+  int32_t n_pairs;
+  int32_t precondition;                   /* 1: the listing; 0: plain AdamW per tensor */
+  float   lr, beta1, beta2, eps;
+  float   reg;                            /* delta, > 0 (1e-6) */
+  float   bias_corr1, bias_corr2;
+  const float* gnorm_sq;                  /* the clip prologue of qfx_adamw_step */
+  float   max_norm, grad_scale;
+  int32_t* skipped;                       /* device counter, written */
+} qfx_scaled_adamw_args;
+int qfx_scaled_adamw_check_table(const qfx_scaled_adamw_pair* host_table, int32_t n_pairs, int64_t n_elems);
+int qfx_scaled_adamw_step(const qfx_scaled_adamw_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

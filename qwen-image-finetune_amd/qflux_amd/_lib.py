@@ -259,6 +259,18 @@ class MaxnormArgs(C.Structure):
                 ("ratios", C.c_void_p), ("summary", C.c_void_p)]
 
 
+class ScaledAdamwPair(C.Structure):
+    _fields_ = [("off_a", C.c_int64), ("off_b", C.c_int64), ("r", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32),
+                ("lr_ratio_a", C.c_float), ("lr_ratio_b", C.c_float), ("wd_a", C.c_float), ("wd_b", C.c_float), ("reserved", C.c_int32)]
+
+
+class ScaledAdamwArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("table", C.c_void_p),
+                ("n_pairs", C.c_int32), ("precondition", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("reg", C.c_float), ("bias_corr1", C.c_float), ("bias_corr2", C.c_float), ("gnorm_sq", C.c_void_p),
+                ("max_norm", C.c_float), ("grad_scale", C.c_float), ("skipped", C.c_void_p)]
+
+
 class StatsEntry(C.Structure):
     _fields_ = [("off", C.c_int64), ("numel", C.c_int32), ("pad", C.c_int32)]
 
@@ -397,6 +409,8 @@ SYMBOLS = {
     "qfx_ema_swap": (C.c_int, [_vp, _vp, _i64, _vp]),
     "qfx_maxnorm_check_table": (C.c_int, [C.POINTER(MaxnormPair), _i32, _i64]),
     "qfx_maxnorm_apply": (C.c_int, [C.POINTER(MaxnormArgs), _vp]),
+    "qfx_scaled_adamw_check_table": (C.c_int, [C.POINTER(ScaledAdamwPair), _i32, _i64]),
+    "qfx_scaled_adamw_step": (C.c_int, [C.POINTER(ScaledAdamwArgs), _vp]),
     "qfx_adapter_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f, _f, _vp]),
     "qfx_lora_dropout_apply": (C.c_int, [C.POINTER(LoraDropoutArgs), _i32, _vp, _vp]),
     "qfx_lora_dropout_advance": (C.c_int, [_vp, _vp]),

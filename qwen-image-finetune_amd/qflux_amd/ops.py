@@ -906,6 +906,81 @@ def maxnorm_apply(pflat, table, max_norm, norms, ratios, summary):
     L.check(lib.qfx_maxnorm_apply(a, stream_ptr()), "qfx_maxnorm_apply")
 
 
+SCALED_ADAMW_MAX_RANK = 64
+
+
+class ScaledAdamwLayout:
+    """Descriptor table of one flat-buffer layout for qfx_scaled_adamw_step, built once per layout and grouping.  `pairs[i]` =
+    (off_a, off_b, r, in_features, out_features, lr_ratio_a, lr_ratio_b, wd_a, wd_b) of adapter pair i; extent: elements the flat
+    buffers need."""
+
+    def __init__(self, table, pairs, extent):
+        self.table, self.pairs, self.extent = table, pairs, extent
+        self.n_pairs = len(pairs)
+
+
+def scaled_adamw_table(pairs, device=None, n_elems=None):
+    """pairs: (off_a, off_b, r, in_features, out_features, lr_ratio_a, lr_ratio_b, wd_a, wd_b) of every adapter pair in the flat
+    buffers -- A [r, in] at off_a, B [out, r] at off_b, the tensors' learning rates over the step's lr and their weight decays.
+    Checked by qfx_scaled_adamw_check_table against n_elems (default: the extent of the pairs themselves) before it goes to the
+    device."""
+    rows, extent = [], 0
+    for i, (off_a, off_b, r, nin, nout, ra, rb, wa, wb) in enumerate(pairs):
+        row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(ra), float(rb), float(wa), float(wb))
+        if row[2] > SCALED_ADAMW_MAX_RANK:
+            raise NotImplementedError(f"scaled_adamw table: pair {i} has rank {row[2]}: ranks above {SCALED_ADAMW_MAX_RANK} are not implemented")
+        rows.append(row)
+        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
+    if not rows:
+        raise ValueError("scaled_adamw table: no pairs")
+    arr = (L.ScaledAdamwPair * len(rows))(*[L.ScaledAdamwPair(*r, 0) for r in rows])
+    if lib.qfx_scaled_adamw_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
+        raise ValueError("scaled_adamw table: refused by qfx_scaled_adamw_check_table (a dimension, an offset, an overlap, an lr ratio "
+                         "or a weight decay)")
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return ScaledAdamwLayout(table, rows, extent)
+
+
+def scaled_adamw_check(lr, betas, eps, reg=1e-6, precondition=True):
+    """The constructor checks of the scaled AdamW family (torch.optim.AdamW's, with its messages, and reg > 0)."""
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    if len(betas) != 2:
+        raise ValueError(f"scaled_adamw: betas is a pair, not {betas!r}")
+    for i, b in enumerate(betas):
+        if not 0.0 <= b < 1.0:
+            raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+    if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not (reg > 0 and math.isfinite(reg)):
+        raise ValueError(f"scaled_adamw: reg must be a finite float > 0, not {reg!r}")
+    if not isinstance(precondition, bool):
+        raise ValueError(f"scaled_adamw: precondition must be a bool, not {precondition!r}")
+
+
+def scaled_adamw_step(p, g, m, v, layout, skipped, lr, beta1, beta2, eps, step, reg=1e-6, precondition=True, gnorm_sq=None, max_norm=0.0,
+                      grad_scale=1.0):
+    """One Riemannian-preconditioned AdamW step (qfx.h: qfx_scaled_adamw_step, whose listing is the specification) over the flat
+    fp32 buffers p / g with the moments m / v, one launch for every pair of `layout` (a scaled_adamw_table: the per-tensor lr
+    ratios and weight decays are part of it).  skipped: int32 device tensor of one element, zeroed and written by the launch -- the
+    number of pairs left untouched (a non-finite gradient, a failed factorisation).  Nothing synchronises."""
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < layout.extent or t.device != p.device:
+            raise ValueError(f"scaled_adamw_step: {name} must be a contiguous float32 tensor on {p.device} with >= {layout.extent} elements")
+    if skipped is None or skipped.dtype != torch.int32 or skipped.numel() < 1 or skipped.device != p.device:
+        raise ValueError(f"scaled_adamw_step: skipped must be an int32 tensor on {p.device}")
+    if layout.table.device != p.device:
+        raise ValueError("scaled_adamw_step: the descriptor table lives on another device")
+    scaled_adamw_check(lr, (beta1, beta2), eps, reg, bool(precondition))
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    a = L.ScaledAdamwArgs(_p(p), _p(g), _p(m), _p(v), _p(layout.table), layout.n_pairs, int(bool(precondition)), lr, beta1, beta2, eps,
+                          reg, bc1, bc2, _p(gnorm_sq), max_norm, grad_scale, _p(skipped))
+    L.check(lib.qfx_scaled_adamw_step(a, stream_ptr()), "qfx_scaled_adamw_step")
+
+
 STATS_ROW_FIELDS = tuple(n for n, _ in L.StatsRow._fields_)
 STATS_ROW_DTYPE = [(n, "<i4" if t is C.c_int32 else "<f4") for n, t in L.StatsRow._fields_]      # numpy view of the 32-byte rows
 

@@ -1,7 +1,7 @@
 """The fused optimizers as torch.optim.Optimizer classes, for the reference's unmodified loop.
 
 BaseTrainer.configure_optimizers (base_trainer.py:884-916) builds `cls(lora_layers, **init_args)` from the YAML's class_path; with
-`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree, RAdam, NAdam, Adamax, AdEMAMix, AdEMAMix8bit) that optimizer is one of the classes below and
+`class_path: qflux_amd.optim.Adam8bit` (or AdamW, Adam, AdamW8bit, Prodigy, SGD, Adafactor, CAME, Lion, Lion8bit, PagedLion8bit, Muon, AdamWScheduleFree, RAdam, NAdam, Adamax, AdEMAMix, AdEMAMix8bit, ScaledAdamW) that optimizer is one of the classes below and
 `optimizer.step()` is the family's ONE fused launch over the flat LoRA buffers instead of a foreach over every adapter view.  Each
 class takes the constructor keywords of the class it stands in for and holds the same state object, steps it with the same kernel
 and writes the same optimizer.bin as QwenLoraTrainStep(optimizer=...) (trainer/optim_state.py): files are interchangeable between
@@ -9,7 +9,8 @@ the two ways of driving the model and with the original packages'.
 
 `params` must be exactly the adapter parameters of ONE model: a plain list, or torch's list of group dicts whose union is that set,
 each parameter in exactly one group.  AdamW, Adam, Adam8bit, AdamW8bit, SGD, Lion, Lion8bit, PagedLion8bit, RAdam, NAdam, Adamax, AdEMAMix and AdEMAMix8bit step several groups
-in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); Prodigy, Adafactor, CAME,
+in their one launch (the *_grouped kernels of include/qfx.h; one group launches the ungrouped kernel, as ever); ScaledAdamW takes
+groups too, which may differ in lr and weight_decay only (they become per-tensor fields of its pair table); Prodigy, Adafactor, CAME,
 Muon and AdamWScheduleFree refuse a second group.  loraplus_param_groups builds the two LoRA+ groups.  The loop has clipped already
 (accelerator.clip_grad_norm_, base_trainer.py:449-455), so step() launches without the fused clip; lr, betas, eps, weight_decay and
 the family's own fields are read from every param_groups[k] at every step (schedulers write there).  step() never synchronises
@@ -23,7 +24,7 @@ from .trainer import optim_state as OS
 from .trainer.optim_config import optimizer_kwargs_from_config
 
 __all__ = ["AdamW", "Adam", "Adam8bit", "AdamW8bit", "Prodigy", "SGD", "Adafactor", "CAME", "Lion", "Lion8bit", "PagedLion8bit", "Muon", "AdamWScheduleFree",
-           "RAdam", "NAdam", "Adamax", "AdEMAMix", "AdEMAMix8bit", "loraplus_param_groups"]
+           "RAdam", "NAdam", "Adamax", "AdEMAMix", "AdEMAMix8bit", "ScaledAdamW", "loraplus_param_groups"]
 
 
 def _find_store(param_groups):
@@ -340,6 +341,23 @@ class AdEMAMix8bit(_FlatOptimizer):
                  min_8bit_size=4096, is_paged=False, *, blocksize=256):
         super().__init__(params, lr=lr, betas=betas, alpha=alpha, t_alpha=t_alpha, t_beta3=t_beta3, eps=eps, weight_decay=weight_decay,
                          min_8bit_size=min_8bit_size, is_paged=is_paged, _own_args={"blocksize": blocksize})
+
+
+class ScaledAdamW(_FlatOptimizer):
+    """Riemannian-preconditioned AdamW for LoRA pairs (Zhang & Pilanci, "Riemannian Preconditioned LoRA", ICML 2024): the gradient
+    of lora_A is multiplied by (B^T B + reg I)^-1, that of lora_B by (A A^T + reg I)^-1, then AdamW -- one launch, one workgroup
+    per pair (include/qfx.h: qfx_scaled_adamw_step, whose listing is the specification; the authors' package was not at hand).
+    `params` must be the adapter set of one model, as for Muon: the pairs are found through the model's flat store.  Groups may
+    differ in lr and weight_decay (loraplus_param_groups), not in betas or eps.  precondition=False is plain AdamW per tensor.
+    `skipped` (a device int32 after the first step) counts the pairs the last step left untouched."""
+    _PATH = "qflux_amd.optim.ScaledAdamW"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, reg=1e-6, precondition=True):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, reg=reg, precondition=precondition)
+
+    @property
+    def skipped(self):
+        return None if self._opt_state is None else self._opt_state.skipped
 
 
 class AdamWScheduleFree(_FlatOptimizer):

@@ -29,6 +29,7 @@ _FAMILY = {
     "qflux_amd.optim.AdEMAMix": "ademamix",
     "bitsandbytes.optim.AdEMAMix8bit": _ADEMAMIX8, "bitsandbytes.optim.PagedAdEMAMix8bit": _ADEMAMIX8,
     "qflux_amd.optim.AdEMAMix8bit": _ADEMAMIX8[0],
+    "qflux_amd.optim.ScaledAdamW": "scaled_adamw",
 }
 # the lr of torch.optim.RAdam / NAdam / Adamax when the config gives none
 _ADAMX_LR = {"radam": 1e-3, "nadam": 2e-3, "adamax": 2e-3}
@@ -91,6 +92,9 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
     is_paged and optim_bits are dropped; percentile_clipping != 100, max_unorm != 0, block_wise=False, skip_zeros=True and
     amsgrad=True are refused, and so is every other keyword; a betas that is no triple, a beta outside [0, 1), a negative lr, eps,
     weight_decay or alpha and a t_alpha / t_beta3 that is neither None nor > 0 raise ValueError.
+        qflux_amd.optim.ScaledAdamW -> optimizer="scaled_adamw" (lr, betas, eps, weight_decay; left out: lr 1e-3, weight decay
+    1e-2) + optimizer_args (reg, precondition); reg that is not finite and > 0, a precondition that is no bool and every other
+    keyword are refused.  The authors' package of the method was not at hand, so no class path of theirs is mapped.
     Unknown classes raise: silently training with a different optimizer is worse than stopping."""
     if state_bits not in (8, 32):
         raise ValueError(f"state_bits must be 8 or 32, not {state_bits!r}")
@@ -150,6 +154,16 @@ def optimizer_kwargs_from_config(class_path: str, init_args: dict | None = None,
         a.pop("optim_bits", None)      # the class name decides the state's width
         out["optimizer_args"] = args
         if a:      # before the common knobs below are dropped: none of them is a keyword of these classes
+            raise NotImplementedError(f"unsupported optimizer init_args for {class_path}: {sorted(a)}")
+    elif fam == "scaled_adamw":
+        out.setdefault("lr", 1e-3)
+        out.setdefault("weight_decay", 1e-2)
+        args = _take(a, OS.ScaledAdamWState)
+        full = dict(OS.ScaledAdamWState.DEFAULTS, **args)
+        OS.ScaledAdamWState.validate(full)
+        OS.ops.scaled_adamw_check(out["lr"], out.get("betas", (0.9, 0.999)), out.get("eps", 1e-8), full["reg"], full["precondition"])
+        out["optimizer_args"] = args
+        if a:      # before the common knobs below are dropped: none of them is a keyword of this class
             raise NotImplementedError(f"unsupported optimizer init_args for {class_path}: {sorted(a)}")
     elif fam.endswith("_blockwise"):
         out.setdefault("weight_decay", 0.01 if fam == "adamw8bit_blockwise" else 0.0)

@@ -2,7 +2,8 @@
 file layout), ProdigyState (prodigyopt.Prodigy's), BlockwiseState (bitsandbytes' blockwise 8-bit), SgdState (torch.optim.SGD's),
 AdafactorState (transformers.optimization.Adafactor's), CameState (came_pytorch.CAME's), LionState (lion_pytorch.Lion's), LionBlockwiseState (bitsandbytes'
 Lion8bit), MuonState (torch.optim.Muon's), ScheduleFreeAdamWState (schedulefree.AdamWScheduleFree's), RAdamState / NAdamState /
-AdamaxState (torch.optim.RAdam's / NAdam's / Adamax's) and AdEMAMixState / AdEMAMixBlockwiseState (bitsandbytes' AdEMAMix / AdEMAMix8bit).
+AdamaxState (torch.optim.RAdam's / NAdam's / Adamax's), AdEMAMixState / AdEMAMixBlockwiseState (bitsandbytes' AdEMAMix / AdEMAMix8bit)
+and ScaledAdamWState (Riemannian-preconditioned AdamW for LoRA pairs).
 QwenLoraTrainStep and the torch.optim classes of qflux_amd.optim hold one of them and know only their common surface:
   cls(store, args)               zeroed state for the store's layout; re-created whenever cls.layout_key(store, args) changes
   LAYOUT_ARGS                    the optimizer_args that shape the buffers: broadcast_state agrees on them before the buffers
@@ -116,6 +117,10 @@ class FlatState:
     @staticmethod
     def validate(args):
         pass
+
+    @classmethod
+    def check_rule_fields(cls, k, rule):
+        """A param_groups rule of the train steps, before any store exists: a family refuses here the fields it cannot vary."""
 
     @classmethod
     def group_args(cls, sd, args):
@@ -1125,6 +1130,127 @@ class AdEMAMixBlockwiseState(_AdEMAMix, _BlockwiseBase):
         return state, step
 
 
+class ScaledAdamWState(AdamWState):
+    """Riemannian-preconditioned AdamW for LoRA pairs (Zhang & Pilanci 2024; include/qfx.h: qfx_scaled_adamw_step, whose listing is
+    the specification -- the authors' package was not at hand): AdamW's exp_avg (m) and exp_avg_sq (v) in fp32, indexed like pflat,
+    the table of adapter pairs of the layout and the device counter of pairs the last step left untouched (`skipped`).  The table
+    is built from the store's entries: `X.lora_A.<adapter>.weight` [r, in] pairs with `X.lora_B.<adapter>.weight` [out, r].
+    Parameter groups resolve on the host to the table's per-tensor fields -- a tensor's learning rate over the step's, and its
+    weight decay -- so LoRA+ costs nothing; betas and eps are the launch's and cannot differ between groups.  The table is rebuilt
+    when those fields change.  Files are torch.optim.AdamW's with reg and precondition in the group."""
+    GROUPED, FAMILY = True, "scaled_adamw"
+    DEFAULTS = dict(reg=1e-6, precondition=True)
+
+    def __init__(self, store, args):
+        super().__init__(store, args)
+        self.pairs = self.adapter_pairs(store.entries)
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=store.pflat.device)
+        self.layout = self._fields = None
+
+    @staticmethod
+    def adapter_pairs(entries):
+        """(module, index of lora_A's entry, index of lora_B's entry, r, in_features, out_features) of every adapter pair, in the
+        order of the lora_A entries.  NotImplementedError naming the module for a tensor without its partner, a shape that is no
+        pair's and a rank above 64."""
+        at = {n: i for i, (n, _, _, _) in enumerate(entries)}
+        pairs, used = [], set()
+        for i, (n, p, _, _) in enumerate(entries):
+            if ".lora_A." not in n:
+                continue
+            module = n.split(".lora_A.")[0]
+            j = at.get(n.replace(".lora_A.", ".lora_B."))
+            if j is None:
+                raise NotImplementedError(f"scaled_adamw: the adapter of {module!r} has a lora_A without its lora_B: the preconditioner "
+                                          "of a tensor is taken from its partner")
+            q = entries[j][1]
+            if p.dim() != 2 or q.dim() != 2 or q.shape[1] != p.shape[0]:
+                raise NotImplementedError(f"scaled_adamw: the adapter of {module!r} is no pair A [r, in], B [out, r]: lora_A is "
+                                          f"{tuple(p.shape)}, lora_B is {tuple(q.shape)}")
+            r, nin = (int(d) for d in p.shape)
+            if r > ops.SCALED_ADAMW_MAX_RANK:
+                raise NotImplementedError(f"scaled_adamw: the adapter of {module!r} has rank {r}; ranks above "
+                                          f"{ops.SCALED_ADAMW_MAX_RANK} are not implemented")
+            pairs.append((module, i, j, r, nin, int(q.shape[0])))
+            used.update((i, j))
+        for i, (n, _, _, _) in enumerate(entries):
+            if i not in used:
+                module = n.split(".lora_B.")[0]
+                raise NotImplementedError(f"scaled_adamw: the adapter tensor {n!r} of {module!r} has no partner: the fused step is "
+                                          "defined on lora_A / lora_B pairs only")
+        return pairs
+
+    @classmethod
+    def _base_key(cls, store, args):
+        return super()._base_key(store, args) + (tuple((n, tuple(p.shape)) for n, p, _, _ in store.entries),)
+
+    @staticmethod
+    def validate(args):
+        reg, pre = args["reg"], args["precondition"]
+        if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not (reg > 0 and reg < float("inf")):
+            raise ValueError(f"scaled_adamw: reg must be a finite float > 0, not {reg!r}")
+        if not isinstance(pre, bool):
+            raise ValueError(f"scaled_adamw: precondition must be a bool, not {pre!r}")
+        args["reg"] = float(reg)
+
+    @classmethod
+    def check_rule_fields(cls, k, rule):
+        on = [n for n in ("betas", "eps") if n in rule]
+        if on:
+            raise ParamGroupsNotImplemented(f"{cls.FAMILY}: param_groups[{k}] sets {' / '.join(on)}: a pair is stepped by one workgroup "
+                                            "with the launch's betas and eps; a group may set lr and weight_decay")
+
+    def build_group_map(self, store, assign, n_groups):
+        """The group of every store entry, on the host: the groups become per-tensor fields of the pair table."""
+        return tuple(assign)
+
+    def table_fields(self, lr, betas, eps, weight_decay, groups):
+        """(the launch's lr, [(lr_ratio_a, lr_ratio_b, wd_a, wd_b) of every pair as the fp32 values the table holds]).  One group: the
+        step's lr, ratios 1 and the step's weight decay.  Several: the rows alone decide, as in the other grouped families -- the
+        launch's lr is group 0's and every tensor carries its group's lr over that."""
+        f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float32))
+        if groups is None or len(groups) <= 1 or self.group_map is None:
+            return lr, [(1.0, 1.0, f32(weight_decay), f32(weight_decay))] * len(self.pairs)
+        for k, row in enumerate(groups):
+            if tuple(row.get("betas", betas)) != tuple(betas) or row.get("eps", eps) != eps:
+                raise ParamGroupsNotImplemented(f"{self.FAMILY}: parameter group {k} has its own betas / eps: a pair is stepped by one "
+                                                "workgroup with the launch's; a group may set lr and weight_decay")
+        base = groups[0]["lr"]
+        ratio = [f32(row["lr"] / base) if base != 0 else 1.0 for row in groups]
+        wd = [f32(row["weight_decay"]) for row in groups]
+        g = self.group_map
+        return base, [(ratio[g[i]], ratio[g[j]], wd[g[i]], wd[g[j]]) for _, i, j, _, _, _ in self.pairs]
+
+    def ensure_table(self, store, fields):
+        if self.layout is None or self._fields != fields:
+            off = [o for _, _, o, _ in store.entries]
+            self.layout = ops.scaled_adamw_table([(off[i], off[j], r, nin, nout) + f for (_, i, j, r, nin, nout), f in zip(self.pairs, fields)],
+                                                 device=store.pflat.device, n_elems=store.pflat.numel())
+            self._fields = fields
+        return self.layout
+
+    def step(self, store, lr, betas, eps, weight_decay, step, gnorm_sq, max_norm, grad_scale, args, groups=None):
+        self.validate(args)
+        lr, fields = self.table_fields(lr, betas, eps, weight_decay, groups)
+        layout = self.ensure_table(store, fields)
+        ops.scaled_adamw_check(lr, betas, eps, args["reg"], args["precondition"])
+        ops.scaled_adamw_step(store.pflat, store.gflat, self.m, self.v, layout, self.skipped, lr, betas[0], betas[1], eps, step,
+                              reg=args["reg"], precondition=args["precondition"], gnorm_sq=gnorm_sq, max_norm=max_norm,
+                              grad_scale=grad_scale)
+
+    @classmethod
+    def save(cls, state, entries, step, args):
+        """torch.optim.AdamW's per-parameter {"step", "exp_avg", "exp_avg_sq"}; the group carries reg and precondition."""
+        group, per = super().save(state, entries, step, args)
+        return dict(group, **{n: args[n] for n in cls.DEFAULTS}), per
+
+    @classmethod
+    def load(cls, store, sd, args):
+        cls.group_args(sd, args)
+        if not sd["state"]:
+            return None, 0
+        return super().load(store, sd, args)
+
+
 ADAMX = {"radam": RAdamState, "nadam": NAdamState, "adamax": AdamaxState}
 ADEMAMIX = ("ademamix",) + A8.ADEMAMIX_BLOCKWISE
 LION = ("lion",) + A8.LION_BLOCKWISE
@@ -1135,7 +1261,8 @@ FAMILIES = {"adamw": (AdamWState, 0.01), "prodigy": (ProdigyState, 0.0), "sgd": 
             "adam8bit_blockwise": (BlockwiseState, 0.0), "adamw8bit_blockwise": (BlockwiseState, 0.01),
             "lion8bit_blockwise": (LionBlockwiseState, 0.0),
             "radam": (RAdamState, 0.0), "nadam": (NAdamState, 0.0), "adamax": (AdamaxState, 0.0),
-            "ademamix": (AdEMAMixState, 0.01), "ademamix8bit_blockwise": (AdEMAMixBlockwiseState, 0.01)}
+            "ademamix": (AdEMAMixState, 0.01), "ademamix8bit_blockwise": (AdEMAMixBlockwiseState, 0.01),
+            "scaled_adamw": (ScaledAdamWState, 0.01)}
 
 
 def default_betas(optimizer):
@@ -1195,6 +1322,11 @@ def resolve_family(optimizer, weight_decay=None, optimizer_args=None):
     t_alpha (None) and t_beta3 (None), the lengths in steps of the warm-ups of alpha and beta3.  "ademamix8bit_blockwise":
     bitsandbytes.optim.AdEMAMix8bit / PagedAdEMAMix8bit with the three states in blockwise 8-bit codes (both averages in one
     two-plane state1); optimizer_args: those three plus min_8bit_size (4096) and blocksize (256 or 2048).
+    "scaled_adamw": Riemannian-preconditioned AdamW for LoRA pairs (Zhang & Pilanci, ICML 2024; include/qfx.h:
+    qfx_scaled_adamw_step, whose listing is the specification -- the authors' package was not at hand): the gradient of each half of
+    a pair is multiplied by the inverse of the other half's r x r Gram matrix plus reg I, then AdamW; weight decay decoupled,
+    default 1e-2; optimizer_args: reg (1e-6; finite and > 0) and precondition (True; False is plain AdamW per tensor).  Parameter
+    groups and LoRA+ set per-tensor lr and weight decay; per-group betas / eps are refused; ranks above 64 are refused.
     betas=None (the default) means the optimizer class's own default: (0.9, 0.99) for the two Lion families, CAME's and AdEMAMix's triples, (0.9, 0.999) --
     torch.optim.AdamW's, the train step constructor's default before Lion -- for every other one; betas given explicitly are never
     reinterpreted."""

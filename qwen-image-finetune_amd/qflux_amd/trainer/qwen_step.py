@@ -456,6 +456,7 @@ class QwenLoraTrainStep:
             if "match" not in r or unknown:
                 raise ValueError(f"param_groups[{k}]: a rule is a dict with a 'match' regex and any of {self._RULE_FIELDS}" +
                                  (f", not {sorted(unknown)}" if unknown else ""))
+            self._opt_cls.check_rule_fields(k, r)
             out.append(dict(r, match=re.compile(r["match"]), **({"betas": tuple(r["betas"])} if "betas" in r else {})))
         self._opt_cls.check_groups(len(out))      # a second group is refused here by the families without grouped kernels
         return out
