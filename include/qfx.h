@@ -1270,6 +1270,90 @@ typedef struct qfx_scaled_adamw_args {
 int qfx_scaled_adamw_check_table(const qfx_scaled_adamw_pair* host_table, int32_t n_pairs, int64_t n_elems);
 int qfx_scaled_adamw_step(const qfx_scaled_adamw_args* a, void* stream);
 
+/* ---- The singular value decomposition of every adapter pair dW = B A over the flat LoRA buffer (csrc/qfx_lora_svd.hip): the
+ * spectrum of each adapter, and kohya's resize_lora.py -- a trained pair re-expressed at a lower rank by truncated SVD -- without
+ * ever forming the [out, in] product.  Appended under ABI 7: new structs and entry points only.  kohya's script was not at hand:
+ * THIS LISTING IS THE SPECIFICATION (tests/lora_svd_ref.py restates it in numpy).  For one pair A [r, in], B [out, r] (row-major
+ * fp32 at off_a / off_b of p), 1 <= r <= 64, 1 <= in, out <= 2^24, any offsets:
+ *   G_A = A A^T,  G_B = B^T B               [r, r] fp64 sums over the widened fp32 inputs, fixed order (as qfx_maxnorm_apply forms them)
+ *   G_A = V L V^T                           cyclic Jacobi in LDS, fp64 (below); negative l set to 0
+ *   K   = L^1/2 V^T G_B                     [r, r] fp64: dots over the r terms in index order, then the one multiply by l_i^1/2
+ *   H   = K V L^1/2                         [r, r] fp64, likewise; symmetrised: H_ij = H_ji = (H_ij + H_ji) / 2
+ *   H   = W Th W^T                          cyclic Jacobi; th sorted descending (ties by index), negative th set to 0
+ *   sv[i]  = sqrt(th_i)                     the singular values of B A (unscaled: the caller multiplies by |scaling|), written as
+ *                                           fp64 sv [n_pairs, ld_sv]; entries r <= i < ld_sv are written 0
+ *   rho    = #{ i : sv[i] > rank_tol sv[0] }    (0 when sv[0] == 0)
+ *   T_B = V L^1/2 W             [r, r]      B T_B = U S;  columns i >= rho written as 0        ((V_ik l_k^1/2) W_kj summed over k in order)
+ *   T_A = Th^-1 W^T K           [r, r]      T_A A = V^T (the right singular vectors as rows);  rows i >= rho written as 0
+ *   info[pair] = { rho, sweeps of the first solve, sweeps of the second solve, converged (both) }    int32 x 4
+ * No division occurs except by th_i for i < rho (and those of the rotations).  T_B and T_A go as fp64 to the caller's workspace
+ * ws [n_pairs][2][64][64] (T_B first; row stride 64; everything outside the r x r corner written 0); ws == NULL: the spectrum
+ * only, neither is formed.
+ * The Jacobi solve of a symmetric M [n, n]: thr = 2^-52 ||M||_F / n; before each sweep off = max_{i<j} |M_ij|, the solve ends
+ * converged when off <= thr and ends unconverged after max_sweeps sweeps (what it has is still written).  A sweep is n' - 1 rounds
+ * (n' = n rounded up to even; index n is padding) of the round-robin ordering: round d pairs n' - 1 with d, and (d + k) mod (n' - 1)
+ * with (d - k) mod (n' - 1) for k = 1 .. n'/2 - 1.  For each pair p < q of a round, from the matrix as the round finds it:
+ *   M_pq == 0: c = 1, s = 0;  else tau = (M_qq - M_pp) / (2 M_pq), t = sign(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c
+ * then every pair's columns (x, y) = (M_ip, M_iq) -> (c x - s y, s x + c y), the same on the accumulated vectors, then every pair's
+ * rows likewise, with M_pq and M_qp set to 0.  Every trip count is fixed by r and max_sweeps: the kernel cannot spin (a NaN never
+ * meets the criterion and runs to the cap).
+ * Skip rule (Muon's, max-norm's): a pair with a non-finite Gram entry gets sv = 0, info = 0 (so converged = 0), a zero workspace,
+ * and *skipped (device int32, set to 0 by a memset node ahead of the launch) counts it.
+ * qfx_lora_spectrum: ONE launch, one 256-lane workgroup per pair, any number of pairs.  Both Gram matrices, both eigenproblems
+ * and the transforms live in LDS (138 KB); no atomics but the integer skip counter, nothing else crosses a workgroup: same inputs
+ * -> same bits at any address.  16-byte accesses for the tiles where A is 16-byte aligned and in % 4 == 0, resp. B 16-byte aligned
+ * and r % 4 == 0; scalar ones otherwise.
+ * qfx_lora_project: ONE launch, one workgroup per pair; reads p, ws and, per pair, dst = { dst_off_a, dst_off_b, k components
+ * kept (1 <= k <= r), r_dst rows allocated (k <= r_dst <= 64) }; writes A' [r_dst, in] and B' [out, r_dst] into another buffer q:
+ *   B'[:, j] = fp32(sum_i B[:, i] T_B[i, j])   j < k      fp64 products and sums in index order from +0, one rounding to fp32
+ *   A'[j, :] = fp32(sum_i T_A[j, i] A[i, :])   j < k
+ *   columns / rows k <= j < r_dst are written as +0.0
+ * kohya's split: lora_up = U S, lora_down = V^T; the pair's scaling is unchanged, so the new lora_alpha is scaling * r_dst.
+ * 16-byte stores of B' where its address is 16-byte aligned and r_dst % 4 == 0, 16-byte loads and stores for A' where A and A'
+ * are 16-byte aligned and in % 4 == 0.
+ * The two check functions run on HOST copies of the tables: QFX_EINVAL for n_pairs < 0, n_elems < 0, a NULL table with
+ * n_pairs > 0, r outside 1..64, in or out outside 1..2^24, a negative offset, a matrix that reaches past n_elems, two matrices of
+ * the table that overlap; qfx_lora_project_check_table (destination side, against the extent of q) also for k outside 1..r and
+ * r_dst outside k..64.  The kernels skip a pair with such dimensions or offsets (spectrum: as a skipped pair, not counted;
+ * project: nothing written); they do not check extents: launch only tables that passed.
+ * qfx_lora_spectrum rejects with QFX_EINVAL before any launch: a NULL args, n_pairs < 0, a rank_tol that is not in (0, 1),
+ * max_sweeps outside 1..64, ld_sv < 64, with n_pairs > 0 a NULL p, table, sv, info or skipped.  qfx_lora_project: a NULL args,
+ * n_pairs < 0, q == p, with n_pairs > 0 a NULL p, q, table, dst or ws.  n_pairs == 0 returns QFX_OK without a launch. ---- */
+typedef struct qfx_lora_svd_pair {        /* 32 bytes */
+  int64_t off_a, off_b;                   /* first element of A [r, in] / B [out, r], row-major, in p */
+  int32_t r, in_features, out_features;
+  int32_t reserved;
+} qfx_lora_svd_pair;
+typedef struct qfx_lora_svd_dst {         /* 24 bytes */
+  int64_t dst_off_a, dst_off_b;           /* first element of A' [r_dst, in] / B' [out, r_dst], row-major, in q */
+  int32_t k, r_dst;
+} qfx_lora_svd_dst;
+typedef struct qfx_lora_spectrum_args {
+  const float* p;                         /* flat adapter weights, read */
+  const qfx_lora_svd_pair* table;         /* device array */
+  int32_t n_pairs;
+  int32_t max_sweeps;                     /* 1..64 (30) */
+  double  rank_tol;                       /* in (0, 1) (1e-6) */
+  double* sv;                             /* [n_pairs, ld_sv], written */
+  int64_t ld_sv;                          /* >= 64 */
+  int32_t* info;                          /* [n_pairs, 4], written */
+  double* ws;                             /* [n_pairs][2][64][64], written; may be NULL */
+  int32_t* skipped;                       /* device counter, written */
+} qfx_lora_spectrum_args;
+typedef struct qfx_lora_project_args {
+  const float* p;                         /* the buffer qfx_lora_spectrum read */
+  float* q;                               /* another flat buffer, written */
+  const qfx_lora_svd_pair* table;         /* device array */
+  const qfx_lora_svd_dst* dst;            /* device array */
+  int32_t n_pairs;
+  int32_t reserved;
+  const double* ws;                       /* what qfx_lora_spectrum wrote */
+} qfx_lora_project_args;
+int qfx_lora_svd_check_table(const qfx_lora_svd_pair* host_table, int32_t n_pairs, int64_t n_elems);
+int qfx_lora_project_check_table(const qfx_lora_svd_pair* host_table, const qfx_lora_svd_dst* host_dst, int32_t n_pairs, int64_t n_elems_dst);
+int qfx_lora_spectrum(const qfx_lora_spectrum_args* a, void* stream);
+int qfx_lora_project(const qfx_lora_project_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,6 +271,25 @@ class ScaledAdamwArgs(C.Structure):
                 ("max_norm", C.c_float), ("grad_scale", C.c_float), ("skipped", C.c_void_p)]
 
 
+class LoraSvdPair(C.Structure):
+    _fields_ = [("off_a", C.c_int64), ("off_b", C.c_int64), ("r", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class LoraSvdDst(C.Structure):
+    _fields_ = [("dst_off_a", C.c_int64), ("dst_off_b", C.c_int64), ("k", C.c_int32), ("r_dst", C.c_int32)]
+
+
+class LoraSpectrumArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("table", C.c_void_p), ("n_pairs", C.c_int32), ("max_sweeps", C.c_int32), ("rank_tol", C.c_double),
+                ("sv", C.c_void_p), ("ld_sv", C.c_int64), ("info", C.c_void_p), ("ws", C.c_void_p), ("skipped", C.c_void_p)]
+
+
+class LoraProjectArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("q", C.c_void_p), ("table", C.c_void_p), ("dst", C.c_void_p), ("n_pairs", C.c_int32),
+                ("reserved", C.c_int32), ("ws", C.c_void_p)]
+
+
 class StatsEntry(C.Structure):
     _fields_ = [("off", C.c_int64), ("numel", C.c_int32), ("pad", C.c_int32)]
 
@@ -411,6 +430,10 @@ SYMBOLS = {
     "qfx_maxnorm_apply": (C.c_int, [C.POINTER(MaxnormArgs), _vp]),
     "qfx_scaled_adamw_check_table": (C.c_int, [C.POINTER(ScaledAdamwPair), _i32, _i64]),
     "qfx_scaled_adamw_step": (C.c_int, [C.POINTER(ScaledAdamwArgs), _vp]),
+    "qfx_lora_svd_check_table": (C.c_int, [C.POINTER(LoraSvdPair), _i32, _i64]),
+    "qfx_lora_project_check_table": (C.c_int, [C.POINTER(LoraSvdPair), C.POINTER(LoraSvdDst), _i32, _i64]),
+    "qfx_lora_spectrum": (C.c_int, [C.POINTER(LoraSpectrumArgs), _vp]),
+    "qfx_lora_project": (C.c_int, [C.POINTER(LoraProjectArgs), _vp]),
     "qfx_adapter_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f, _f, _vp]),
     "qfx_lora_dropout_apply": (C.c_int, [C.POINTER(LoraDropoutArgs), _i32, _vp, _vp]),
     "qfx_lora_dropout_advance": (C.c_int, [_vp, _vp]),

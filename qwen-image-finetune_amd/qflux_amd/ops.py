@@ -906,6 +906,108 @@ def maxnorm_apply(pflat, table, max_norm, norms, ratios, summary):
     L.check(lib.qfx_maxnorm_apply(a, stream_ptr()), "qfx_maxnorm_apply")
 
 
+LORA_SVD_MAX_RANK = 64
+LORA_SVD_RANK_TOL = 1e-6
+LORA_SVD_MAX_SWEEPS = 30
+LORA_SVD_WS_DOUBLES = 2 * 64 * 64          # per pair: T_B and T_A, [64][64] fp64 each
+
+
+class LoraSvdLayout:
+    """Descriptor table of one flat-buffer layout for qfx_lora_spectrum / qfx_lora_project, built once per layout.  `pairs[i]` =
+    (off_a, off_b, r, in_features, out_features) of adapter pair i; extent: elements p needs; host: the ctypes array."""
+
+    def __init__(self, table, pairs, extent, host):
+        self.table, self.pairs, self.extent, self.host = table, pairs, extent, host
+        self.n_pairs = len(pairs)
+
+
+def lora_svd_table(pairs, device=None, n_elems=None):
+    """pairs: (off_a, off_b, r, in_features, out_features) of every adapter pair in the flat buffer -- A [r, in] at off_a,
+    B [out, r] at off_b.  Checked by qfx_lora_svd_check_table against n_elems (default: the extent of the pairs themselves)
+    before it goes to the device."""
+    rows, extent = [], 0
+    for i, (off_a, off_b, r, nin, nout) in enumerate(pairs):
+        row = (int(off_a), int(off_b), int(r), int(nin), int(nout))
+        if row[2] > LORA_SVD_MAX_RANK:
+            raise NotImplementedError(f"lora_svd table: pair {i} has rank {row[2]}: ranks above {LORA_SVD_MAX_RANK} are not implemented")
+        rows.append(row)
+        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
+    if not rows:
+        raise ValueError("lora_svd table: no pairs")
+    arr = (L.LoraSvdPair * len(rows))(*[L.LoraSvdPair(*r, 0) for r in rows])
+    if lib.qfx_lora_svd_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
+        raise ValueError("lora_svd table: refused by qfx_lora_svd_check_table (a dimension, an offset or an overlap)")
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return LoraSvdLayout(table, rows, extent, arr)
+
+
+def _svd_buf(what, name, t, dtype, n, dev):
+    if t is None or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() < n or t.device != dev:
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor on {dev} with >= {n} elements")
+
+
+def lora_spectrum(pflat, table, sv, info, skipped, ws=None, rank_tol=LORA_SVD_RANK_TOL, max_sweeps=LORA_SVD_MAX_SWEEPS):
+    """The singular values of B A of every pair of `table` (a lora_svd_table) in ONE launch: sv [n_pairs, ld_sv >= 64] fp64,
+    info [n_pairs, 4] int32 (numeric rank, sweeps of the two solves, converged), skipped [1] int32, and with ws
+    [n_pairs * LORA_SVD_WS_DOUBLES] fp64 the transforms T_B / T_A that lora_project reads.  Nothing synchronises.  See qfx.h."""
+    rank_tol, max_sweeps = float(rank_tol), int(max_sweeps)
+    if not 0.0 < rank_tol < 1.0:
+        raise ValueError(f"lora_spectrum: rank_tol must lie in (0, 1), not {rank_tol}")
+    if not 1 <= max_sweeps <= 64:
+        raise ValueError(f"lora_spectrum: max_sweeps must lie in 1..64, not {max_sweeps}")
+    dev, n = pflat.device, table.n_pairs
+    if sv is None or sv.dim() != 2 or sv.shape[0] < n or sv.shape[1] < 64:
+        raise ValueError(f"lora_spectrum: sv must be [>= {n}, >= 64]")
+    _svd_buf("lora_spectrum", "pflat", pflat, torch.float32, table.extent, dev)
+    _svd_buf("lora_spectrum", "sv", sv, torch.float64, n * 64, dev)
+    _svd_buf("lora_spectrum", "info", info, torch.int32, 4 * n, dev)
+    _svd_buf("lora_spectrum", "skipped", skipped, torch.int32, 1, dev)
+    if ws is not None:
+        _svd_buf("lora_spectrum", "ws", ws, torch.float64, n * LORA_SVD_WS_DOUBLES, dev)
+    if table.table.device != dev:
+        raise ValueError("lora_spectrum: the descriptor table lives on another device")
+    a = L.LoraSpectrumArgs(_p(pflat), _p(table.table), n, max_sweeps, rank_tol, _p(sv), sv.shape[1], _p(info),
+                           _p(ws) if ws is not None else None, _p(skipped))
+    L.check(lib.qfx_lora_spectrum(a, stream_ptr()), "qfx_lora_spectrum")
+
+
+def lora_project_table(table, dst, device=None, n_elems=None):
+    """dst: (dst_off_a, dst_off_b, k, r_dst) per pair of `table` (a lora_svd_table).  Checked by qfx_lora_project_check_table
+    against n_elems, the extent of the destination buffer (default: the extent of the rows themselves).  -> (device table, extent)"""
+    if len(dst) != table.n_pairs:
+        raise ValueError(f"lora_project table: {len(dst)} destinations for {table.n_pairs} pairs")
+    rows, extent = [], 0
+    for (off_a, off_b, k, r_dst), (_, _, _, nin, nout) in zip(dst, table.pairs):
+        row = (int(off_a), int(off_b), int(k), int(r_dst))
+        rows.append(row)
+        extent = max(extent, row[0] + row[3] * nin, row[1] + nout * row[3])
+    arr = (L.LoraSvdDst * len(rows))(*[L.LoraSvdDst(*r) for r in rows])
+    if lib.qfx_lora_project_check_table(table.host, arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
+        raise ValueError("lora_project table: refused by qfx_lora_project_check_table (k, r_dst, an offset or an overlap)")
+    t = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        t = t.to(device)
+    return t, extent
+
+
+def lora_project(pflat, qflat, table, dst_table, ws):
+    """B' = fp32(B T_B[:, :k]), A' = fp32(T_A[:k] A) of every pair into another flat buffer, in ONE launch; dst_table from
+    lora_project_table, ws what lora_spectrum wrote.  See qfx.h."""
+    dev, n = pflat.device, table.n_pairs
+    dst, extent = dst_table
+    _svd_buf("lora_project", "pflat", pflat, torch.float32, table.extent, dev)
+    _svd_buf("lora_project", "qflat", qflat, torch.float32, extent, dev)
+    _svd_buf("lora_project", "ws", ws, torch.float64, n * LORA_SVD_WS_DOUBLES, dev)
+    if qflat.data_ptr() == pflat.data_ptr():
+        raise ValueError("lora_project: the destination must be another buffer")
+    if table.table.device != dev or dst.device != dev:
+        raise ValueError("lora_project: a descriptor table lives on another device")
+    a = L.LoraProjectArgs(_p(pflat), _p(qflat), _p(table.table), _p(dst), n, 0, _p(ws))
+    L.check(lib.qfx_lora_project(a, stream_ptr()), "qfx_lora_project")
+
+
 SCALED_ADAMW_MAX_RANK = 64
 
 

@@ -588,6 +588,14 @@ class QwenLoraTrainStep:
         None before the first step and without max_weight_norm."""
         return None if self.last_weight_norms is None else self.last_weight_norms.stats()
 
+    def adapter_spectrum(self, **kw):
+        """qflux_amd.spectrum.adapter_spectrum of the model: {module name: the singular values of scaling * B @ A}.  One launch on
+        the current stream OUTSIDE the captured step graph and one device-to-host copy; its buffers are allocated on the first
+        call and kept for the store layout (FluxKontextTrainStep inherits it)."""
+        from .. import spectrum as SP
+        self._spectrum_state = SP.ensure_state(getattr(self, "_spectrum_state", None), self.dit)
+        return SP.adapter_spectrum(self.dit, state=self._spectrum_state, **kw)
+
     @property
     def last_adapter_stats(self):
         """{adapter tensor name: {grad_norm, weight_norm, update_norm, update_ratio, grad_absmax, grad_nonfinite, weight_nonfinite}}
