@@ -1354,6 +1354,84 @@ int qfx_lora_project_check_table(const qfx_lora_svd_pair* host_table, const qfx_
 int qfx_lora_spectrum(const qfx_lora_spectrum_args* a, void* stream);
 int qfx_lora_project(const qfx_lora_project_args* a, void* stream);
 
+/* ---- A rank-k factorisation D ~ Q C of every dense difference D = W1 - W0 of a device table (csrc/qfx_lora_extract.hip):
+ * kohya's extract_lora_from_models.py by a randomized range finder (Halko, Martinsson, Tropp 2011, algorithms 4.4 / 5.1) instead
+ * of a full SVD per layer.  Appended under ABI 7: new structs and entry points only.  kohya's script was not at hand:
+ * THIS LISTING IS THE SPECIFICATION (tests/lora_extract_ref.py restates it in numpy).  For matrix m of the table, W1 and W0
+ * [out, in] row-major with leading dimensions ld1 / ld0, both bf16 (dtype 0) or both fp32 (dtype 1), 1 <= k <= 64,
+ * 1 <= in, out <= 2^24:
+ *   D      = fp32(W1) - fp32(W0)            one fp32 subtraction per element; W0 == NULL: D = W1.  Formed before any product.
+ *   Omega  [in, k] of +-1                   Philox4x32-10 (the generator of the dropout masks above), key = (seed_lo, seed_hi),
+ *                                           counter = (row i, index, 0x4C524B58, 0) with `index` the field of the table row;
+ *                                           Omega[i, j] = +1 if bit j & 31 of output word j >> 5 is clear, else -1
+ *   Y = D Omega;  Q = orth(Y)
+ *   q times:  Z = orth(D^T Q);  Q = orth(D Z)                0 <= q <= 4
+ *   C = Q^T D                               [k, in]
+ * Every product is over the fp32 values of D and of the other operand, one fp32 FMA per term in ascending order of the summed
+ * index, the result an fp32 [out, k] resp. [in, k] matrix.  Nothing is rounded to bf16.
+ * orth(Y) is o(o(Y)) with o(Y), for Y [n, k] fp32:
+ *   G = Y^T Y                               [k, k] fp64 over the widened fp32 values (every product exact): per chunk of 64 rows
+ *                                           in row order, the chunks' partials added in chunk order through the workspace
+ *   G = V L V^T                             the cyclic Jacobi solve of the qfx_lora_spectrum listing above: the same ordering,
+ *                                           threshold, sweep cap (max_sweeps) and fixed trip counts; l sorted descending, ties
+ *                                           by index
+ *   kept = #{ i : l_i > orth_tol l_0 }      (0 when l_0 <= 0)
+ *   T_ij = V_ij / sqrt(l_j)  for j < kept,  0 otherwise
+ *   o(Y) = fp32(Y T)                        fp64 products and sums in index order from +0, one rounding to fp32; the columns
+ *                                           j >= kept come out as +0
+ * The variant is rank-revealing on purpose: rank(D) < k (a model with a LoRA merged in) and k > min(out, in) leave the surplus
+ * columns of Q and rows of C zero where a Cholesky QR would break down.
+ * Output: Q as B [out, k] at off_b and C as A [k, in] at off_a of the flat fp32 buffer p, row-major: rows (off_a, off_b, k, in,
+ * out) are a qfx_lora_svd_pair table with r = k for qfx_lora_spectrum / qfx_lora_project.  normsq[m] = ||D||_F^2 in fp64 (a
+ * lane's elements in its order, the 256 lanes by a fixed tree, the chunks' partials in residue classes mod 256, then the tree).
+ * info[m] = { kept of the last orth, the converged flags of every Jacobi solve of the matrix ANDed }.
+ * Skip rule (Muon's, max-norm's): a matrix with a non-finite element of D gets A = 0, B = 0, normsq = 0, info = 0, and *skipped
+ * (device int32, set to 0 by a memset node ahead of the launches) counts it.
+ * qfx_lowrank_sketch enqueues 8 + 10 q launches and the memset on the stream, whatever the data; no host synchronisation, no
+ * host -> device copy (host_table is read at enqueue time only: for the checks below and the grid sizes), so it can sit in a
+ * captured graph.  The grids cover (chunk, matrix); a table may mix shapes and dtypes.  16-byte loads of W1 / W0 where both are
+ * 16-byte aligned with leading dimensions that are multiples of 8 (bf16) resp. 4 (fp32) elements, scalar ones otherwise; the
+ * edges of a 64 x 64 tile are handled in the kernel.  No floating-point atomics: same inputs -> same bits at any address.
+ * ws: qfx_lowrank_sketch_workspace bytes (QFX_EINVAL, negative, for what the check below refuses in k / in / out / dtype / ld /
+ * W1), 16-byte aligned; its contents need not survive between calls.
+ * qfx_lowrank_check_table runs on a HOST copy of the table: QFX_EINVAL for n_mats < 0, n_elems < 0, a NULL table with
+ * n_mats > 0, k outside 1..64, in or out outside 1..2^24, a leading dimension < in, a dtype other than 0 or 1, a NULL W1,
+ * a negative offset, an output that reaches past n_elems, two outputs that overlap.
+ * qfx_lowrank_sketch rejects with QFX_EINVAL before any launch: a NULL args, n_mats outside 0..65535, q outside 0..4, max_sweeps
+ * outside 1..64, an orth_tol that is not in [0, 1), with n_mats > 0 a NULL table, host_table, p, normsq, info, skipped or ws, a
+ * ws that is not 16-byte aligned or shorter than qfx_lowrank_sketch_workspace says, and whatever qfx_lowrank_check_table refuses
+ * of host_table against n_elems.  n_mats == 0 returns QFX_OK without a launch. ---- */
+typedef struct qfx_lowrank_mat {          /* 80 bytes */
+  const void* w1;                         /* [out, in], device */
+  const void* w0;                         /* [out, in], device; NULL: D = W1 */
+  int64_t ld1, ld0;                       /* elements */
+  int64_t off_a, off_b;                   /* first element of A = C [k, in] / B = Q [out, k] in p */
+  int32_t k, in_features, out_features;
+  int32_t dtype;                          /* 0: bf16, 1: fp32 */
+  int32_t index;                          /* counter word 1 of Omega */
+  int32_t reserved[3];
+} qfx_lowrank_mat;
+typedef struct qfx_lowrank_args {
+  const qfx_lowrank_mat* table;           /* device array */
+  const qfx_lowrank_mat* host_table;      /* the same rows on the host */
+  int32_t n_mats;
+  int32_t q;                              /* power iterations, 0..4 (2) */
+  uint32_t seed_lo, seed_hi;
+  double  orth_tol;                       /* in [0, 1) (1e-12) */
+  int32_t max_sweeps;                     /* 1..64 (30) */
+  int32_t reserved;
+  float* p;                               /* flat output buffer, written */
+  int64_t n_elems;                        /* its extent */
+  double* normsq;                         /* [n_mats], written */
+  int32_t* info;                          /* [n_mats, 2], written */
+  int32_t* skipped;                       /* device counter, written */
+  void* ws;
+  int64_t ws_bytes;
+} qfx_lowrank_args;
+int qfx_lowrank_check_table(const qfx_lowrank_mat* host_table, int32_t n_mats, int64_t n_elems);
+int64_t qfx_lowrank_sketch_workspace(const qfx_lowrank_mat* host_table, int32_t n_mats);
+int qfx_lowrank_sketch(const qfx_lowrank_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,19 @@ class LoraProjectArgs(C.Structure):
                 ("reserved", C.c_int32), ("ws", C.c_void_p)]
 
 
+class LowrankMat(C.Structure):
+    _fields_ = [("w1", C.c_void_p), ("w0", C.c_void_p), ("ld1", C.c_int64), ("ld0", C.c_int64), ("off_a", C.c_int64), ("off_b", C.c_int64),
+                ("k", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32), ("dtype", C.c_int32), ("index", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class LowrankArgs(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("host_table", C.c_void_p), ("n_mats", C.c_int32), ("q", C.c_int32), ("seed_lo", C.c_uint32),
+                ("seed_hi", C.c_uint32), ("orth_tol", C.c_double), ("max_sweeps", C.c_int32), ("reserved", C.c_int32), ("p", C.c_void_p),
+                ("n_elems", C.c_int64), ("normsq", C.c_void_p), ("info", C.c_void_p), ("skipped", C.c_void_p), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_int64)]
+
+
 class StatsEntry(C.Structure):
     _fields_ = [("off", C.c_int64), ("numel", C.c_int32), ("pad", C.c_int32)]
 
@@ -434,6 +447,9 @@ SYMBOLS = {
     "qfx_lora_project_check_table": (C.c_int, [C.POINTER(LoraSvdPair), C.POINTER(LoraSvdDst), _i32, _i64]),
     "qfx_lora_spectrum": (C.c_int, [C.POINTER(LoraSpectrumArgs), _vp]),
     "qfx_lora_project": (C.c_int, [C.POINTER(LoraProjectArgs), _vp]),
+    "qfx_lowrank_check_table": (C.c_int, [C.POINTER(LowrankMat), _i32, _i64]),
+    "qfx_lowrank_sketch_workspace": (_i64, [C.POINTER(LowrankMat), _i32]),
+    "qfx_lowrank_sketch": (C.c_int, [C.POINTER(LowrankArgs), _vp]),
     "qfx_adapter_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f, _f, _vp]),
     "qfx_lora_dropout_apply": (C.c_int, [C.POINTER(LoraDropoutArgs), _i32, _vp, _vp]),
     "qfx_lora_dropout_advance": (C.c_int, [_vp, _vp]),

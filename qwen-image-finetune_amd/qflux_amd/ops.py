@@ -1008,6 +1008,81 @@ def lora_project(pflat, qflat, table, dst_table, ws):
     L.check(lib.qfx_lora_project(a, stream_ptr()), "qfx_lora_project")
 
 
+LOWRANK_MAX_K = 64
+LOWRANK_MAX_POWER_ITERS = 4
+LOWRANK_ORTH_TOL = 1e-12
+_LOWRANK_DTYPES = {torch.bfloat16: 0, torch.float32: 1}
+
+
+class LowrankLayout:
+    """Descriptor table of qfx_lowrank_sketch, built once per set of matrices.  rows[i] = (off_a, off_b, k, in_features,
+    out_features): the same rows are a lora_svd_table of the output buffer with r = k.  extent: elements the output needs;
+    host: the ctypes array (read again at every launch); ws_bytes: the workspace; keep: the tensors the table points at."""
+
+    def __init__(self, table, rows, extent, host, ws_bytes, keep):
+        self.table, self.rows, self.extent, self.host, self.ws_bytes, self.keep = table, rows, extent, host, ws_bytes, keep
+        self.n_mats = len(rows)
+
+
+def lowrank_table(mats, device=None, n_elems=None):
+    """mats: (W1, W0 or None, k, off_a, off_b[, index]) per matrix -- W1 / W0 2-D device tensors [out, in] with unit column stride,
+    both bfloat16 or both float32; Q [out, k] goes to off_b and C [k, in] to off_a of the flat output buffer; index (default: the
+    position in the list) keys the test matrix.  Checked by qfx_lowrank_check_table against n_elems (default: the extent of the
+    rows themselves) before it goes to the device."""
+    rows, structs, keep, extent = [], [], [], 0
+    for i, mat in enumerate(mats):
+        W1, W0, k, off_a, off_b = mat[:5]
+        index = int(mat[5]) if len(mat) > 5 else i
+        if W1 is None or W1.dim() != 2 or W1.dtype not in _LOWRANK_DTYPES or W1.stride(1) != 1:
+            raise ValueError(f"lowrank table: matrix {i}: W1 must be a 2-D bfloat16 or float32 tensor with unit column stride")
+        if W0 is not None and (W0.shape != W1.shape or W0.dtype != W1.dtype or W0.stride(1) != 1 or W0.device != W1.device):
+            raise ValueError(f"lowrank table: matrix {i}: W0 must match W1 in shape, dtype and device")
+        if int(k) > LOWRANK_MAX_K:
+            raise NotImplementedError(f"lowrank table: matrix {i} asks for k = {k}: sketches wider than {LOWRANK_MAX_K} are not implemented")
+        nout, nin = W1.shape
+        row = (int(off_a), int(off_b), int(k), int(nin), int(nout))
+        rows.append(row)
+        structs.append(L.LowrankMat(_p(W1), _p(W0) if W0 is not None else None, W1.stride(0) if nout > 1 else max(W1.stride(0), nin),
+                                    (W0.stride(0) if nout > 1 else max(W0.stride(0), nin)) if W0 is not None else 0,
+                                    row[0], row[1], row[2], row[3], row[4], _LOWRANK_DTYPES[W1.dtype], index))
+        keep.append((W1, W0))
+        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
+    if not rows:
+        raise ValueError("lowrank table: no matrices")
+    arr = (L.LowrankMat * len(rows))(*structs)
+    if lib.qfx_lowrank_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
+        raise ValueError("lowrank table: refused by qfx_lowrank_check_table (a dimension, a leading dimension, an offset or an overlap)")
+    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    if device is not None:
+        table = table.to(device)
+    return LowrankLayout(table, rows, extent, arr, int(lib.qfx_lowrank_sketch_workspace(arr, len(rows))), keep)
+
+
+def lowrank_sketch(table, pflat, normsq, info, skipped, ws, power_iters=2, seed=0, orth_tol=LOWRANK_ORTH_TOL,
+                   max_sweeps=LORA_SVD_MAX_SWEEPS):
+    """D = W1 - W0 ~ Q C of every matrix of `table` (a lowrank_table) by a randomized range finder with `power_iters` power
+    iterations: Q [out, k] and C [k, in] into pflat at the table's offsets, normsq [n] fp64 = ||D||_F^2, info [n, 2] int32 (columns
+    kept, converged), skipped [1] int32; ws: uint8, >= table.ws_bytes.  A fixed sequence of launches, nothing synchronises.  See qfx.h."""
+    power_iters, max_sweeps, orth_tol, seed = int(power_iters), int(max_sweeps), float(orth_tol), int(seed)
+    if not 0 <= power_iters <= LOWRANK_MAX_POWER_ITERS:
+        raise ValueError(f"lowrank_sketch: power_iters must lie in 0..{LOWRANK_MAX_POWER_ITERS}, not {power_iters}")
+    if not 0.0 <= orth_tol < 1.0:
+        raise ValueError(f"lowrank_sketch: orth_tol must lie in [0, 1), not {orth_tol}")
+    if not 1 <= max_sweeps <= 64:
+        raise ValueError(f"lowrank_sketch: max_sweeps must lie in 1..64, not {max_sweeps}")
+    dev, n = pflat.device, table.n_mats
+    _svd_buf("lowrank_sketch", "pflat", pflat, torch.float32, table.extent, dev)
+    _svd_buf("lowrank_sketch", "normsq", normsq, torch.float64, n, dev)
+    _svd_buf("lowrank_sketch", "info", info, torch.int32, 2 * n, dev)
+    _svd_buf("lowrank_sketch", "skipped", skipped, torch.int32, 1, dev)
+    _svd_buf("lowrank_sketch", "ws", ws, torch.uint8, table.ws_bytes, dev)
+    if table.table.device != dev or any(w1.device != dev for w1, _ in table.keep):
+        raise ValueError("lowrank_sketch: the descriptor table or a matrix lives on another device")
+    a = L.LowrankArgs(_p(table.table), C.cast(table.host, C.c_void_p), n, power_iters, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                      orth_tol, max_sweeps, 0, _p(pflat), pflat.numel(), _p(normsq), _p(info), _p(skipped), _p(ws), ws.numel())
+    L.check(lib.qfx_lowrank_sketch(a, stream_ptr()), "qfx_lowrank_sketch")
+
+
 SCALED_ADAMW_MAX_RANK = 64
 
 
