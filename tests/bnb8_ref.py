@@ -84,11 +84,19 @@ def step_scalars(lr, b1, b2, eps, wd, t):
                 wd=wd32 > 0)
 
 
+def sqrt_rn(x):
+    """The correctly rounded square root, as the kernel's sqrtf is.  torch.sqrt on fp32 CPU tensors is a vectorised approximation
+    that misses the correctly rounded value on part of its inputs -- how many, and which, depends on the machine; numpy's is the
+    hardware instruction."""
+    with np.errstate(all="ignore"):
+        return torch.from_numpy(np.sqrt(x.detach().numpy()))
+
+
 def _update(p, gs, m, v, K, fp32_form):
     fin = torch.isfinite(gs)
     m2 = m * K["b1"] + K["omb1"] * gs
     v2 = v * K["b2"] + K["omb2"] * (gs * gs) if fp32_form else v * K["b2"] + (K["omb2"] * gs) * gs
-    p2 = p + K["step_size"] * (m2 / (torch.sqrt(v2) + K["eps_hat"]))
+    p2 = p + K["step_size"] * (m2 / (sqrt_rn(v2) + K["eps_hat"]))
     if K["wd"]:
         p2 = p2 * K["decay"]
     return torch.where(fin, p2, p), torch.where(fin, m2, m), torch.where(fin, v2, v)
@@ -161,6 +169,7 @@ class Adam8bitRef:
                 bs = blocksize_of(st, p.numel())
                 m = dequant(st["state1"], st["qmap1"], st["absmax1"], bs)
                 v = dequant(st["state2"], st["qmap2"], st["absmax2"], bs)
+                _, st["_m64"], st["_v64"] = _update(pf.double(), gs.double(), m.double(), v.double(), K, False)     # the float64 twins
                 pn, m, v = _update(pf, gs, m, v, K, False)
                 c1, c2, a1, a2 = encode(m, v, st["qmap1"], st["qmap2"], bs)
                 st["state1"], st["state2"] = c1.view(p.shape), c2.view(p.shape)
@@ -179,3 +188,163 @@ def blocksize_of(st, numel):
         if st["absmax1"].numel() == (numel + bs - 1) // bs:
             return bs
     raise ValueError("no block size fits")
+
+
+# ---------------------------------------------------------------- the exact comparison rule of the blockwise 8-bit kernels
+# (shared by tests/lion_ref.py and tests/ademamix_ref.py).  A kernel is held to the fp32 restatement bit for bit wherever that is a
+# statement about the kernel: the parameters, the block maxima and the fp32 moments of small tensors.  A stored code is the outcome
+# of a comparison x > mid, and there the rule says which elements the comparison decides.
+#
+# Between the fp32 moment m and that comparison lie two rounded operations:
+#   x^   = fl(m / mx)                   one division:         x^   = x   (1 + d1),  x = m / mx exactly
+#   mid^ = fl(q[k] + q[k + 1]) / 2      one midpoint average: mid^ = mid (1 + d2),  the halving is exact
+# Correctly rounded, |d1|, |d2| <= u = 2^-24.  x^ > mid^ and x > mid can differ only when |x - mid| <= |d1| |x| + |d2| |mid|.  The
+# rule grants each operation a whole ulp (2u = EPS32: a division that is faithfully, not correctly, rounded), so an element is
+# DECIDED when its margin min_k |x - mid_k| > EPS32 (|x| + |mid_k|), margin and midpoints evaluated in float64 (2^-53: nothing
+# beside u).  The bound is relative and vanishes at zero with the quantities themselves.  The sign repair of a signed state is a
+# further boundary at x = 0; it is taken on the sign BIT of m, which no operation rounds, so |x| > EPS32 |x| decides every m != 0,
+# and m = +-0 is decided as well: 0 / mx is exact.  A block with maximum 0 performs no division: decided.
+# A block is UNDECIDED, all its elements with it, when its maximum is tied: the float64 twin of the update (the same statement
+# evaluated in double from the same decoded state) holds an element within TIE_ULPS fp32 ulp of the block's float64 maximum whose
+# fp32 magnitude is not the block's fp32 maximum -- the two rounded apart, and one more rounding somewhere could name the other.
+EPS32 = float(np.finfo(np.float32).eps)
+TIE_ULPS = 4.0
+UNDECIDED_CAP = 1e-4          # share of the compared elements per step that may be undecided (lion_ref.UNDECIDED_CAP is this)
+
+
+def code_margin(m, mx, qmap, signed):
+    """(margin, bound) in float64 per element: the distance of m / mx from the nearest boundary (a code midpoint; for a signed
+    state also 0, the sign repair) and the rule's bound at that boundary.  mx: the block maximum per element, > 0."""
+    x = m.double() / mx.double()
+    q = qmap.double()
+    mid = (q[:-1] + q[1:]) / 2.0
+    k = torch.searchsorted(mid, x.contiguous(), side="left")
+    margin = torch.full_like(x, float("inf"))
+    bound = torch.zeros_like(x)
+    for kk in ((k - 1).clamp(0, 254), k.clamp(0, 254)):
+        b = mid[kk]
+        d, lim = (x - b).abs(), EPS32 * (x.abs() + b.abs())
+        closer = d - lim < margin - bound
+        margin, bound = torch.where(closer, d, margin), torch.where(closer, lim, bound)
+    if signed:
+        d, lim = x.abs(), EPS32 * x.abs()
+        closer = (d - lim < margin - bound) & (m != 0)
+        margin, bound = torch.where(closer, d, margin), torch.where(closer, lim, bound)
+    return margin, bound
+
+
+def tied_blocks(m, m64, blk, n_blocks):
+    """bool[n_blocks]: the blocks whose maximum is tied (see above).  m: the fp32 moments, m64: their float64 twins, blk: the block
+    of every element."""
+    a32, a64 = m.abs(), m64.abs()
+    top32 = torch.zeros(n_blocks, dtype=a32.dtype).scatter_reduce_(0, blk, a32, "amax")
+    top64 = torch.zeros(n_blocks, dtype=a64.dtype).scatter_reduce_(0, blk, a64, "amax")
+    other = torch.where(a32 == top32[blk], torch.zeros_like(a64), a64)
+    rival = torch.zeros(n_blocks, dtype=a64.dtype).scatter_reduce_(0, blk, other, "amax")
+    return (rival > 0) & (rival >= top64 * (1.0 - TIE_ULPS * EPS32))
+
+
+def undecided_codes(m, m64, blk, n_blocks, qmap, signed):
+    """bool per element: True where the rule lets the stored code differ by one step.  Also returns the fp32 block maxima."""
+    mx = torch.zeros(n_blocks, dtype=torch.float32).scatter_reduce_(0, blk, m.abs(), "amax")
+    d = mx[blk]
+    live = d > 0
+    margin, bound = code_margin(m, torch.where(live, d, torch.ones_like(d)), qmap, signed)
+    und = live & ~(margin > bound)
+    return und | tied_blocks(m, m64, blk, n_blocks)[blk], mx
+
+
+def sign_repaired(m, mx_elem, qmap1):
+    """bool per element: the restatement takes the keep-the-sign branch of a signed state there."""
+    live = mx_elem > 0
+    x = torch.where(live, m / torch.where(live, mx_elem, torch.ones_like(mx_elem)), torch.zeros_like(m))
+    return live & (torch.signbit(qmap1[quantize(x, qmap1)]) != torch.signbit(m))
+
+
+def same_bits(a, b):
+    a, b = (t.reshape(-1).clone(memory_format=torch.contiguous_format) for t in (a, b))      # (a one-element view keeps its parent's stride: clone, not contiguous)
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.uint8), b.view(torch.uint8))
+
+
+def ulp_diff(a, b):
+    """Largest distance of two fp32 tensors in units in the last place (finite values; 0 where the bits are equal)."""
+    ia, ib = (t.contiguous().view(torch.int32).long() for t in (a, b))
+    ia, ib = (torch.where(t < 0, -(t & 0x7FFFFFFF), t) for t in (ia, ib))
+    return int((ia - ib).abs().max()) if a.numel() else 0
+
+
+def check_codes(got, want, und, where):
+    """The rule on one buffer of codes: identical on decided elements, within one step elsewhere.  Returns (decided mismatches,
+    undecided elements that differ)."""
+    got, want = got.reshape(-1).long(), want.reshape(-1).long()
+    diff = got != want
+    bad = int((diff & ~und).sum())
+    assert bad == 0, (where, f"{bad} decided codes differ", torch.nonzero(diff & ~und).flatten()[:8].tolist())
+    assert not diff.any() or int((got - want).abs().max()) <= 1, (where, "an undecided code is more than one step off")
+    return bad, int(diff.sum())
+
+
+# ---------------------------------------------------------------- the inputs tests/test_adam8bit_gpu.py (the kernel) and
+# tests/test_blockwise8_cpu.py (the undecided census of the same steps, without a device) share
+SIZES = [1000, 4096, 5000, 300, 9000, 20000, 64, 4100]      # a LoraStore-like flat buffer: tensors below 4096 elements, lengths that
+KW = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_norm=1.0, grad_scale=0.5)      # are no multiple of a block size
+
+
+def file_cases(bs):
+    """(sizes, min_8bit_size, seed of the parameters, steps) of the two restatement tests of test_adam8bit_gpu.py: SIZES, and 259
+    elements (8-bit, the last block short), exactly one block and 5 elements (fp32 moments) at min_8bit_size 256."""
+    return {"sizes": (SIZES, 4096, 1, 5), "clipped": ([256 + 3, bs, 5], 256, 3, 3)}
+
+
+def flat_offsets(sizes):
+    offs, off = [], 0
+    for k in sizes:
+        offs.append(off)
+        off += (k + 63) // 64 * 64
+    return offs, off
+
+
+def make_params(sizes, seed):
+    torch.manual_seed(seed)
+    return [torch.randn(k) * 0.1 for k in sizes]
+
+
+def make_grads(sizes, it, bs):
+    g = torch.Generator().manual_seed(100 + it)
+    out = [torch.randn(k, generator=g) * (10.0 ** (i % 3 - 1)) for i, k in enumerate(sizes)]
+    if sizes != SIZES:
+        return out
+    out[4][:bs] = 0.0                                   # an all-zero block (with zero state: absmax 0, the code of 0.0)
+    if it == 2:
+        out[2][17] = float("nan")
+        out[5][3000] = float("inf")
+    if it == 3:
+        out[0][5] = float("-inf")                       # a small (fp32-moment) tensor
+    return out
+
+
+def gnorm_sq(grads):
+    """Sum of squares of the finite gradient elements (what the tests hand both sides as the clip's norm)."""
+    return float(sum(torch.nan_to_num(g.double(), nan=0.0, posinf=0.0, neginf=0.0).pow(2).sum() for g in grads))
+
+
+def file_reference(which, bs):
+    """The restatement and the gradients of one of file_cases: (opt, [(grads, gnorm_sq)]); the caller steps opt."""
+    sizes, min8, seed, steps = file_cases(bs)[which]
+    opt = Adam8bitRef(make_params(sizes, seed), lr=KW["lr"], betas=KW["betas"], eps=KW["eps"], weight_decay=KW["weight_decay"],
+                      min_8bit_size=min8, blocksize=bs)
+    steps = [(g, gnorm_sq(g)) for g in (make_grads(sizes, it, bs) for it in range(steps))]
+    return opt, steps
+
+
+def census(opt, bs):
+    """(codes, undecided codes) of the step opt just took, by the rule above."""
+    tot = n_und = 0
+    for p, st in zip(opt.params, opt.state):
+        if st["state1"].dtype != torch.uint8:
+            continue
+        blk = torch.arange(p.numel()) // bs
+        for mk, qk, sg in (("_m", "qmap1", True), ("_v", "qmap2", False)):
+            n_und += int(undecided_codes(st[mk], st[mk + "64"], blk, st["absmax1"].numel(), st[qk], sg)[0].sum())
+            tot += p.numel()
+    return tot, n_und

@@ -23,6 +23,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from bnb8_ref import UNDECIDED_CAP as B8_UNDECIDED_CAP
 from bnb8_ref import blocks_absmax, clip_coef, create_dynamic_map, dequant, keep_sign, quantize
 
 F32 = np.float32
@@ -82,6 +83,7 @@ class LionRef:
         self.qmap1 = create_dynamic_map(True)
         self.state = [{} for _ in params]
         self.undecided = [None for _ in params]       # per tensor, of the last step (test diagnostics)
+        self.m64 = [None for _ in params]             # per 8-bit tensor, the float64 twin of the last step's moment (test diagnostics)
 
     def _init(self, p, st):
         if self.min_8bit_size is None:
@@ -115,6 +117,7 @@ class LionRef:
                 st["step"] += 1
                 bs = blocksize_of(st, p.numel())
                 m = dequant(st["state1"], st["qmap1"], st["absmax1"], bs)
+                self.m64[i] = update(pf.double(), gs.double(), m.double(), K)[1]      # the float64 twin (bnb8_ref.tied_blocks)
                 pn, m, und = update(pf, gs, m, K)
                 c1, a1 = encode(m, st["qmap1"], bs)
                 st["state1"], st["absmax1"] = c1.view(p.shape), a1
@@ -133,7 +136,7 @@ class LionRef:
 SIZES = [1000, 4096, 5000, 300, 9000, 20000, 64, 4100]
 STEPS = 5
 KW = dict(lr=1e-3, betas=(0.9, 0.99), max_norm=1.0, grad_scale=0.5)
-UNDECIDED_CAP = 1e-4          # share of the compared elements per step that may be undecided
+UNDECIDED_CAP = B8_UNDECIDED_CAP          # share of the compared elements per step that may be undecided (1e-4, all three families)
 
 
 def flat_offsets(sizes):
@@ -185,7 +188,8 @@ def run_reference(bs, weight_decay):
             assert gsq * KW["grad_scale"] ** 2 > 1.0                    # the clip is active
             before = snap()
             opt.step([g.clone() for g in grads], gnorm_sq=gsq, max_norm=KW["max_norm"], grad_scale=KW["grad_scale"])
-            recs.append(dict(grads=grads, gsq=gsq, before=before, after=snap(), undecided=[u.clone() for u in opt.undecided]))
+            recs.append(dict(grads=grads, gsq=gsq, before=before, after=snap(), undecided=[u.clone() for u in opt.undecided],
+                             m64=[None if t is None else t.clone() for t in opt.m64]))
         _RUNS[key] = recs
     return _RUNS[key]
 

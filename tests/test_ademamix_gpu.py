@@ -8,8 +8,8 @@ from the fp32 restatement's is recorded beside it.  On exactly representable dat
 grouped launch gives every tensor the bits a one-group launch with its row gives it; a launch repeated gives the same bits; an
 element with a non-finite g' keeps p and its states; canaries around every buffer hold and g is not written.
 8-bit: codes and absmax equal the 8-bit restatement's exactly; were a code to differ, the test counts and prints them and accepts
-only a neighbouring code at a midpoint tie of the fp32 value.  p is held to the same 2x bar, per step, against the fp64 update from
-the same decoded states.
+only a neighbouring code at a midpoint tie of the fp32 value.  p equals the 8-bit restatement's bit for bit, and is held to the
+same 2x bar, per step, against the fp64 update from the same decoded states.
 Every figure is printed before it is judged and dumped as ademamix_parity_gpu.json (kept as profiles/ademamix_parity.json)."""
 import numpy as np
 import pytest
@@ -365,6 +365,7 @@ def test_8bit_codes_absmax_and_parameters_match_the_restatement(bs):
                 assert torch.equal(bits(o["p"]), bits(ref.params[i])), case
                 continue
             last = ref.last[i]
+            assert torch.equal(bits(o["p"]), bits(ref.params[i])), case      # the update reads only the decoded old state: the fp32 restatement's bits
             assert torch.equal(bits(o["absmax1"]), bits(st["absmax1"])), case
             assert torch.equal(bits(o["absmax2"]), bits(st["absmax2"])), case
             blk = torch.arange(SIZES8[i]) // bs

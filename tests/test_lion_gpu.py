@@ -1,7 +1,7 @@
 """GPU: the fused Lion steps (qfx_lion_step, qfx_lion8bit_step) against their CPU restatement (tests/lion_ref.py), their determinism,
 the trainer / checkpoint path with optimizer="lion" / "lion8bit_blockwise", and the torch.optim classes in the stock loop.
 
-The parameter comparison: |p - p_ref| <= 1e-6 max|p_ref| on every element but those where the restatement itself calls the sign of
+The parameter comparison: the restatement's bits on every element but those where the restatement itself calls the sign of
 c = m b1 + (1 - b1) g' undecided (lion_ref.update: the clip coefficient is formed on the host there and on the device here, and a
 last-bit difference in g' can turn a near-cancelled sign, which moves p by 2 lr).  That set is computed from the restatement alone
 and may hold at most lion_ref.UNDECIDED_CAP of the compared elements per step; tests/test_lion_cpu.py checks that the shared inputs
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bnb8_ref as B  # noqa: E402
 import lion_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -25,9 +26,21 @@ SIZES = R.SIZES
 def _check_params(pk, p_ref, und, where):
     """One tensor's parameters against the restatement's outside the undecided set; returns the set's size."""
     assert torch.isfinite(pk).all(), where
-    err = (pk - p_ref).abs() / p_ref.abs().max()
-    assert err[~und].max().item() <= 1e-6, (where, err[~und].max().item())
+    assert B.same_bits(pk[~und], p_ref.reshape(-1)[~und]), (where, "parameters", B.ulp_diff(pk[~und], p_ref.reshape(-1)[~und]))
     return int(und.sum())
+
+
+def _check_state8(got_m32, got_a1, got_codes, st, m64, bs, where):
+    """One tensor's state under the exact rule of bnb8_ref: the fp32 moment or the block maxima bit for bit, every decided code
+    identical, an undecided one within one step.  Returns (codes compared, undecided codes)."""
+    if st["state1"].dtype != torch.uint8:
+        assert B.same_bits(got_m32, st["state1"].reshape(-1)), (where, "fp32 moment")
+        return 0, 0
+    assert B.same_bits(got_a1, st["absmax1"]), (where, "block maxima")
+    k = st["_m"].numel()
+    und, _ = B.undecided_codes(st["_m"], m64, torch.arange(k) // bs, st["absmax1"].numel(), st["qmap1"], True)
+    B.check_codes(got_codes, st["state1"], und, where)
+    return k, int(und.sum())
 
 
 def test_fp32_kernel_matches_restatement():
@@ -155,24 +168,22 @@ def test_8bit_kernel_matches_restatement(bs):
         d.step(rec["grads"], rec["gsq"], 0.01, **R.KW)
         torch.cuda.synchronize()
         p1, s1 = rec["after"]
-        same = tot = n_und = 0
+        tot = n_und = 0
         for i, ((off, k, eight, a0, nb, s0), pt, st) in enumerate(zip(d.lay.tensors, p1, s1)):
             n_und += _check_params(d.p[off:off + k].cpu(), pt, rec["undecided"][i], (it, k))
+            n, u = _check_state8(d.m32[s0:s0 + k].cpu() if not eight else None, d.a1[a0:a0 + nb].cpu() if eight else None,
+                                 d.q1[off:off + k].cpu(), st, rec["m64"][i], bs, (it, k))
+            tot += n; n_und += u
             if not eight:
-                assert torch.allclose(d.m32[s0:s0 + k].cpu(), st["state1"], rtol=1e-6, atol=0), (it, k)
                 continue
-            assert torch.allclose(d.a1[a0:a0 + nb].cpu(), st["absmax1"], rtol=1e-6, atol=0), (it, k)
-            ck, cr = d.q1[off:off + k].cpu().long(), st["state1"].reshape(-1).long()
-            assert (ck - cr).abs().max().item() <= 1, (it, k)            # decoded moments within one code step
-            same += int((ck == cr).sum()); tot += k
+            ck = d.q1[off:off + k].cpu().long()
             z = (st["absmax1"] == 0).repeat_interleave(bs)[:k]
             assert (ck[z] == 127).all()                                  # a zero block stores the code of 0.0
             if i == 4:
                 assert z[:bs].all() and torch.equal(d.p[off:off + bs].cpu(), pt[:bs])       # sgn(0) = 0: only the decay moved them
-        stats.append(same / tot)
-        assert same >= 0.999 * tot, (it, same / tot)
+        stats.append((tot, n_und))
         assert n_und <= R.UNDECIDED_CAP * sum(SIZES), (it, n_und)
-    print(f"lion8bit bs={bs}: identical codes per step {stats}")
+    print(f"lion8bit bs={bs}: per step (codes compared, undecided parameters and codes) {stats}")
 
 
 @pytest.mark.parametrize("bs", [256, 2048])
@@ -191,18 +202,13 @@ def test_8bit_kernel_clip_active_on_short_block_one_block_and_fp32_tensors(bs):
         d.step(grads, gsq, wd, **R.KW)
         opt.step([g.clone() for g in grads], gnorm_sq=gsq, max_norm=R.KW["max_norm"], grad_scale=R.KW["grad_scale"])
         torch.cuda.synchronize()
-        same = tot = n_und = 0
+        tot = n_und = 0
         for i, ((off, k, eight, a0, nb, s0), pt, st) in enumerate(zip(d.lay.tensors, opt.params, opt.state)):
             n_und += _check_params(d.p[off:off + k].cpu(), pt, opt.undecided[i], (it, k))
-            if not eight:
-                assert torch.allclose(d.m32[s0:s0 + k].cpu(), st["state1"], rtol=1e-6, atol=0), (it, k)
-                continue
-            assert torch.allclose(d.a1[a0:a0 + nb].cpu(), st["absmax1"], rtol=1e-6, atol=0), (it, k)
-            ck, cr = d.q1[off:off + k].cpu().long(), st["state1"].reshape(-1).long()
-            assert (ck - cr).abs().max().item() <= 1, (it, k)            # decoded moments within one code step
-            same += int((ck == cr).sum()); tot += k
-        print(f"lion8bit clipped bs={bs} step {it}: {same} of {tot} codes identical, {n_und} undecided")
-        assert same >= 0.999 * tot, (it, same / tot)
+            n, u = _check_state8(d.m32[s0:s0 + k].cpu() if not eight else None, d.a1[a0:a0 + nb].cpu() if eight else None,
+                                 d.q1[off:off + k].cpu(), st, opt.m64[i], bs, (it, k))
+            tot += n; n_und += u
+        print(f"lion8bit clipped bs={bs} step {it}: {tot} codes compared, {n_und} undecided")
         assert n_und <= R.UNDECIDED_CAP * sum(SIZES), (it, n_und)
 
 
