@@ -6,27 +6,22 @@
 //   product   Y = D X (a block owns 64 rows of D) or Z = D^T X (a block owns 64 columns): 64 x 64 tiles of D, formed as
 //             fp32(W1) - fp32(W0) on the way into LDS, times a 64 x k tile of X, fp32 FMA in ascending order of the summed index,
 //             a 4 x 4 register block per lane; the epilogue writes the chunk and its k x k fp64 Gram partial
-//   solve     one workgroup per matrix: the partials folded in chunk order, the cyclic Jacobi solve of qfx_lora_svd.hip (copied:
-//             that file keeps its own so that what it compiles to does not move), T = V L^-1/2 with the kept columns first
+//   solve     one workgroup per matrix: the partials folded in chunk order, the cyclic Jacobi solve that qfx_lora_svd.hip uses
+//             (jacobi of qfx_pair_linalg.h), T = V L^-1/2 with the kept columns first
 //   apply     Y <- fp32(Y T), fp64 sums in index order, in place (the last one writes Q to its place in the flat buffer)
 // Nothing crosses a workgroup but through the ordered partials and the integer skip counter: same inputs -> same bits.
 #include "qfx_common.h"
 
-#include <algorithm>
-#include <utility>
-#include <vector>
-
 #pragma clang fp contract(off)
+
+#include "qfx_pair_linalg.h"                // the Jacobi solve, block_sum and the table check
 
 namespace {
 
-constexpr int NT = 256;                     // four waves
-constexpr int KMAX = 64;                    // widest sketch
-constexpr int DIM_MAX = 1 << 24;            // largest in_features / out_features
+constexpr int KMAX = MAT_N;                 // widest sketch
 constexpr int TS = 64;                      // rows of a row chunk = columns of a column chunk = the tile edge
 constexpr int LDD = TS + 4;                 // row stride of the fp32 tiles in LDS (16-byte rows)
-constexpr int LDM = KMAX + 1;               // row stride of the fp64 matrices of the solve
-constexpr int MSZ = KMAX * LDM;
+constexpr int MSZ = KMAX * LDM;             // one fp64 matrix of the solve
 constexpr int MAX_MATS = 65535;             // grid.y
 constexpr uint32_t OMEGA_TAG = 0x4C524B58u; // counter word 2 of the test matrix ("LRKX")
 
@@ -123,18 +118,6 @@ __global__ __launch_bounds__(NT) void lowrank_omega_kernel(const qfx_lowrank_arg
     const int j = j0 + jj;
     if (j < t.k) w.Z[i * t.k + j] = ((o[j >> 5] >> (j & 31)) & 1u) ? -1.f : 1.f;
   }
-}
-
-__device__ __forceinline__ double block_sum(double loc, double* red, int tid) {
-  red[tid] = loc;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = red[tid] + red[tid + s];
-    __syncthreads();
-  }
-  const double v = red[0];
-  __syncthreads();
-  return v;
 }
 
 // Dl[r][c] = D[row0 + r][col0 + c] for r, c < 64, +0 outside the matrix.  STATS: the lane's sum of squares and finiteness.
@@ -362,100 +345,10 @@ __global__ __launch_bounds__(NT) void lowrank_product_kernel(const qfx_lowrank_a
 struct Small {
   double red[NT];
   double ls[KMAX];                          // the eigenvalues, sorted descending
-  double rc[KMAX / 2], rs[KMAX / 2];        // the rotations of a round
-  int rp[KMAX / 2], rq[KMAX / 2];
+  JacobiRot rot;
   int perm[KMAX];
   int keep;
 };
-
-// max |M_ij| over i < j; a NaN stays once taken  (qfx_lora_svd.hip)
-__device__ __forceinline__ double block_offmax(const double* M, int n, double* red, int tid) {
-  double loc = 0.0;
-  for (int e = tid; e < n * n; e += NT) {
-    const int i = e / n, j = e - i * n;
-    if (i < j) {
-      const double x = fabs(M[i * LDM + j]);
-      if (x > loc || x != x) loc = x;
-    }
-  }
-  red[tid] = loc;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      const double x = red[tid + s], y = red[tid];
-      red[tid] = (x > y || x != x) ? x : y;
-    }
-    __syncthreads();
-  }
-  const double v = red[0];
-  __syncthreads();
-  return v;
-}
-
-// (qfx_lora_svd.hip's jacobi) M [n][LDM] symmetric -> diagonal in place, V = the rotations' product; conv = 1 when
-// max_{i<j} |M_ij| <= 2^-52 ||M0||_F / n was met within `cap` sweeps.  At most cap * (n - 1 | 1) rounds.
-__device__ __forceinline__ int jacobi(double* M, double* V, int n, int cap, Small& sm, int& conv, int tid) {
-  const int m = (n + 1) & ~1, half = m >> 1, mod = m - 1;
-  double loc = 0.0;
-  for (int e = tid; e < n * n; e += NT) {
-    const int i = e / n, j = e - i * n;
-    const double x = M[i * LDM + j];
-    loc = loc + x * x;
-    V[i * LDM + j] = i == j ? 1.0 : 0.0;
-  }
-  const double thr = 0x1p-52 * sqrt(block_sum(loc, sm.red, tid)) / (double)n;
-  int sweeps = 0;
-  conv = 0;
-  for (int s = 0; s <= cap; ++s) {
-    const double off = block_offmax(M, n, sm.red, tid);
-    if (off <= thr) { conv = 1; break; }   // a NaN is never <=
-    if (s == cap) break;
-    for (int rd = 0; rd < mod; ++rd) {
-      if (tid < half) {
-        const int a = tid == 0 ? mod : (rd + tid) % mod, b = tid == 0 ? rd : (rd - tid + mod) % mod;
-        int p = a < b ? a : b;
-        const int q = a < b ? b : a;
-        double c = 1.0, sn = 0.0;
-        if (q < n) {
-          const double apq = M[p * LDM + q];
-          if (fabs(apq) > 0.0) {           // false for a NaN
-            const double tau = (M[q * LDM + q] - M[p * LDM + p]) / (2.0 * apq);
-            const double tt = copysign(1.0, tau) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            c = 1.0 / sqrt(1.0 + tt * tt);
-            sn = tt * c;
-          }
-        } else {
-          p = -1;                          // the padding index of an odd n: nothing to rotate
-        }
-        sm.rp[tid] = p; sm.rq[tid] = q; sm.rc[tid] = c; sm.rs[tid] = sn;
-      }
-      __syncthreads();
-      for (int e = tid; e < half * n; e += NT) {          // M <- M J, V <- V J
-        const int k = e / n, i = e - k * n, p = sm.rp[k], q = sm.rq[k];
-        if (p < 0) continue;
-        const double c = sm.rc[k], sn = sm.rs[k];
-        const double x = M[i * LDM + p], y = M[i * LDM + q];
-        M[i * LDM + p] = c * x - sn * y;
-        M[i * LDM + q] = sn * x + c * y;
-        const double vx = V[i * LDM + p], vy = V[i * LDM + q];
-        V[i * LDM + p] = c * vx - sn * vy;
-        V[i * LDM + q] = sn * vx + c * vy;
-      }
-      __syncthreads();
-      for (int e = tid; e < half * n; e += NT) {          // M <- J^T M; the rotated element itself is set to 0
-        const int k = e / n, j = e - k * n, p = sm.rp[k], q = sm.rq[k];
-        if (p < 0) continue;
-        const double c = sm.rc[k], sn = sm.rs[k];
-        const double x = M[p * LDM + j], y = M[q * LDM + j];
-        M[p * LDM + j] = j == q ? 0.0 : c * x - sn * y;
-        M[q * LDM + j] = j == p ? 0.0 : sn * x + c * y;
-      }
-      __syncthreads();
-    }
-    ++sweeps;
-  }
-  return sweeps;
-}
 
 // side 0: the Gram partials of Y (row chunks of D), side 1: of Z (column chunks).  first: also the skip verdict and normsq.
 __global__ __launch_bounds__(NT) void lowrank_solve_kernel(const qfx_lowrank_args a, int side, int first, int last) {
@@ -509,7 +402,7 @@ __global__ __launch_bounds__(NT) void lowrank_solve_kernel(const qfx_lowrank_arg
   }
   __syncthreads();
   int conv = 0;
-  jacobi(M, V, k, a.max_sweeps, sm, conv, tid);
+  jacobi(M, V, k, a.max_sweeps, sm.rot, sm.red, conv, tid);
   if (tid < k) {                             // descending, ties by index
     const double me = M[tid * LDM + tid];
     int rank = 0;
@@ -582,24 +475,12 @@ __global__ __launch_bounds__(NT) void lowrank_apply_kernel(const qfx_lowrank_arg
   gram_partial(Y2, k, nm, part, tid);
 }
 
-inline bool span_in(int64_t off, int64_t n, int64_t n_elems) { return off >= 0 && n <= n_elems && off <= n_elems - n; }
-
 inline int check_host(const qfx_lowrank_mat* tab, int32_t n_mats, int64_t n_elems) {
-  if (n_mats < 0 || n_elems < 0 || (n_mats > 0 && !tab)) return QFX_EINVAL;
-  std::vector<std::pair<int64_t, int64_t>> spans;
-  spans.reserve(2 * (size_t)n_mats);
-  for (int32_t i = 0; i < n_mats; ++i) {
+  return check_pair_table(n_mats, n_elems, tab != nullptr, KMAX, [&](int32_t i, PairDims& d) {
     const qfx_lowrank_mat& t = tab[i];
-    if (!dims_ok(t)) return QFX_EINVAL;
-    const int64_t na = (int64_t)t.k * t.in_features, nb = (int64_t)t.out_features * t.k;
-    if (!span_in(t.off_a, na, n_elems) || !span_in(t.off_b, nb, n_elems)) return QFX_EINVAL;
-    spans.emplace_back(t.off_a, t.off_a + na);
-    spans.emplace_back(t.off_b, t.off_b + nb);
-  }
-  std::sort(spans.begin(), spans.end());
-  for (size_t i = 1; i < spans.size(); ++i)
-    if (spans[i].first < spans[i - 1].second) return QFX_EINVAL;
-  return QFX_OK;
+    d = {t.off_a, t.off_b, t.k, t.in_features, t.out_features};
+    return dims_ok(t);                       // also the dtype, the pointers and the leading dimensions
+  });
 }
 
 }  // namespace

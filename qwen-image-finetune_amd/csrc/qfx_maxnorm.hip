@@ -15,96 +15,19 @@
 // weights are one fp32 operation each, where tests/maxnorm_ref.py rounds them.
 #include "qfx_common.h"
 
-#include <algorithm>
 #include <cmath>
-#include <utility>
-#include <vector>
 
 #pragma clang fp contract(off)
 
+#include "qfx_pair_linalg.h"                // fill_a, fill_b, gram_tile and the table check
+
 namespace {
 
-constexpr int NT = 256;                     // four waves
 constexpr int RMAX = 128;                   // largest rank
-constexpr int DIM_MAX = 1 << 24;            // largest in_features / out_features
 constexpr int TILE_F = 16384;               // 64 KB: the A / B tile; then the staging area of the fold (16 x 256 fp64 = 32 KB)
 constexpr int NBLK_MAX = 136;               // 16 * 17 / 2 blocks of the upper triangle: r = 64 at T = 4, r = 128 at T = 8
 constexpr int G_ELEMS = NBLK_MAX * 64;      // the full Gram matrix of A, block by block (68 KB of fp64 at T = 8)
 constexpr int SUM_TILE = 1024;
-
-// A tile: element (i, k) of the r x kt slice that starts at column k0 of A [r, ld] -> tile[k * S + i]; rows r..rp-1 are zeros.
-// vec: A and ld are multiples of 16 bytes / 4 elements (k0 and kt then are, too).
-__device__ __forceinline__ void fill_a(float* tile, const float* __restrict__ g, int r, int rp, int S, int64_t ld, int64_t k0, int kt,
-                                       bool vec, int tid) {
-  if (vec) {
-    const unsigned nq = (unsigned)kt >> 2;
-#pragma unroll 4
-    for (unsigned e = tid; e < (unsigned)r * nq; e += NT) {
-      const unsigned i = e / nq, kq = e - i * nq;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(g + (int64_t)i * ld + k0 + 4 * kq);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tile[(4 * kq + j) * S + i] = v[j];
-    }
-    const unsigned np = (unsigned)(rp - r);
-    for (unsigned e = tid; e < (unsigned)kt * np; e += NT) {
-      const unsigned k = e / np;
-      tile[k * S + r + (e - k * np)] = 0.f;
-    }
-  } else {
-#pragma unroll 4
-    for (unsigned e = tid; e < (unsigned)rp * (unsigned)kt; e += NT) {
-      const unsigned i = e / (unsigned)kt, k = e - i * (unsigned)kt;
-      tile[k * S + i] = i < (unsigned)r ? g[(int64_t)i * ld + k0 + k] : 0.f;
-    }
-  }
-}
-
-// B tile: element (i, k) of the kt rows that start at row k0 of B [out, r] -> tile[k * S + i] (the summed index is B's row index:
-// the slice is one contiguous run of kt * r floats).  vec: B is 16-byte aligned and r % 4 == 0 (a quad then lies in one row).
-__device__ __forceinline__ void fill_b(float* tile, const float* __restrict__ g, int r, int rp, int S, int64_t k0, int kt, bool vec,
-                                       int tid) {
-  const float* src = g + k0 * r;
-  if (vec) {
-    const unsigned nq = ((unsigned)kt * (unsigned)r) >> 2;
-#pragma unroll 4
-    for (unsigned q = tid; q < nq; q += NT) {
-      const unsigned k = (4 * q) / (unsigned)r, i = 4 * q - k * (unsigned)r;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tile[k * S + i + j] = v[j];
-    }
-    const unsigned np = (unsigned)(rp - r);
-    for (unsigned e = tid; e < (unsigned)kt * np; e += NT) {
-      const unsigned k = e / np;
-      tile[k * S + r + (e - k * np)] = 0.f;
-    }
-  } else {
-#pragma unroll 4
-    for (unsigned e = tid; e < (unsigned)kt * (unsigned)rp; e += NT) {
-      const unsigned k = e / (unsigned)rp, i = e - k * (unsigned)rp;
-      tile[k * S + i] = i < (unsigned)r ? src[(int64_t)k * r + i] : 0.f;
-    }
-  }
-}
-
-// acc[u][v] += sum over this lane's k of tile[k][i0 + u] * tile[k][j0 + v]
-template <int T>
-__device__ __forceinline__ void gram_tile(const float* tile, int S, int kt, int i0, int j0, int ks, int ksplit, double (&acc)[T * T]) {
-  for (int k = ks; k < kt; k += ksplit) {
-    const float* row = tile + k * S;
-    double a[T], c[T];
-#pragma unroll
-    for (int u = 0; u < T; ++u) {
-      a[u] = (double)row[i0 + u];
-      c[u] = (double)row[j0 + u];
-    }
-#pragma unroll
-    for (int u = 0; u < T; ++u) {
-#pragma unroll
-      for (int v = 0; v < T; ++v) acc[u * T + v] = __builtin_fma(a[u], c[v], acc[u * T + v]);
-    }
-  }
-}
 
 // x[0..n) *= q, one fp32 multiply per element: scalar accesses up to the first 16-byte boundary and behind the last whole quad
 __device__ __forceinline__ void scale_range(float* x, int64_t n, float q, int tid) {
@@ -224,9 +147,7 @@ __global__ __launch_bounds__(NT) void maxnorm_kernel(const qfx_maxnorm_args a) {
   __shared__ float bcast[2];
   const int pi = blockIdx.x;
   const qfx_maxnorm_pair t = a.table[pi];
-  // what qfx_maxnorm_check_table refuses is never touched
-  if (t.r < 1 || t.r > RMAX || t.in_features < 1 || t.in_features > DIM_MAX || t.out_features < 1 || t.out_features > DIM_MAX ||
-      t.off_a < 0 || t.off_b < 0) {
+  if (QFX_PAIR_REFUSED(t, RMAX)) {         // what qfx_maxnorm_check_table refuses is never touched
     if (threadIdx.x == 0) {
       a.norms[pi] = 0.f;
       a.ratios[pi] = 1.f;
@@ -272,23 +193,10 @@ __global__ __launch_bounds__(NT) void maxnorm_summary_kernel(const float* __rest
 }  // namespace
 
 extern "C" int qfx_maxnorm_check_table(const qfx_maxnorm_pair* host_table, int32_t n_pairs, int64_t n_elems) {
-  if (n_pairs < 0 || n_elems < 0 || (n_pairs > 0 && !host_table)) return QFX_EINVAL;
-  std::vector<std::pair<int64_t, int64_t>> spans;
-  spans.reserve(2 * (size_t)n_pairs);
-  for (int32_t i = 0; i < n_pairs; ++i) {
-    const qfx_maxnorm_pair& t = host_table[i];
-    if (t.r < 1 || t.r > RMAX || t.in_features < 1 || t.in_features > DIM_MAX || t.out_features < 1 || t.out_features > DIM_MAX)
-      return QFX_EINVAL;
-    if (!std::isfinite(t.scale)) return QFX_EINVAL;
-    const int64_t na = (int64_t)t.r * t.in_features, nb = (int64_t)t.out_features * t.r;
-    if (t.off_a < 0 || t.off_b < 0 || na > n_elems || nb > n_elems || t.off_a > n_elems - na || t.off_b > n_elems - nb) return QFX_EINVAL;
-    spans.emplace_back(t.off_a, t.off_a + na);
-    spans.emplace_back(t.off_b, t.off_b + nb);
-  }
-  std::sort(spans.begin(), spans.end());
-  for (size_t i = 1; i < spans.size(); ++i)
-    if (spans[i].first < spans[i - 1].second) return QFX_EINVAL;      // two matrices overlap (of one pair or of two)
-  return QFX_OK;
+  return check_pair_table(n_pairs, n_elems, host_table != nullptr, RMAX, [&](int32_t i, PairDims& d) {
+    d = pair_dims(host_table[i]);
+    return std::isfinite(host_table[i].scale);
+  });
 }
 
 extern "C" int qfx_maxnorm_apply(const qfx_maxnorm_args* a, void* stream) {

@@ -20,22 +20,17 @@
 #include "qfx_common.h"
 #include "qfx_optim.h"
 
-#include <algorithm>
 #include <cmath>
-#include <utility>
-#include <vector>
 
 #pragma clang fp contract(off)
 
+#include "qfx_pair_linalg.h"                // the Gram sweep and the table check
+
 namespace {
 
-constexpr int NT = 256;                     // four waves
-constexpr int RMAX = 64;                    // largest rank
-constexpr int DIM_MAX = 1 << 24;            // largest in_features / out_features
+constexpr int RMAX = MAT_N;                 // largest rank
 constexpr int TILE_F = 16384;               // 64 KB: the A / B tile of the Gram sweeps; the staging area of the fold (16 x 256 fp64);
                                             // the two [64][64] fp64 right-hand sides of the solves; the g tile of the second sweep
-constexpr int LDM = RMAX + 1;               // row stride of the two fp64 matrices in LDS
-constexpr int T = 4, TT = T * T;            // block of the Gram matrices' upper triangle a lane owns
 
 struct Hyper { float lr, b1, b2, eps, wd, step, rs2; };
 
@@ -46,126 +41,6 @@ __device__ __forceinline__ void adamw_apply(float& p, float gi, float& m, float&
   const float vi = h.b2 * v + ((1.0f - h.b2) * gi) * gi;
   p = pi - (h.step * mi) / fmaf(h.rs2, sqrtf(vi), h.eps);
   m = mi; v = vi;
-}
-
-// A tile: element (i, k) of the r x kt slice that starts at column k0 of A [r, ld] -> tile[k * S + i]; rows r..rp-1 are zeros.
-// vec: A and ld are multiples of 16 bytes / 4 elements (k0 and kt then are, too).  (qfx_maxnorm.hip's fill_a)
-__device__ __forceinline__ void fill_a(float* tile, const float* __restrict__ g, int r, int rp, int S, int64_t ld, int64_t k0, int kt,
-                                       bool vec, int tid) {
-  if (vec) {
-    const unsigned nq = (unsigned)kt >> 2;
-#pragma unroll 4
-    for (unsigned e = tid; e < (unsigned)r * nq; e += NT) {
-      const unsigned i = e / nq, kq = e - i * nq;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(g + (int64_t)i * ld + k0 + 4 * kq);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tile[(4 * kq + j) * S + i] = v[j];
-    }
-    const unsigned np = (unsigned)(rp - r);
-    for (unsigned e = tid; e < (unsigned)kt * np; e += NT) {
-      const unsigned k = e / np;
-      tile[k * S + r + (e - k * np)] = 0.f;
-    }
-  } else {
-#pragma unroll 4
-    for (unsigned e = tid; e < (unsigned)rp * (unsigned)kt; e += NT) {
-      const unsigned i = e / (unsigned)kt, k = e - i * (unsigned)kt;
-      tile[k * S + i] = i < (unsigned)r ? g[(int64_t)i * ld + k0 + k] : 0.f;
-    }
-  }
-}
-
-// B tile: element (i, k) of the kt rows that start at row k0 of B [out, r] -> tile[k * S + i] (the summed index is B's row index:
-// the slice is one contiguous run of kt * r floats).  vec: B is 16-byte aligned and r % 4 == 0.  (qfx_maxnorm.hip's fill_b)
-__device__ __forceinline__ void fill_b(float* tile, const float* __restrict__ g, int r, int rp, int S, int64_t k0, int kt, bool vec,
-                                       int tid) {
-  const float* src = g + k0 * r;
-  if (vec) {
-    const unsigned nq = ((unsigned)kt * (unsigned)r) >> 2;
-#pragma unroll 4
-    for (unsigned q = tid; q < nq; q += NT) {
-      const unsigned k = (4 * q) / (unsigned)r, i = 4 * q - k * (unsigned)r;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tile[k * S + i + j] = v[j];
-    }
-    const unsigned np = (unsigned)(rp - r);
-    for (unsigned e = tid; e < (unsigned)kt * np; e += NT) {
-      const unsigned k = e / np;
-      tile[k * S + r + (e - k * np)] = 0.f;
-    }
-  } else {
-#pragma unroll 4
-    for (unsigned e = tid; e < (unsigned)kt * (unsigned)rp; e += NT) {
-      const unsigned k = e / (unsigned)rp, i = e - k * (unsigned)rp;
-      tile[k * S + i] = i < (unsigned)r ? src[(int64_t)k * r + i] : 0.f;
-    }
-  }
-}
-
-// acc[u][v] += sum over this lane's k of tile[k][i0 + u] * tile[k][j0 + v]: both factors are widened fp32, the product is exact
-__device__ __forceinline__ void gram_tile(const float* tile, int S, int kt, int i0, int j0, int ks, int ksplit, double (&acc)[TT]) {
-  for (int k = ks; k < kt; k += ksplit) {
-    const float* row = tile + k * S;
-    double a[T], c[T];
-#pragma unroll
-    for (int u = 0; u < T; ++u) {
-      a[u] = (double)row[i0 + u];
-      c[u] = (double)row[j0 + u];
-    }
-#pragma unroll
-    for (int u = 0; u < T; ++u) {
-#pragma unroll
-      for (int v = 0; v < T; ++v) acc[u * T + v] = __builtin_fma(a[u], c[v], acc[u * T + v]);
-    }
-  }
-}
-
-// The Gram matrix of one tensor into M [r][LDM] (both triangles) with reg on the diagonal.  is_a: X = A [r, n], summed over its
-// columns; else X = B [n, r], summed over its rows.
-__device__ __forceinline__ void gram(const float* __restrict__ X, bool is_a, int r, int n, double reg, float* tile, double* M, int tid) {
-  const int nb = (r + T - 1) / T, nblk = nb * (nb + 1) / 2, ksplit = NT / nblk;
-  const int rp = nb * T, S = rp + 1, KT = (TILE_F / S) & ~3;          // S odd; KT >= 252 rows of the tile, a multiple of 4
-  const int blk = tid / ksplit, ks = tid - blk * ksplit;
-  const bool active = blk < nblk;
-  int bi = 0, bj = 0;                                                  // block (bi, bj), bi <= bj, row-major over the upper triangle
-  if (active) {
-    int rem = blk;
-    while (rem >= nb - bi) { rem -= nb - bi; ++bi; }
-    bj = bi + rem;
-  }
-  const bool vec = (((uintptr_t)X & 15) == 0) && ((is_a ? n : r) & 3) == 0;
-  double acc[TT];
-#pragma unroll
-  for (int u = 0; u < TT; ++u) acc[u] = 0.0;
-  for (int64_t k0 = 0; k0 < n; k0 += KT) {
-    const int kt = (int)(n - k0 < KT ? n - k0 : KT);
-    __syncthreads();                       // the previous tile (or whatever the caller kept in it) has been read
-    if (is_a) fill_a(tile, X, r, rp, S, n, k0, kt, vec, tid);
-    else      fill_b(tile, X, r, rp, S, k0, kt, vec, tid);
-    __syncthreads();
-    if (active) gram_tile(tile, S, kt, bi * T, bj * T, ks, ksplit, acc);
-  }
-  // per block and element the partial sums of the residue classes in class order
-  double* stage = reinterpret_cast<double*>(tile);
-  __syncthreads();                         // the tile has been read
-#pragma unroll
-  for (int u = 0; u < TT; ++u) stage[u * NT + tid] = acc[u];
-  __syncthreads();
-  for (int e = tid; e < nblk * TT; e += NT) {
-    const int b = e >> 4, u = e & 15;
-    const double* s = stage + u * NT + b * ksplit;
-    double v = s[0];
-    for (int x = 1; x < ksplit; ++x) v += s[x];
-    int ei = 0, rem = b;
-    while (rem >= nb - ei) { rem -= nb - ei; ++ei; }
-    const int i = ei * T + (u >> 2), j = (ei + rem) * T + (u & 3);
-    if (i < r && j < r) {
-      if (i == j) v += reg;
-      M[i * LDM + j] = v;
-      if (rem != 0) M[j * LDM + i] = v;    // a diagonal block holds both triangles itself (the same products in the same order)
-    }
-  }
 }
 
 // In-place Cholesky factor (lower triangle and diagonal of M) by `nth` lanes, lane lt of them; every lane of the workgroup takes
@@ -320,10 +195,7 @@ __global__ __launch_bounds__(NT) void scaled_adamw_kernel(const qfx_scaled_adamw
   __shared__ double MB[RMAX * LDM];        // G_B, its factor, then P_B
   const int tid = threadIdx.x;
   const qfx_scaled_adamw_pair t = a.table[blockIdx.x];
-  // what qfx_scaled_adamw_check_table refuses is never touched
-  if (t.r < 1 || t.r > RMAX || t.in_features < 1 || t.in_features > DIM_MAX || t.out_features < 1 || t.out_features > DIM_MAX ||
-      t.off_a < 0 || t.off_b < 0)
-    return;
+  if (QFX_PAIR_REFUSED(t, RMAX)) return;   // what qfx_scaled_adamw_check_table refuses is never touched
   const int r = t.r, nin = t.in_features, nout = t.out_features;
   const int64_t na = (int64_t)r * nin, nb = (int64_t)nout * r;
   const float clip = opt_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
@@ -334,8 +206,8 @@ __global__ __launch_bounds__(NT) void scaled_adamw_kernel(const qfx_scaled_adamw
   for (int64_t i = tid; i < nb; i += NT) bad |= !__builtin_isfinite(a.g[t.off_b + i]);
   if (pre) {
     const double reg = (double)a.reg;
-    gram(a.p + t.off_a, true, r, nin, reg, tile, MA, tid);
-    gram(a.p + t.off_b, false, r, nout, reg, tile, MB, tid);
+    gram<TILE_F, true>(a.p + t.off_a, true, r, nin, tile, MA, tid, reg);
+    gram<TILE_F, true>(a.p + t.off_b, false, r, nout, tile, MB, tid, reg);
     bad |= cholesky(tid < NT / 2 ? MA : MB, r, tid & (NT / 2 - 1), NT / 2);
   }
   if (__syncthreads_or(bad)) {             // the same verdict on every lane; nothing of the pair has been written
@@ -366,23 +238,11 @@ inline bool ratio_ok(float x) { return std::isfinite(x) && x >= 0.f; }
 }  // namespace
 
 extern "C" int qfx_scaled_adamw_check_table(const qfx_scaled_adamw_pair* host_table, int32_t n_pairs, int64_t n_elems) {
-  if (n_pairs < 0 || n_elems < 0 || (n_pairs > 0 && !host_table)) return QFX_EINVAL;
-  std::vector<std::pair<int64_t, int64_t>> spans;
-  spans.reserve(2 * (size_t)n_pairs);
-  for (int32_t i = 0; i < n_pairs; ++i) {
+  return check_pair_table(n_pairs, n_elems, host_table != nullptr, RMAX, [&](int32_t i, PairDims& d) {
     const qfx_scaled_adamw_pair& t = host_table[i];
-    if (t.r < 1 || t.r > RMAX || t.in_features < 1 || t.in_features > DIM_MAX || t.out_features < 1 || t.out_features > DIM_MAX)
-      return QFX_EINVAL;
-    if (!ratio_ok(t.lr_ratio_a) || !ratio_ok(t.lr_ratio_b) || !ratio_ok(t.wd_a) || !ratio_ok(t.wd_b)) return QFX_EINVAL;
-    const int64_t na = (int64_t)t.r * t.in_features, nb = (int64_t)t.out_features * t.r;
-    if (t.off_a < 0 || t.off_b < 0 || na > n_elems || nb > n_elems || t.off_a > n_elems - na || t.off_b > n_elems - nb) return QFX_EINVAL;
-    spans.emplace_back(t.off_a, t.off_a + na);
-    spans.emplace_back(t.off_b, t.off_b + nb);
-  }
-  std::sort(spans.begin(), spans.end());
-  for (size_t i = 1; i < spans.size(); ++i)
-    if (spans[i].first < spans[i - 1].second) return QFX_EINVAL;      // two matrices overlap (of one pair or of two)
-  return QFX_OK;
+    d = pair_dims(t);
+    return ratio_ok(t.lr_ratio_a) && ratio_ok(t.lr_ratio_b) && ratio_ok(t.wd_a) && ratio_ok(t.wd_b);
+  });
 }
 
 extern "C" int qfx_scaled_adamw_step(const qfx_scaled_adamw_args* a, void* stream) {

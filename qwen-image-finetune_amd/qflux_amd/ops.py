@@ -3,6 +3,7 @@ These are what the per-kernel parity tests call; the model builds cached argumen
 (plan/qwen.py, plan/flux.py) so that a training step is a flat list of C calls."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -858,35 +859,68 @@ def ema_swap(p, s):
 MAXNORM_MAX_RANK = 128
 
 
-class MaxnormLayout:
-    """Descriptor table of one flat-buffer layout for qfx_maxnorm_apply, built once per layout.  `pairs[i]` = (off_a, off_b, r,
-    in_features, out_features, scale) of adapter pair i; extent: elements p needs."""
+class PairLayout:
+    """Descriptor table of one flat-buffer layout for a per-pair kernel, built once per layout (and, for scaled AdamW, grouping).
+    `pairs[i]` = (off_a, off_b, r, in_features, out_features, ...) of adapter pair i, the rest of the row as its table builder
+    documents it; extent: elements the flat buffers need; host: the ctypes array the device table was made from."""
 
-    def __init__(self, table, pairs, extent):
-        self.table, self.pairs, self.extent = table, pairs, extent
+    def __init__(self, table, pairs, extent, host=None):
+        self.table, self.pairs, self.extent, self.host = table, pairs, extent, host
         self.n_pairs = len(pairs)
+
+
+MaxnormLayout = ScaledAdamwLayout = LoraSvdLayout = PairLayout
+
+
+def _table_tensor(arr, device):
+    """The bytes of a ctypes array as a uint8 tensor, on `device` if one is given."""
+    t = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
+    return t if device is None else t.to(device)
+
+
+# What differs between the descriptor tables: the name in qfx_<what>_check_table and in the messages, the ctypes row, the rank cap,
+# what the check may have refused, and the wording of a rank above the cap and of an empty table.
+_TableSpec = collections.namedtuple("_TableSpec", "what ctype cap refused over none",
+                                    defaults=("pair {i} has rank {r}: ranks above {cap} are not implemented", "pairs"))
+_BuiltTable = collections.namedtuple("_BuiltTable", "table rows extent host")
+
+
+def _pair_table(spec, rows, device, n_elems):
+    """The common part of the descriptor-table builders.  rows: an iterable of (row, ctypes fields) with row = (off_a, off_b, rank,
+    in_features, out_features, ...) already coerced.  A rank above spec.cap is a NotImplementedError; an empty table and a table
+    that qfx_<what>_check_table refuses against n_elems (default: the extent of the rows themselves) are ValueErrors."""
+    kept, structs, extent = [], [], 0
+    for i, (row, fields) in enumerate(rows):
+        if row[2] > spec.cap:
+            raise NotImplementedError(f"{spec.what} table: " + spec.over.format(i=i, r=row[2], cap=spec.cap))
+        kept.append(row)
+        structs.append(spec.ctype(*fields))
+        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
+    if not kept:
+        raise ValueError(f"{spec.what} table: no {spec.none}")
+    arr = (spec.ctype * len(kept))(*structs)
+    if getattr(lib, f"qfx_{spec.what}_check_table")(arr, len(kept), extent if n_elems is None else int(n_elems)) != 0:
+        raise ValueError(f"{spec.what} table: refused by qfx_{spec.what}_check_table ({spec.refused})")
+    return _BuiltTable(_table_tensor(arr, device), kept, extent, arr)
+
+
+def _pair_layout(spec, rows, device, n_elems):
+    b = _pair_table(spec, rows, device, n_elems)
+    return PairLayout(table=b.table, pairs=b.rows, extent=b.extent, host=b.host)
+
+
+_MAXNORM_TABLE = _TableSpec("maxnorm", L.MaxnormPair, MAXNORM_MAX_RANK, refused="a dimension, an offset, an overlap or a scale")
 
 
 def maxnorm_table(pairs, device=None, n_elems=None):
     """pairs: (off_a, off_b, r, in_features, out_features, scale) of every adapter pair in the flat buffer -- A [r, in] at off_a,
     B [out, r] at off_b, scale = lora_alpha / r.  Checked by qfx_maxnorm_check_table against n_elems (default: the extent of the
     pairs themselves) before it goes to the device."""
-    rows, extent = [], 0
-    for i, (off_a, off_b, r, nin, nout, scale) in enumerate(pairs):
-        row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(scale))
-        if row[2] > MAXNORM_MAX_RANK:
-            raise NotImplementedError(f"maxnorm table: pair {i} has rank {row[2]}: ranks above {MAXNORM_MAX_RANK} are not implemented")
-        rows.append(row)
-        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
-    if not rows:
-        raise ValueError("maxnorm table: no pairs")
-    arr = (L.MaxnormPair * len(rows))(*[L.MaxnormPair(*r) for r in rows])
-    if lib.qfx_maxnorm_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
-        raise ValueError("maxnorm table: refused by qfx_maxnorm_check_table (a dimension, an offset, an overlap or a scale)")
-    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
-    if device is not None:
-        table = table.to(device)
-    return MaxnormLayout(table, rows, extent)
+    def rows():
+        for off_a, off_b, r, nin, nout, scale in pairs:
+            row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(scale))
+            yield row, row
+    return _pair_layout(_MAXNORM_TABLE, rows(), device, n_elems)
 
 
 def maxnorm_apply(pflat, table, max_norm, norms, ratios, summary):
@@ -912,35 +946,18 @@ LORA_SVD_MAX_SWEEPS = 30
 LORA_SVD_WS_DOUBLES = 2 * 64 * 64          # per pair: T_B and T_A, [64][64] fp64 each
 
 
-class LoraSvdLayout:
-    """Descriptor table of one flat-buffer layout for qfx_lora_spectrum / qfx_lora_project, built once per layout.  `pairs[i]` =
-    (off_a, off_b, r, in_features, out_features) of adapter pair i; extent: elements p needs; host: the ctypes array."""
-
-    def __init__(self, table, pairs, extent, host):
-        self.table, self.pairs, self.extent, self.host = table, pairs, extent, host
-        self.n_pairs = len(pairs)
+_LORA_SVD_TABLE = _TableSpec("lora_svd", L.LoraSvdPair, LORA_SVD_MAX_RANK, refused="a dimension, an offset or an overlap")
 
 
 def lora_svd_table(pairs, device=None, n_elems=None):
     """pairs: (off_a, off_b, r, in_features, out_features) of every adapter pair in the flat buffer -- A [r, in] at off_a,
     B [out, r] at off_b.  Checked by qfx_lora_svd_check_table against n_elems (default: the extent of the pairs themselves)
     before it goes to the device."""
-    rows, extent = [], 0
-    for i, (off_a, off_b, r, nin, nout) in enumerate(pairs):
-        row = (int(off_a), int(off_b), int(r), int(nin), int(nout))
-        if row[2] > LORA_SVD_MAX_RANK:
-            raise NotImplementedError(f"lora_svd table: pair {i} has rank {row[2]}: ranks above {LORA_SVD_MAX_RANK} are not implemented")
-        rows.append(row)
-        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
-    if not rows:
-        raise ValueError("lora_svd table: no pairs")
-    arr = (L.LoraSvdPair * len(rows))(*[L.LoraSvdPair(*r, 0) for r in rows])
-    if lib.qfx_lora_svd_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
-        raise ValueError("lora_svd table: refused by qfx_lora_svd_check_table (a dimension, an offset or an overlap)")
-    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
-    if device is not None:
-        table = table.to(device)
-    return LoraSvdLayout(table, rows, extent, arr)
+    def rows():
+        for off_a, off_b, r, nin, nout in pairs:
+            row = (int(off_a), int(off_b), int(r), int(nin), int(nout))
+            yield row, row + (0,)
+    return _pair_layout(_LORA_SVD_TABLE, rows(), device, n_elems)
 
 
 def _svd_buf(what, name, t, dtype, n, dev):
@@ -986,10 +1003,7 @@ def lora_project_table(table, dst, device=None, n_elems=None):
     arr = (L.LoraSvdDst * len(rows))(*[L.LoraSvdDst(*r) for r in rows])
     if lib.qfx_lora_project_check_table(table.host, arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
         raise ValueError("lora_project table: refused by qfx_lora_project_check_table (k, r_dst, an offset or an overlap)")
-    t = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
-    if device is not None:
-        t = t.to(device)
-    return t, extent
+    return _table_tensor(arr, device), extent
 
 
 def lora_project(pflat, qflat, table, dst_table, ws):
@@ -1024,38 +1038,33 @@ class LowrankLayout:
         self.n_mats = len(rows)
 
 
+_LOWRANK_TABLE = _TableSpec("lowrank", L.LowrankMat, LOWRANK_MAX_K, refused="a dimension, a leading dimension, an offset or an overlap",
+                            over="matrix {i} asks for k = {r}: sketches wider than {cap} are not implemented", none="matrices")
+
+
 def lowrank_table(mats, device=None, n_elems=None):
     """mats: (W1, W0 or None, k, off_a, off_b[, index]) per matrix -- W1 / W0 2-D device tensors [out, in] with unit column stride,
     both bfloat16 or both float32; Q [out, k] goes to off_b and C [k, in] to off_a of the flat output buffer; index (default: the
     position in the list) keys the test matrix.  Checked by qfx_lowrank_check_table against n_elems (default: the extent of the
     rows themselves) before it goes to the device."""
-    rows, structs, keep, extent = [], [], [], 0
-    for i, mat in enumerate(mats):
-        W1, W0, k, off_a, off_b = mat[:5]
-        index = int(mat[5]) if len(mat) > 5 else i
-        if W1 is None or W1.dim() != 2 or W1.dtype not in _LOWRANK_DTYPES or W1.stride(1) != 1:
-            raise ValueError(f"lowrank table: matrix {i}: W1 must be a 2-D bfloat16 or float32 tensor with unit column stride")
-        if W0 is not None and (W0.shape != W1.shape or W0.dtype != W1.dtype or W0.stride(1) != 1 or W0.device != W1.device):
-            raise ValueError(f"lowrank table: matrix {i}: W0 must match W1 in shape, dtype and device")
-        if int(k) > LOWRANK_MAX_K:
-            raise NotImplementedError(f"lowrank table: matrix {i} asks for k = {k}: sketches wider than {LOWRANK_MAX_K} are not implemented")
-        nout, nin = W1.shape
-        row = (int(off_a), int(off_b), int(k), int(nin), int(nout))
-        rows.append(row)
-        structs.append(L.LowrankMat(_p(W1), _p(W0) if W0 is not None else None, W1.stride(0) if nout > 1 else max(W1.stride(0), nin),
-                                    (W0.stride(0) if nout > 1 else max(W0.stride(0), nin)) if W0 is not None else 0,
-                                    row[0], row[1], row[2], row[3], row[4], _LOWRANK_DTYPES[W1.dtype], index))
-        keep.append((W1, W0))
-        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
-    if not rows:
-        raise ValueError("lowrank table: no matrices")
-    arr = (L.LowrankMat * len(rows))(*structs)
-    if lib.qfx_lowrank_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
-        raise ValueError("lowrank table: refused by qfx_lowrank_check_table (a dimension, a leading dimension, an offset or an overlap)")
-    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
-    if device is not None:
-        table = table.to(device)
-    return LowrankLayout(table, rows, extent, arr, int(lib.qfx_lowrank_sketch_workspace(arr, len(rows))), keep)
+    keep = []
+
+    def described():
+        for i, mat in enumerate(mats):
+            W1, W0, k, off_a, off_b = mat[:5]
+            index = int(mat[5]) if len(mat) > 5 else i
+            if W1 is None or W1.dim() != 2 or W1.dtype not in _LOWRANK_DTYPES or W1.stride(1) != 1:
+                raise ValueError(f"lowrank table: matrix {i}: W1 must be a 2-D bfloat16 or float32 tensor with unit column stride")
+            if W0 is not None and (W0.shape != W1.shape or W0.dtype != W1.dtype or W0.stride(1) != 1 or W0.device != W1.device):
+                raise ValueError(f"lowrank table: matrix {i}: W0 must match W1 in shape, dtype and device")
+            nout, nin = W1.shape
+            row = (int(off_a), int(off_b), int(k), int(nin), int(nout))
+            keep.append((W1, W0))
+            yield row, (_p(W1), _p(W0) if W0 is not None else None, W1.stride(0) if nout > 1 else max(W1.stride(0), nin),
+                        (W0.stride(0) if nout > 1 else max(W0.stride(0), nin)) if W0 is not None else 0,
+                        row[0], row[1], row[2], row[3], row[4], _LOWRANK_DTYPES[W1.dtype], index)
+    b = _pair_table(_LOWRANK_TABLE, described(), device, n_elems)
+    return LowrankLayout(b.table, b.rows, b.extent, b.host, int(lib.qfx_lowrank_sketch_workspace(b.host, len(b.rows))), keep)
 
 
 def lowrank_sketch(table, pflat, normsq, info, skipped, ws, power_iters=2, seed=0, orth_tol=LOWRANK_ORTH_TOL,
@@ -1086,14 +1095,8 @@ def lowrank_sketch(table, pflat, normsq, info, skipped, ws, power_iters=2, seed=
 SCALED_ADAMW_MAX_RANK = 64
 
 
-class ScaledAdamwLayout:
-    """Descriptor table of one flat-buffer layout for qfx_scaled_adamw_step, built once per layout and grouping.  `pairs[i]` =
-    (off_a, off_b, r, in_features, out_features, lr_ratio_a, lr_ratio_b, wd_a, wd_b) of adapter pair i; extent: elements the flat
-    buffers need."""
-
-    def __init__(self, table, pairs, extent):
-        self.table, self.pairs, self.extent = table, pairs, extent
-        self.n_pairs = len(pairs)
+_SCALED_ADAMW_TABLE = _TableSpec("scaled_adamw", L.ScaledAdamwPair, SCALED_ADAMW_MAX_RANK,
+                                 refused="a dimension, an offset, an overlap, an lr ratio or a weight decay")
 
 
 def scaled_adamw_table(pairs, device=None, n_elems=None):
@@ -1101,23 +1104,11 @@ def scaled_adamw_table(pairs, device=None, n_elems=None):
     buffers -- A [r, in] at off_a, B [out, r] at off_b, the tensors' learning rates over the step's lr and their weight decays.
     Checked by qfx_scaled_adamw_check_table against n_elems (default: the extent of the pairs themselves) before it goes to the
     device."""
-    rows, extent = [], 0
-    for i, (off_a, off_b, r, nin, nout, ra, rb, wa, wb) in enumerate(pairs):
-        row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(ra), float(rb), float(wa), float(wb))
-        if row[2] > SCALED_ADAMW_MAX_RANK:
-            raise NotImplementedError(f"scaled_adamw table: pair {i} has rank {row[2]}: ranks above {SCALED_ADAMW_MAX_RANK} are not implemented")
-        rows.append(row)
-        extent = max(extent, row[0] + row[2] * row[3], row[1] + row[4] * row[2])
-    if not rows:
-        raise ValueError("scaled_adamw table: no pairs")
-    arr = (L.ScaledAdamwPair * len(rows))(*[L.ScaledAdamwPair(*r, 0) for r in rows])
-    if lib.qfx_scaled_adamw_check_table(arr, len(rows), extent if n_elems is None else int(n_elems)) != 0:
-        raise ValueError("scaled_adamw table: refused by qfx_scaled_adamw_check_table (a dimension, an offset, an overlap, an lr ratio "
-                         "or a weight decay)")
-    table = torch.frombuffer(bytearray(arr), dtype=torch.uint8)
-    if device is not None:
-        table = table.to(device)
-    return ScaledAdamwLayout(table, rows, extent)
+    def rows():
+        for off_a, off_b, r, nin, nout, ra, rb, wa, wb in pairs:
+            row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(ra), float(rb), float(wa), float(wb))
+            yield row, row + (0,)
+    return _pair_layout(_SCALED_ADAMW_TABLE, rows(), device, n_elems)
 
 
 def scaled_adamw_check(lr, betas, eps, reg=1e-6, precondition=True):
