@@ -61,43 +61,23 @@ __global__ __launch_bounds__(256) void adamx_kernel(float* __restrict__ p, const
   if ((int)threadIdx.x < n_groups) rows[threadIdx.x] = tab.g[threadIdx.x];
   const float clip = opt_clip(gnorm_sq, max_norm, grad_scale);
   __syncthreads();
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    const qfx_adamx_group k = rows[tile_group ? group_index(tile_group, i >> 4, n_groups) : 0];
-    f32x4 pv = *(const f32x4*)(p + 4 * i);
-    const f32x4 gv = *(const f32x4*)(g + 4 * i);
-    f32x4 mv = *(const f32x4*)(m + 4 * i);
-    f32x4 sv = *(const f32x4*)(s + 4 * i);
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t tile, auto w) {
+    constexpr int W = decltype(w)::value;
+    const qfx_adamx_group k = rows[tile_group ? group_index(tile_group, tile, n_groups) : 0];
+    float pv[W], gv[W], mv[W], sv[W];
+    flat_load(p + i, pv); flat_load(g + i, gv); flat_load(m + i, mv); flat_load(s + i, sv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], mj = mv[j], sj = sv[j];
-      adamx_elem<V>(pj, gv[j], mj, sj, clip, k);
-      pv[j] = pj; mv[j] = mj; sv[j] = sj;
-    }
-    *(f32x4*)(p + 4 * i) = pv;
-    *(f32x4*)(m + 4 * i) = mv;
-    *(f32x4*)(s + 4 * i) = sv;
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const qfx_adamx_group k = rows[tile_group ? group_index(tile_group, i >> 6, n_groups) : 0];
-    float pi = p[i], mi = m[i], si = s[i];
-    adamx_elem<V>(pi, g[i], mi, si, clip, k);
-    p[i] = pi; m[i] = mi; s[i] = si;
-  }
+    for (int j = 0; j < W; ++j) adamx_elem<V>(pv[j], gv[j], mv[j], sv[j], clip, k);
+    flat_store(p + i, pv); flat_store(m + i, mv); flat_store(s + i, sv);
+  });
 }
 
 template <int V>
-void adamx_launch(const qfx_adamx_args& a, hipStream_t stream) {
-  const GroupTable<qfx_adamx_group> tab = group_table(a.groups, a.n_groups);
-  const bool vec = (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.exp_avg | (uintptr_t)a.state2) & 15) == 0;
-  const int blocks = flat_grid(vec ? (a.n + 3) / 4 : a.n, FLAT_STEP_CAP);      // adamw_kernel's grid policy
-  if (vec)
-    hipLaunchKernelGGL((adamx_kernel<V, true>), dim3(blocks), dim3(256), 0, stream, a.p, a.g, a.exp_avg, a.state2, a.n, a.tile_group, tab,
-                       a.n_groups, a.gnorm_sq, a.max_norm, a.grad_scale);
-  else
-    hipLaunchKernelGGL((adamx_kernel<V, false>), dim3(blocks), dim3(256), 0, stream, a.p, a.g, a.exp_avg, a.state2, a.n, a.tile_group, tab,
-                       a.n_groups, a.gnorm_sq, a.max_norm, a.grad_scale);
+void adamx_launch(const qfx_adamx_args& a, void* stream) {
+  const FlatShape s = flat_launch_shape(a.n, FLAT_STEP_CAP, a.p, a.g, a.exp_avg, a.state2);      // adamw_kernel's grid policy
+  launch_either<adamx_kernel<V, true>, adamx_kernel<V, false>>(s.vec, s.blocks, stream, a.p, a.g, a.exp_avg, a.state2, a.n, a.tile_group,
+                                                               group_table(a.groups, a.n_groups), a.n_groups, a.gnorm_sq, a.max_norm,
+                                                               a.grad_scale);
 }
 
 }  // namespace
@@ -112,9 +92,9 @@ extern "C" int qfx_adamx_step(const qfx_adamx_args* a, void* stream) {
     if (a->variant == QFX_ADAMX_RADAM && !(q.bias_corr1 > 0.f)) return QFX_EINVAL;
     if (a->variant == QFX_ADAMX_NADAM && !(q.bias_corr2 > 0.f)) return QFX_EINVAL;
   }
-  if (a->variant == QFX_ADAMX_RADAM) adamx_launch<QFX_ADAMX_RADAM>(*a, (hipStream_t)stream);
-  else if (a->variant == QFX_ADAMX_NADAM) adamx_launch<QFX_ADAMX_NADAM>(*a, (hipStream_t)stream);
-  else adamx_launch<QFX_ADAMX_ADAMAX>(*a, (hipStream_t)stream);
+  if (a->variant == QFX_ADAMX_RADAM) adamx_launch<QFX_ADAMX_RADAM>(*a, stream);
+  else if (a->variant == QFX_ADAMX_NADAM) adamx_launch<QFX_ADAMX_NADAM>(*a, stream);
+  else adamx_launch<QFX_ADAMX_ADAMAX>(*a, stream);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

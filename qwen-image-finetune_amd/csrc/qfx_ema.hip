@@ -26,57 +26,36 @@ __device__ __forceinline__ float ema_elem(float s, float p, float omd) {
 // scalar.  NS shadows are updated from the one p held in registers: all loads first, then the arithmetic, then the stores.
 template <bool VEC, int NS>
 __global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ p, int64_t n, EmaConst k) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    const f32x4 pv = *(const f32x4*)(p + 4 * i);
-    f32x4 sv[NS];
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t, auto w) {
+    constexpr int W = decltype(w)::value;
+    float pv[W], sv[NS][W];
+    flat_load(p + i, pv);
 #pragma unroll
-    for (int q = 0; q < NS; ++q) sv[q] = *(const f32x4*)(k.s[q] + 4 * i);
+    for (int q = 0; q < NS; ++q) flat_load(k.s[q] + i, sv[q]);
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sv[q][j] = ema_elem(sv[q][j], pv[j], k.omd[q]);
+      for (int j = 0; j < W; ++j) sv[q][j] = ema_elem(sv[q][j], pv[j], k.omd[q]);
     }
 #pragma unroll
-    for (int q = 0; q < NS; ++q) *(f32x4*)(k.s[q] + 4 * i) = sv[q];
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const float pi = p[i];
-    float si[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) si[q] = k.s[q][i];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) k.s[q][i] = ema_elem(si[q], pi, k.omd[q]);
-  }
+    for (int q = 0; q < NS; ++q) flat_store(k.s[q] + i, sv[q]);
+  });
 }
 
 // the words travel as integers: no float operation sees a NaN payload, a denormal or a signed zero
 template <bool VEC>
 __global__ __launch_bounds__(256) void ema_swap_kernel(uint32_t* __restrict__ p, uint32_t* __restrict__ s, int64_t n) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    const u32x4 pv = *(const u32x4*)(p + 4 * i);
-    const u32x4 sv = *(const u32x4*)(s + 4 * i);
-    *(u32x4*)(p + 4 * i) = sv;
-    *(u32x4*)(s + 4 * i) = pv;
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const uint32_t pi = p[i], si = s[i];
-    p[i] = si;
-    s[i] = pi;
-  }
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t, auto w) {
+    constexpr int W = decltype(w)::value;
+    uint32_t pv[W], sv[W];
+    flat_load(p + i, pv); flat_load(s + i, sv);
+    flat_store(p + i, sv); flat_store(s + i, pv);
+  });
 }
 
-template <bool VEC>
-void ema_update_launch(int blocks, hipStream_t st, const float* p, int64_t n, const EmaConst& k, int ns) {
-  switch (ns) {
-    case 1: hipLaunchKernelGGL((ema_update_kernel<VEC, 1>), dim3(blocks), dim3(256), 0, st, p, n, k); break;
-    case 2: hipLaunchKernelGGL((ema_update_kernel<VEC, 2>), dim3(blocks), dim3(256), 0, st, p, n, k); break;
-    case 3: hipLaunchKernelGGL((ema_update_kernel<VEC, 3>), dim3(blocks), dim3(256), 0, st, p, n, k); break;
-    default: hipLaunchKernelGGL((ema_update_kernel<VEC, 4>), dim3(blocks), dim3(256), 0, st, p, n, k); break;
-  }
+template <int NS>
+void ema_update_launch(const FlatShape& s, void* stream, const float* p, int64_t n, const EmaConst& k) {
+  launch_either<ema_update_kernel<true, NS>, ema_update_kernel<false, NS>>(s.vec, s.blocks, stream, p, n, k);
 }
 
 }  // namespace
@@ -84,7 +63,6 @@ void ema_update_launch(int blocks, hipStream_t st, const float* p, int64_t n, co
 extern "C" int qfx_ema_update(const float* p, int64_t n, const qfx_ema_args* a, void* stream) {
   if (!p || !a || n < 0 || a->n_shadows < 1 || a->n_shadows > QFX_EMA_MAX_SHADOWS) return QFX_EINVAL;
   EmaConst k = {};
-  uintptr_t bits = (uintptr_t)p;
   for (int q = 0; q < a->n_shadows; ++q) {
     if (!a->shadow[q] || a->shadow[q] == p) return QFX_EINVAL;
     if (!(a->one_minus_decay[q] >= 0.f && a->one_minus_decay[q] <= 1.f)) return QFX_EINVAL;      // a NaN fails
@@ -92,14 +70,18 @@ extern "C" int qfx_ema_update(const float* p, int64_t n, const qfx_ema_args* a, 
       if (a->shadow[r] == a->shadow[q]) return QFX_EINVAL;
     k.s[q] = a->shadow[q];
     k.omd[q] = a->one_minus_decay[q];
-    bits |= (uintptr_t)a->shadow[q];
   }
   if (n == 0) return QFX_OK;
-  const bool vec = (bits & 15) == 0;
-  // one 16-byte (or one scalar) access per lane, buffer and pass, at most FLAT_STEP_CAP workgroups, the rest by stride
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
-  if (vec) ema_update_launch<true>(blocks, (hipStream_t)stream, p, n, k, a->n_shadows);
-  else     ema_update_launch<false>(blocks, (hipStream_t)stream, p, n, k, a->n_shadows);
+  // one 16-byte (or one scalar) access per lane, buffer and pass, at most FLAT_STEP_CAP workgroups, the rest by stride; the slots
+  // of k.s behind n_shadows are null
+  static_assert(QFX_EMA_MAX_SHADOWS == 4, "the pointer list below");
+  const FlatShape s = flat_launch_shape(n, FLAT_STEP_CAP, p, k.s[0], k.s[1], k.s[2], k.s[3]);
+  switch (a->n_shadows) {
+    case 1: ema_update_launch<1>(s, stream, p, n, k); break;
+    case 2: ema_update_launch<2>(s, stream, p, n, k); break;
+    case 3: ema_update_launch<3>(s, stream, p, n, k); break;
+    default: ema_update_launch<4>(s, stream, p, n, k); break;
+  }
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }
@@ -107,12 +89,8 @@ extern "C" int qfx_ema_update(const float* p, int64_t n, const qfx_ema_args* a, 
 extern "C" int qfx_ema_swap(float* p, float* s, int64_t n, void* stream) {
   if (!p || !s || p == s || n < 0) return QFX_EINVAL;
   if (n == 0) return QFX_OK;
-  const bool vec = (((uintptr_t)p | (uintptr_t)s) & 15) == 0;
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
-  if (vec)
-    hipLaunchKernelGGL(ema_swap_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)p, (uint32_t*)s, n);
-  else
-    hipLaunchKernelGGL(ema_swap_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)p, (uint32_t*)s, n);
+  const FlatShape sh = flat_launch_shape(n, FLAT_STEP_CAP, p, s);
+  launch_either<ema_swap_kernel<true>, ema_swap_kernel<false>>(sh.vec, sh.blocks, stream, (uint32_t*)p, (uint32_t*)s, n);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

@@ -93,30 +93,15 @@ __global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ 
   }
   const float clip = opt_clip(gnorm_sq, max_norm, grad_scale);
   __syncthreads();
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    const AdamWRow r = rows[group_index(tile_group, i >> 4, n_groups)];
-    f32x4 pv = *(const f32x4*)(p + 4 * i);
-    const f32x4 gv = *(const f32x4*)(g + 4 * i);
-    f32x4 mv = *(const f32x4*)(m + 4 * i);
-    f32x4 vv = *(const f32x4*)(v + 4 * i);
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t tile, auto w) {
+    constexpr int W = decltype(w)::value;
+    const AdamWRow r = rows[group_index(tile_group, tile, n_groups)];
+    float pv[W], gv[W], mv[W], vv[W];
+    flat_load(p + i, pv); flat_load(g + i, gv); flat_load(m + i, mv); flat_load(v + i, vv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], mj = mv[j], vj = vv[j];
-      adamw_elem(pj, gv[j], mj, vj, clip, r.lr, r.b1, r.b2, r.eps, r.wd, r.step, r.rs2);
-      pv[j] = pj; mv[j] = mj; vv[j] = vj;
-    }
-    *(f32x4*)(p + 4 * i) = pv;
-    *(f32x4*)(m + 4 * i) = mv;
-    *(f32x4*)(v + 4 * i) = vv;
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const AdamWRow r = rows[group_index(tile_group, i >> 6, n_groups)];
-    float pi = p[i], mi = m[i], vi = v[i];
-    adamw_elem(pi, g[i], mi, vi, clip, r.lr, r.b1, r.b2, r.eps, r.wd, r.step, r.rs2);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
+    for (int j = 0; j < W; ++j) adamw_elem(pv[j], gv[j], mv[j], vv[j], clip, r.lr, r.b1, r.b2, r.eps, r.wd, r.step, r.rs2);
+    flat_store(p + i, pv); flat_store(m + i, mv); flat_store(v + i, vv);
+  });
 }
 
 // torch.optim.SGD over the flat LoRA buffers after the clip prologue (include/qfx.h).  buf is never touched when mom == 0.
@@ -170,31 +155,17 @@ __global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p,
   }
   const float clip = opt_clip(gnorm_sq, max_norm, grad_scale);
   __syncthreads();
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    const SgdRow r = rows[group_index(tile_group, i >> 4, n_groups)];
-    f32x4 pv = *(const f32x4*)(p + 4 * i);
-    const f32x4 gv = *(const f32x4*)(g + 4 * i);
-    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (r.mom != 0.f && !first) bv = *(const f32x4*)(buf + 4 * i);
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t tile, auto w) {
+    constexpr int W = decltype(w)::value;
+    const SgdRow r = rows[group_index(tile_group, tile, n_groups)];
+    float pv[W], gv[W], bv[W] = {};
+    flat_load(p + i, pv); flat_load(g + i, gv);
+    if (r.mom != 0.f && !first) flat_load(buf + i, bv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], bj = bv[j];
-      sgd_elem(pj, gv[j], bj, clip, r.lr, r.mom, r.keep, r.wd, r.nesterov, first);
-      pv[j] = pj; bv[j] = bj;
-    }
-    if (r.mom != 0.f) *(f32x4*)(buf + 4 * i) = bv;
-    *(f32x4*)(p + 4 * i) = pv;
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    const SgdRow r = rows[group_index(tile_group, i >> 6, n_groups)];
-    float pi = p[i], bi = 0.f;
-    if (r.mom != 0.f && !first) bi = buf[i];
-    sgd_elem(pi, g[i], bi, clip, r.lr, r.mom, r.keep, r.wd, r.nesterov, first);
-    if (r.mom != 0.f) buf[i] = bi;
-    p[i] = pi;
-  }
+    for (int j = 0; j < W; ++j) sgd_elem(pv[j], gv[j], bv[j], clip, r.lr, r.mom, r.keep, r.wd, r.nesterov, first);
+    if (r.mom != 0.f) flat_store(buf + i, bv);
+    flat_store(p + i, pv);
+  });
 }
 
 // ---- Prodigy (prodigyopt 1.x, Adam variant) over the flat LoRA buffers: see include/qfx.h.  Host scalars of the package (Python
@@ -327,15 +298,10 @@ extern "C" int qfx_adamw_step_grouped(float* p, const float* g, float* m, float*
     if (!(q.lr >= 0.f) || !beta_ok(q.beta1) || !beta_ok(q.beta2) || !(q.eps >= 0.f) || !(q.weight_decay >= 0.f)) return QFX_EINVAL;
     if (!(q.bias_corr1 > 0.f) || !(q.bias_corr2 > 0.f)) return QFX_EINVAL;
   }
-  const GroupTable<qfx_adamw_group> tab = group_table(groups, n_groups);
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
-  if (vec)
-    hipLaunchKernelGGL(adamw_grouped_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, tile_group, tab,
-                       n_groups, gnorm_sq, max_norm, grad_scale);
-  else
-    hipLaunchKernelGGL(adamw_grouped_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, tile_group, tab,
-                       n_groups, gnorm_sq, max_norm, grad_scale);
+  const FlatShape s = flat_launch_shape(n, FLAT_STEP_CAP, p, g, m, v);
+  launch_either<adamw_grouped_kernel<true>, adamw_grouped_kernel<false>>(s.vec, s.blocks, stream, p, g, m, v, n, tile_group,
+                                                                         group_table(groups, n_groups), n_groups, gnorm_sq, max_norm,
+                                                                         grad_scale);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }
@@ -350,15 +316,10 @@ extern "C" int qfx_sgd_step_grouped(float* p, const float* g, float* buf, int64_
     if (!buf && q.momentum != 0.f) return QFX_EINVAL;
     if (q.nesterov && (!(q.momentum > 0.f) || q.dampening != 0.f)) return QFX_EINVAL;
   }
-  const GroupTable<qfx_sgd_group> tab = group_table(groups, n_groups);
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0;
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, FLAT_STEP_CAP);
-  if (vec)
-    hipLaunchKernelGGL(sgd_grouped_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, tile_group, tab,
-                       n_groups, first, gnorm_sq, max_norm, grad_scale);
-  else
-    hipLaunchKernelGGL(sgd_grouped_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, tile_group, tab,
-                       n_groups, first, gnorm_sq, max_norm, grad_scale);
+  const FlatShape s = flat_launch_shape(n, FLAT_STEP_CAP, p, g, buf);
+  launch_either<sgd_grouped_kernel<true>, sgd_grouped_kernel<false>>(s.vec, s.blocks, stream, p, g, buf, n, tile_group,
+                                                                     group_table(groups, n_groups), n_groups, first, gnorm_sq, max_norm,
+                                                                     grad_scale);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

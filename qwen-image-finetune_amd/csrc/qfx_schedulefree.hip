@@ -42,42 +42,27 @@ __global__ __launch_bounds__(256) void sfadamw_kernel(float* __restrict__ p, con
                                                       float max_norm, float grad_scale) {
   k.clip = opt_clip(gnorm_sq, max_norm, grad_scale);
   k.first = FIRST;
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    f32x4 pv = *(const f32x4*)(p + 4 * i);
-    const f32x4 gv = *(const f32x4*)(g + 4 * i);
-    f32x4 zv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-    if (!FIRST) { zv = *(const f32x4*)(z + 4 * i); vv = *(const f32x4*)(v + 4 * i); }
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t, auto w) {
+    constexpr int W = decltype(w)::value;
+    float pv[W], gv[W], zv[W] = {}, vv[W] = {};
+    flat_load(p + i, pv); flat_load(g + i, gv);
+    if (!FIRST) { flat_load(z + i, zv); flat_load(v + i, vv); }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], zj = zv[j], vj = vv[j];
-      sf_elem(pj, gv[j], zj, vj, k);
-      pv[j] = pj; zv[j] = zj; vv[j] = vj;
-    }
-    *(f32x4*)(p + 4 * i) = pv;
-    *(f32x4*)(z + 4 * i) = zv;
-    *(f32x4*)(v + 4 * i) = vv;
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) {
-    float pi = p[i], zi = FIRST ? 0.f : z[i], vi = FIRST ? 0.f : v[i];
-    sf_elem(pi, g[i], zi, vi, k);
-    p[i] = pi; z[i] = zi; v[i] = vi;
-  }
+    for (int j = 0; j < W; ++j) sf_elem(pv[j], gv[j], zv[j], vv[j], k);
+    flat_store(p + i, pv); flat_store(z + i, zv); flat_store(v + i, vv);
+  });
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void sf_swap_kernel(float* __restrict__ p, const float* __restrict__ z, int64_t n, float w, float omw) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nv = VEC ? n / 4 : 0;
-  for (int64_t i = tid; i < nv; i += nt) {
-    f32x4 pv = *(const f32x4*)(p + 4 * i);
-    const f32x4 zv = *(const f32x4*)(z + 4 * i);
+  flat_sweep<VEC>(n, [&](int64_t i, int64_t, auto wd) {
+    constexpr int W = decltype(wd)::value;
+    float pv[W], zv[W];
+    flat_load(p + i, pv); flat_load(z + i, zv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) pv[j] = sf_lerp(pv[j], zv[j], w, omw);
-    *(f32x4*)(p + 4 * i) = pv;
-  }
-  for (int64_t i = 4 * nv + tid; i < n; i += nt) p[i] = sf_lerp(p[i], z[i], w, omw);
+    for (int j = 0; j < W; ++j) pv[j] = sf_lerp(pv[j], zv[j], w, omw);
+    flat_store(p + i, pv);
+  });
 }
 
 }  // namespace
@@ -93,27 +78,22 @@ extern "C" int qfx_sfadamw_step(float* p, const float* g, float* z, float* v, in
   k.b2 = beta2; k.omb2 = 1.0f - beta2; k.bc2 = bias_corr2; k.eps = eps; k.wd = weight_decay; k.wdon = weight_decay != 0.f;
   k.w = ckp1; k.omw = 1.0f - ckp1; k.lr = lr_t; k.clip = 1.0f; k.first = 0;
   k.ylr = (float)((double)lr_t * ((double)beta1 * (1.0 - (double)ckp1) - 1.0));
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)z | (uintptr_t)v) & 15) == 0;
   // one 16-byte (or one scalar) access per lane and pass, at most 256 CUs x 8 workgroups, the rest by stride
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, 2048);
-  hipStream_t s = (hipStream_t)stream;
-#define SF_LAUNCH(VEC, FIRST) \
-  hipLaunchKernelGGL((sfadamw_kernel<VEC, FIRST>), dim3(blocks), dim3(256), 0, s, p, g, z, v, n, k, gnorm_sq, max_norm, grad_scale)
-  if (vec) { if (first) SF_LAUNCH(true, true); else SF_LAUNCH(true, false); }
-  else     { if (first) SF_LAUNCH(false, true); else SF_LAUNCH(false, false); }
-#undef SF_LAUNCH
+  const FlatShape s = flat_launch_shape(n, 2048, p, g, z, v);
+  if (first)
+    launch_either<sfadamw_kernel<true, true>, sfadamw_kernel<false, true>>(s.vec, s.blocks, stream, p, g, z, v, n, k, gnorm_sq, max_norm,
+                                                                           grad_scale);
+  else
+    launch_either<sfadamw_kernel<true, false>, sfadamw_kernel<false, false>>(s.vec, s.blocks, stream, p, g, z, v, n, k, gnorm_sq, max_norm,
+                                                                             grad_scale);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }
 
 extern "C" int qfx_sf_swap(float* p, const float* z, int64_t n, float weight, void* stream) {
   if (!p || !z || n <= 0 || !__builtin_isfinite(weight)) return QFX_EINVAL;
-  const bool vec = (((uintptr_t)p | (uintptr_t)z) & 15) == 0;
-  const int blocks = flat_grid(vec ? (n + 3) / 4 : n, 2048);
-  if (vec)
-    hipLaunchKernelGGL(sf_swap_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, z, n, weight, 1.0f - weight);
-  else
-    hipLaunchKernelGGL(sf_swap_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, z, n, weight, 1.0f - weight);
+  const FlatShape s = flat_launch_shape(n, 2048, p, z);
+  launch_either<sf_swap_kernel<true>, sf_swap_kernel<false>>(s.vec, s.blocks, stream, p, z, n, weight, 1.0f - weight);
   QFX_CHECK_LAUNCH();
   return QFX_OK;
 }

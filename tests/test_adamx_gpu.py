@@ -176,6 +176,19 @@ def test_exact_step_gives_torchs_fp32_bits(family, option):
             assert np.array_equal(got[k].astype(F64), x), (family, option, shift, k)
 
 
+@pytest.mark.parametrize("family", list(HP))
+@pytest.mark.parametrize("n", [64 * 4 + 3, 4096 * 1024 + 64 + 3])
+def test_exact_step_with_a_quad_body_a_tail_and_a_second_trip(family, n):
+    """The exact case at a length with a 16-byte body and an n % 4 tail (also one float past a 16-byte boundary: the scalar form), and
+    at one where 4096 workgroups of 256 quads leave a second trip of the stride loop with such a tail behind it: torch's fp32 bits."""
+    p, grads, hp = CPU.exact_case(family, n=n, option=1)
+    want_p, want = CPU.torch_run(family, p.astype(F32), [g.astype(F32) for g in grads], hp, torch.float32)
+    for shift in (0, 1) if n < 1024 else (0,):
+        got = kernel_run(family, p, grads, [hp], "off", shift=shift)
+        for k, w in (("p", want_p), ("exp_avg", want["exp_avg"]), ("second", want[R.SECOND[family]])):
+            assert np.array_equal(got[k].view(np.uint32), np.asarray(w, F32).view(np.uint32)), (family, n, shift, k)
+
+
 # ---------------------------------------------------------------- parameter groups
 def layout(n_tensors):
     """Tensors of odd sizes at multiples of 64, as LoraStore lays them out: [(off, numel)], the padded extent, the pad slots."""

@@ -175,6 +175,21 @@ def test_exact_case_gives_the_fp32_restatements_bits(betas, exact):
                 assert same_bits(got[k], r32[k]), (betas, wd, shift, k)
 
 
+@pytest.mark.parametrize("n", [64 * 4 + 3, 4096 * 1024 + 64 + 3])
+def test_exact_case_with_a_quad_body_a_tail_and_a_second_trip(n):
+    """The all-exact case above at a length with a 16-byte body and an n % 4 tail (also one float past a 16-byte boundary: the scalar
+    form), and at one where 4096 workgroups of 256 quads leave a second trip of the stride loop with such a tail behind it."""
+    rng = np.random.default_rng(12)
+    p = (rng.choice([-1.0, 1.0], n) * 2.0 ** rng.integers(-2, 3, n)).astype(F32)
+    g = (rng.choice([-1.0, 1.0], n) * 2.0 ** rng.integers(-6, 2, n)).astype(F32)
+    hp = dict(lr=2.0 ** -4, betas=(0.5, 0.75, 0.5), eps=0.0, weight_decay=0.5, alpha=2.0, t_alpha=None, t_beta3=None)
+    r64, r32 = refs(p, [g], hp, "off")
+    for shift in (0, 1) if n < 1024 else (0,):
+        got = kernel_run(p, [g], [hp], "off", shift=shift)
+        for k in OUT:
+            assert np.array_equal(r32[k].astype(F64), r64[k]) and same_bits(got[k], r32[k]), (n, shift, k)
+
+
 # ---------------------------------------------------------------- fp32: parameter groups
 def layout64():
     """Tensors of odd sizes at multiples of 64 filling exactly 64 tiles: [(off, numel)], 4096, the pad slots."""

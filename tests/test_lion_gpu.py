@@ -125,6 +125,39 @@ def test_fp32_kernel_clip_active_aligned_and_offset_view():
     assert n_und <= R.UNDECIDED_CAP * sum(SIZES)
 
 
+@pytest.mark.parametrize("n", [64 * 4 + 3, 4096 * 1024 + 64 + 3])
+def test_fp32_kernels_quad_body_tail_and_second_trip(n):
+    """qfx_lion_step and qfx_lion_step_grouped (two rows, alternating 64-element tiles) at a length with a 16-byte body and an n % 4
+    tail, and at one where 4096 workgroups of 256 quads leave a second trip of the stride loop with such a tail behind it; the short
+    length also through views one float in (the scalar instantiation).  No clip: the restatement's bits, as in
+    test_fp32_kernel_unaligned_and_odd_lengths."""
+    from qflux_amd import ops
+    g0 = torch.Generator().manual_seed(9)
+    vals = [torch.randn(n, generator=g0) * s for s in (0.1, 1.0, 0.01)]
+    rows = [(1e-3, 0.9, 0.99, 0.01), (1.6e-2, 0.95, 0.98, 0.0)]
+    refs = [R.update(vals[0], vals[1], vals[2], R.step_scalars(*r)) for r in rows]
+    tg = (torch.arange((n + 63) // 64) % 2).to(torch.uint8)
+    sel = tg.repeat_interleave(64)[:n].bool()
+    pr, mr, und = (torch.where(sel, refs[1][i], refs[0][i]) for i in range(3))
+    assert int(und.sum()) + int(refs[0][2].sum()) <= R.UNDECIDED_CAP * 2 * n
+    for shift in (0, 1) if n < 1024 else (0,):
+        for grouped in (False, True):
+            bufs = [torch.zeros(n + 8, device=DEV) for _ in range(3)]
+            p, g, m = (b[shift:shift + n] for b in bufs)
+            for t, v in zip((p, g, m), vals):
+                t.copy_(v.to(DEV))
+            if grouped:
+                ops.lion_step_grouped(p, g, m, tg.to(DEV), rows)
+            else:
+                ops.lion_step(p, g, m, *rows[0])
+            torch.cuda.synchronize()
+            wp, wm, wu = (pr, mr, und) if grouped else refs[0]
+            pk, mk = p.cpu(), m.cpu()
+            assert torch.equal(mk, wm) and torch.equal(pk[~wu], wp[~wu]), (n, shift, grouped)
+            assert torch.equal(g.cpu(), vals[1])
+            assert not bufs[0][shift + n:].any() and not bufs[2][shift + n:].any() and not bufs[0][:shift].any()      # nothing past the end
+
+
 class _Dev8:
     """The device buffers of the 8-bit step, loaded from / compared with the restatement's state."""
 

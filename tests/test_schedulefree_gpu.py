@@ -93,6 +93,29 @@ def test_clip_active_at_every_step_aligned_and_offset_view():
             assert torch.equal(runs[0][it][i], runs[1][it][i]), (it, name)
 
 
+def test_second_trip_of_the_16_byte_form_in_the_step_and_the_swap():
+    """n = 2048 workgroups x 256 quads + 64 + 3: the stride loop of the 16-byte form runs a second time, with an n % 4 tail behind it,
+    in the first step (z and v written only), a later one and the swap to the averaged point."""
+    from qflux_amd import ops
+    n = 2048 * 1024 + 64 + 3
+    y, grads, gsq, r64, r32 = _ref(n, 2)
+    got, bufs = _kernel_run(y, grads, gsq, KW)
+    for it in range(2):
+        for i, name in enumerate(("y", "z", "v")):
+            R.check(name, got[it][i], r32[it][i], r64[it][i], f"n={n} step {it}")
+            R.check(name, got[it][i][-131:], r32[it][i][-131:], r64[it][i][-131:], f"n={n} step {it}, second trip")
+    for b in bufs:
+        assert bool((b[n:] == GUARD).all())
+    yk, zk = got[1][0], got[1][1]
+    p, zd = yk.to(DEV), zk.to(DEV)
+    we = 1 - 1 / KW["betas"][0]
+    ops.sf_swap(p, zd, KW["betas"][0], to_eval=True)
+    x64, x32 = torch.lerp(yk.double(), zk.double(), we), torch.lerp(yk, zk, we)
+    R.check("x", p.cpu(), x32, x64, f"eval n={n}")
+    R.check("x", p.cpu()[-131:], x32[-131:], x64[-131:], f"eval n={n}, second trip")
+    assert torch.equal(zd.cpu(), zk) and not torch.equal(p.cpu()[-131:], yk[-131:])
+
+
 @pytest.mark.parametrize("beta1", [0.9, 0.4])
 def test_swap_matches_torch_lerp_and_round_trips(beta1):
     """beta1 = 0.9: weights -0.111.. and 0.1, the |w| < 0.5 branch; beta1 = 0.4: -1.5 and 0.6, the other one."""
