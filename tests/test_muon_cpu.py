@@ -4,8 +4,15 @@ ctypes layout and host-side refusals of qfx_muon_step, and the packed-VALU scan 
 
 Restatement against torch: the momentum buffer bit for bit; with ns_steps = 0 (normalisation only) O and p bit for bit; with the
 iteration, torch's bf16 GEMM and the restatement's fp32 matmul may sum in different orders, so each is measured against the float64
-iteration from the same normalised input and the restatement's error may be at most twice torch's (the rule the kernel is held to)."""
+iteration from the same normalised input and the restatement's error may be at most twice torch's (the rule the kernel is held to).
+
+The stage tests of tests/test_muon_gpu.py, without a GPU: the sign designs normalise to {0, +-2^-j}, every product they reach is
+exact in fp32 in any order (R.exact_ok), two accumulation orders give the same bits, three kernel faults (R.MUTANTS) change them;
+the Gaussian cases keep their norm off the bf16 rounding boundaries; the five-iteration bar lets the chunk-dropping fault through;
+and the bars of the one-iteration Gaussian test (profiles/muon_stage_parity.json; QFX_WRITE_MUON_STAGE_PARITY=1 rewrites them)."""
 import ctypes as C
+import json
+import math
 import os
 import subprocess
 import sys
@@ -14,6 +21,7 @@ import pytest
 import torch
 
 import muon_ref as R
+import test_muon_gpu as TG              # its shapes, Gaussian cases and design table; importing it needs no GPU
 from test_sgd_cpu import toy_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -274,3 +282,120 @@ def test_no_packed_fp32_valu_consumes_an_mfma_result_in_the_muon_kernel(tmp_path
         asm = f.read()
     assert "v_mfma_f32_16x16x32_bf16" in asm and "scratch_" not in asm
     assert not pk_mfma_scan.scan(dst)
+
+
+# ---- the stage-level GPU tests of tests/test_muon_gpu.py: their designs, their margins and their sensitivity, without a GPU -------
+STAGE_PROFILE = os.path.join(ROOT, "profiles", "muon_stage_parity.json")
+SEES = {"gram_chunk": ("gram", "gg"), "g_element": ("gram", "gg"), "hx_strip": ("gram", "gg")}   # H = G under "gram": H X is formed there too
+
+
+def _share(a, b):
+    return float((R.bf16_ulps(a, b) > 0).float().mean())
+
+
+def test_sign_designs_are_exact_under_every_probe_and_every_mutant_shows():
+    for i, shape in enumerate(TG.SHAPES):
+        nz = TG.DESIGN_NONZEROS.get(shape)
+        m = R.sign_design(shape, TG.DESIGN_SEED + i, nz)
+        j = R.max_design_j(shape) - (0 if nz is None else 1)
+        assert int((m != 0).sum()) == 4 ** j and set(m.unique().tolist()) <= {-1.0, 0.0, 1.0}
+        assert bool((m != 0).any(0).all()) and bool((m != 0).any(1).all())
+        x0 = R.normalise(m, 1e-7)
+        assert tuple(x0.shape) == (min(shape), max(shape)) and set(x0.float().abs().unique().tolist()) <= {0.0, 2.0 ** -j}
+        assert torch.equal(x0.float(), R.short_image(m) * 2.0 ** -j)
+        for name, coeffs in R.PROBES.items():
+            x1, ok = R.probe_exact(x0, coeffs)
+            assert all(ok.values()), (shape, name, ok)
+            assert torch.equal(x1, R.ns_bf16(x0, coeffs, 1)), (shape, name)                     # an fp32 order against the fp64 one
+            assert torch.equal(x1, R.ns_bf16(x0.flip(1).contiguous(), coeffs, 1).flip(1)), (shape, name)   # and the reversed order
+            shares = {k: _share(f(x0, coeffs, 1), x1) for k, f in R.MUTANTS.items()}
+            print(f"MUON_STAGE design shape={shape} nonzeros=4^{j} probe={name} exact_ok={ok} mutant_share={shares}")
+            for k, probes in SEES.items():
+                assert (shares[k] > 0) == (name in probes), (shape, name, k, shares[k])
+            if name.startswith("ax"):
+                assert torch.equal(x1.float(), x0.float() * coeffs[0])
+    # why (96, 3072) takes the sparser design: with 4^9 non-zeros bf16(G G) X is past the 24 bits
+    dense = R.normalise(R.sign_design((96, 3072), TG.DESIGN_SEED + TG.SHAPES.index((96, 3072))), 1e-7)
+    assert not R.probe_exact(dense, R.PROBES["gg"])[1]["hx0"] and all(R.probe_exact(dense, R.PROBES["gram"])[1].values())
+
+
+def test_two_step_gram_designs_keep_the_second_iteration_exact():
+    """The second iteration of the "gram" probe: G G is multiplied by c = 0 and H = G, so X X^T and H X of both iterations decide."""
+    for shape, nz in TG.TWO_STEP_NONZEROS.items():
+        x0 = R.normalise(R.sign_design(shape, TG.TWO_STEP_SEED + TG.SHAPES.index(shape), nz), 1e-7)
+        x2, ok = R.ns_staged(x0, R.PROBES["gram"], 2)
+        rel = {k: v for k, v in ok.items() if not k.startswith("gg")}
+        print(f"MUON_STAGE two_step shape={shape} nonzeros={nz} exact_ok={rel}")
+        assert len(rel) == 4 and all(rel.values()), (shape, rel)
+        assert torch.equal(x2, R.ns_bf16(x0, R.PROBES["gram"], 2)) and torch.equal(x2, R.ns_bf16(x0.flip(1).contiguous(), R.PROBES["gram"], 2).flip(1))
+        assert not torch.equal(x2, R.MUTANTS["gram_chunk"](x0, R.PROBES["gram"], 2)) and bool(x2.any())
+    assert {(16, 64), (64, 16)} <= set(TG.TWO_STEP_NONZEROS)
+
+
+def test_gaussian_cases_keep_their_norm_off_the_bf16_rounding_boundaries():
+    """The margin TG.test_normalisation_alone_is_bit_exact needs (derived there), for the seeds of TG.cases(); and the restatement's
+    own fp32 sum of squares lands on the side of the float64 norm."""
+    for c in TG.stage_cases():
+        margin, nrm = R.norm_margin(c["u"])
+        print(f"MUON_STAGE norm shape={c['shape']} norm={nrm:.8e} margin=2^{math.log2(margin):.2f} needed=2^{math.log2(TG.NORM_MARGIN):.0f}")
+        assert margin >= TG.NORM_MARGIN, (c["shape"], margin)
+        xf = R.short_image(c["u"].to(R.BF)).float()
+        assert torch.equal(c["x0"], (xf / torch.tensor(nrm, dtype=torch.float64).to(R.BF).float()).to(R.BF)), c["shape"]
+
+
+def test_five_step_bar_lets_the_chunk_dropping_mutant_through_at_the_large_shapes():
+    """What the stage tests are for: e_kernel <= 2 e_torch after five iterations does not see a Gram product without its last chunk."""
+    cs = {c["shape"]: c for c in TG.stage_cases()}
+    for shape in ((96, 3072), (16, 3104), (32, 1568)):
+        c = cs[shape]
+        e_t = R.rel_err(c["o_t"], c["o64"])
+        for k, f in R.MUTANTS.items():
+            e_m = R.rel_err(R.untranspose(f(c["x0"], R.COEFFS, 5), shape), c["o64"])
+            print(f"MUON_STAGE old_bar shape={shape} mutant={k} e_mutant/e_torch={e_m / e_t:.3f} passes_old_bar={e_m <= 2 * e_t}")
+            if k == "gram_chunk":
+                assert e_m <= 2 * e_t, (shape, e_m, e_t)
+
+
+def _one_step_reference_noise():
+    """Per Gaussian case: two accumulation orders of the reference (torch's fp32 matmul, float64 rounded to fp32) after ONE iteration
+    with the default coefficients -- the share of elements that differ, the largest difference in bf16 steps, the bar the kernel is
+    held to against the float64 order, and each mutant's share over that bar."""
+    ref, bar, sens = {}, {}, {}
+    for c in TG.stage_cases():
+        key = "%dx%d" % c["shape"]
+        d = R.bf16_ulps(R.ns_bf16(c["x0"], R.COEFFS, 1), c["x1"])
+        n = d.numel()
+        ref[key] = {"elements": n, "differing": int((d > 0).sum()), "s_ref": float((d > 0).sum()) / n, "u_ref": int(d.max())}
+        bar[key] = {"share": max(8.0 * ref[key]["s_ref"], 4.0 / n), "ulps": max(ref[key]["u_ref"], 1)}
+        sens[key] = {k: _share(f(c["x0"], R.COEFFS, 1), c["x1"]) / bar[key]["share"] for k, f in R.MUTANTS.items()}
+    return ref, bar, sens
+
+
+def test_one_step_bars_of_the_gpu_test_come_from_the_references_own_noise():
+    ref, bar, sens = _one_step_reference_noise()
+    if os.environ.get("QFX_WRITE_MUON_STAGE_PARITY") == "1":
+        doc = {}
+        if os.path.exists(STAGE_PROFILE):
+            with open(STAGE_PROFILE) as f:
+                doc = json.load(f)
+        doc.update({"rule": "one Newton-Schulz iteration, default coefficients, Gaussian cases of tests/test_muon_gpu.py: s_ref = share of "
+                            "elements on which two accumulation orders of the reference differ (torch's fp32 matmul against float64 "
+                            "rounded to fp32 where the kernel holds fp32), u_ref = their largest difference in bf16 steps; the kernel "
+                            "against the float64 order: differing share <= max(8 s_ref, 4 elements' worth), no element off by more "
+                            "than max(u_ref, 1) bf16 steps; mutant_share_over_bar: the three faults of tests/muon_ref.py MUTANTS, "
+                            "each must exceed the bar at least four times over",
+                    "reference": ref, "bar": bar, "mutant_share_over_bar": sens})
+        with open(STAGE_PROFILE, "w") as f:
+            json.dump(doc, f, indent=1)
+    with open(STAGE_PROFILE) as f:
+        committed = json.load(f)
+    assert set(committed["bar"]) == set(bar) == {"%dx%d" % s for s in TG.SHAPES}
+    for key in bar:
+        b, r = committed["bar"][key], committed["reference"][key]
+        print(f"MUON_STAGE one_step shape={key} now={ref[key]} committed_bar={b} mutant_share_over_committed_bar="
+              f"{ {k: round(v * bar[key]['share'] / b['share'], 1) for k, v in sens[key].items()} }")
+        assert b["share"] == max(8.0 * r["s_ref"], 4.0 / r["elements"]) and b["ulps"] == max(r["u_ref"], 1) and r["elements"] == ref[key]["elements"]
+        # this machine's two orders would themselves pass the committed bar, and every fault misses it four times over
+        assert ref[key]["s_ref"] <= b["share"] and ref[key]["u_ref"] <= b["ulps"], (key, ref[key], b)
+        for k, v in sens[key].items():
+            assert v * bar[key]["share"] >= 4.0 * b["share"], (key, k, v)

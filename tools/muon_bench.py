@@ -9,7 +9,10 @@ There is no pass / fail time: Muon is five iterations of three small matrix prod
 Writes the record to --out (default muon_bench.json; meant for profiles/muon_bench.json).
 
 --parity LOG: instead of timing, collect the MUON_PARITY lines that `pytest -s tests/test_muon_gpu.py` prints (the measured errors of
-torch.optim.Muon, the restatement and the kernel against the float64 iteration) into --out (meant for profiles/muon_parity.json)."""
+torch.optim.Muon, the restatement and the kernel against the float64 iteration) into --out (meant for profiles/muon_parity.json).
+
+--stage-measured FILE: merge the kernel's one-iteration shares that tests/test_muon_gpu.py wrote with QFX_MUON_STAGE_MEASURED_OUT=FILE
+into --out (meant for profiles/muon_stage_parity.json, whose bars tests/test_muon_cpu.py writes) under kernel_measured."""
 import argparse
 import json
 import os
@@ -43,6 +46,19 @@ def parity(log, out):
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)
     print(json.dumps({k: rec[k] for k in ("worst_ratio_e_kernel_over_e_torch", "worst_buf_ulp")}), len(rec["records"]), "records")
+
+
+def stage_measured(measured, out):
+    with open(out) as f:
+        doc = json.load(f)
+    with open(measured) as f:
+        doc["kernel_measured"] = json.load(f)
+    assert set(doc["kernel_measured"]) == set(doc["bar"]), "the measured file and the bars name other shapes"
+    doc["kernel_note"] = ("qfx_muon_step on one MI355X against the float64-accumulated iteration, "
+                          "tests/test_muon_gpu.py (QFX_MUON_STAGE_MEASURED_OUT)")
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print(json.dumps({k: v["differing"] for k, v in doc["kernel_measured"].items()}))
 
 
 def torch_muon_launches(shapes):
@@ -139,8 +155,11 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parity", default=None, metavar="LOG", help="collect MUON_PARITY lines of a pytest -s log instead of timing")
+    ap.add_argument("--stage-measured", default=None, metavar="FILE", help="merge the one-iteration shares the GPU test wrote into --out")
     a = ap.parse_args()
     if a.parity:
         parity(a.parity, a.out or "muon_parity.json")
+    elif a.stage_measured:
+        stage_measured(a.stage_measured, a.out or "muon_stage_parity.json")
     else:
         main(a.out or "muon_bench.json", a.rounds, a.iters)
