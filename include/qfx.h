@@ -1432,6 +1432,53 @@ int qfx_lowrank_check_table(const qfx_lowrank_mat* host_table, int32_t n_mats, i
 int64_t qfx_lowrank_sketch_workspace(const qfx_lowrank_mat* host_table, int32_t n_mats);
 int qfx_lowrank_sketch(const qfx_lowrank_args* a, void* stream);
 
+/* ---- W <- W + c B A over every dense matrix of a device table, in place (csrc/qfx_lora_fold.hip): the residual trunk of a PiSSA
+ * initialisation (Meng et al. 2024; c = -lora_alpha / r) in one pass over the trunk, with bits that do not depend on a BLAS
+ * library.  Appended under ABI 7: new structs and entry points only.  THIS LISTING IS THE SPECIFICATION (tests/pissa_ref.py
+ * restates it in numpy).  For row m of the table: W [out, in] row-major with leading dimension ld, bf16 (dtype 0) or fp32
+ * (dtype 1); A [r, in] and B [out, r] row-major fp32 at off_a / off_b of the flat buffer p, 1 <= r <= 64, 1 <= in, out <= 2^24;
+ * c the row's fp32 coefficient.  For every o < out, i < in:
+ *   s       = sum_{j<r} fp64(B[o,j]) fp64(A[j,i])     ascending j from +0; every product is exact in fp64, one rounding per
+ *                                                     addition (an fp64 FMA gives the same bits; the kernel uses it)
+ *   t       = fp64(c) s                               one rounding
+ *   w'      = fp64(W[o,i]) + t                        one rounding
+ *   W[o,i]  = fp32(w') (nearest even), and for a bf16 W that fp32 value rounded to bf16 (nearest even)
+ * Every element is read and written by the same lane; no atomics, nothing crosses a workgroup: same inputs -> same bits at any
+ * address and in any table order.  Columns in <= i < ld are never touched.  There is no skip rule: non-finite values propagate by
+ * IEEE arithmetic into the elements they reach.  A and B are only read; several rows may name the same ones.
+ * qfx_lora_fold enqueues a one-workgroup launch that writes tile_start [n_mats + 1] (the 64 x 64 tiles of the rows before each
+ * row, int64) from the device table, and ONE launch over the flat grid of (tile, matrix), sized from host_table by the same count
+ * (host_table is read at enqueue time only; no host synchronisation, no host -> device copy: it can sit in a captured graph).
+ * The tile's B [64, r] and A [r, 64] are staged in LDS as fp32; 16-byte loads and stores of W where W is 16-byte aligned and
+ * ld % 8 == 0 (bf16) resp. ld % 4 == 0 (fp32), scalar ones otherwise; tile edges are handled in the kernel.
+ * qfx_lora_fold_check_table runs on a HOST copy of the table: QFX_EINVAL for n_mats outside 0..65535, n_elems < 0, a NULL table
+ * with n_mats > 0, r outside 1..64, in or out outside 1..2^24, ld < in, a dtype other than 0 or 1, a NULL W, a negative offset,
+ * A or B reaching past n_elems, two W of the table whose extents [W, W + (out - 1) ld + in) overlap, more than 2^24 - 1 tiles
+ * in all (the flat grid of 256-lane workgroups stays below 2^32 lanes; 420 matrices of 12288 x 3072 are 3.9 million).
+ * qfx_lora_fold rejects with QFX_EINVAL before any launch: a NULL args, n_mats outside 0..65535, with n_mats > 0 a NULL table,
+ * host_table, p or tile_start, and whatever qfx_lora_fold_check_table refuses of host_table against n_elems.  n_mats == 0
+ * returns QFX_OK without a launch. ---- */
+typedef struct qfx_lora_fold_mat {        /* 64 bytes */
+  void* w;                                /* [out, in], device; read and written */
+  int64_t ld;                             /* elements */
+  int64_t off_a, off_b;                   /* first element of A [r, in] / B [out, r] in p */
+  int32_t r, in_features, out_features;
+  int32_t dtype;                          /* 0: bf16, 1: fp32 */
+  float   c;
+  int32_t reserved[3];
+} qfx_lora_fold_mat;
+typedef struct qfx_lora_fold_args {
+  const qfx_lora_fold_mat* table;         /* device array */
+  const qfx_lora_fold_mat* host_table;    /* the same rows on the host */
+  int32_t n_mats;
+  int32_t reserved;
+  const float* p;                         /* flat fp32 buffer that holds every A and B, read */
+  int64_t n_elems;                        /* its extent */
+  int64_t* tile_start;                    /* device, [n_mats + 1], written */
+} qfx_lora_fold_args;
+int qfx_lora_fold_check_table(const qfx_lora_fold_mat* host_table, int32_t n_mats, int64_t n_elems);
+int qfx_lora_fold(const qfx_lora_fold_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,6 +303,16 @@ class LowrankArgs(C.Structure):
                 ("ws_bytes", C.c_int64)]
 
 
+class LoraFoldMat(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("ld", C.c_int64), ("off_a", C.c_int64), ("off_b", C.c_int64), ("r", C.c_int32),
+                ("in_features", C.c_int32), ("out_features", C.c_int32), ("dtype", C.c_int32), ("c", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class LoraFoldArgs(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("host_table", C.c_void_p), ("n_mats", C.c_int32), ("reserved", C.c_int32), ("p", C.c_void_p),
+                ("n_elems", C.c_int64), ("tile_start", C.c_void_p)]
+
+
 class StatsEntry(C.Structure):
     _fields_ = [("off", C.c_int64), ("numel", C.c_int32), ("pad", C.c_int32)]
 
@@ -450,6 +460,8 @@ SYMBOLS = {
     "qfx_lowrank_check_table": (C.c_int, [C.POINTER(LowrankMat), _i32, _i64]),
     "qfx_lowrank_sketch_workspace": (_i64, [C.POINTER(LowrankMat), _i32]),
     "qfx_lowrank_sketch": (C.c_int, [C.POINTER(LowrankArgs), _vp]),
+    "qfx_lora_fold_check_table": (C.c_int, [C.POINTER(LoraFoldMat), _i32, _i64]),
+    "qfx_lora_fold": (C.c_int, [C.POINTER(LoraFoldArgs), _vp]),
     "qfx_adapter_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _f, _f, _vp]),
     "qfx_lora_dropout_apply": (C.c_int, [C.POINTER(LoraDropoutArgs), _i32, _vp, _vp]),
     "qfx_lora_dropout_advance": (C.c_int, [_vp, _vp]),

@@ -6,7 +6,8 @@ of skinny passes over each difference, k = rank + oversample columns wide, with 
 Q [out, k], C [k, in] in one flat buffer -- exactly the (B, A) form resize.resize_pairs consumes -- and the spectrum, select_rank
 and the projection to the final rank are the two launches of the rank resize.  No dense SVD and no [out, in] temporary.  kohya's
 script is not a dependency and was not at hand: the semantics are restated (tests/lora_extract_ref.py); its --clamp_quantile is
-left out on purpose, as are conv layers, PiSSA / OLoRA initialisation, merging several LoRAs by SVD and ranks above 64.
+left out on purpose, as are conv layers, OLoRA / LoftQ initialisation, merging several LoRAs by SVD and ranks above 64 (PiSSA
+initialisation builds on the same sketch: qflux_amd.pissa).
 """
 from __future__ import annotations
 
@@ -30,16 +31,16 @@ def _align(n, a=64):
 
 
 @torch.no_grad()
-def _sketch(mats, k, power_iters, seed):
+def _sketch(mats, k, power_iters, seed, index0=0):
     """The device part: qfx_lowrank_sketch over mats = [(name, W1, W0 or None)] -> (pflat, pairs as resize_pairs takes them with
-    scaling 1, normsq [n] fp64 and info [n, 2] int32 on the host, skipped)."""
+    scaling 1, normsq [n] fp64 and info [n, 2] int32 on the host, skipped).  index0 + the position in mats keys the test matrix."""
     dev = mats[0][1].device
     rows, pairs, off = [], [], 0
-    for name, W1, W0 in mats:
+    for i, (name, W1, W0) in enumerate(mats):
         nout, nin = W1.shape
         oa, ob = off, off + _align(k * nin)
         off = ob + _align(nout * k)
-        rows.append((W1, W0, k, oa, ob))
+        rows.append((W1, W0, k, oa, ob, index0 + i))
         pairs.append((name, oa, ob, k, int(nin), int(nout), 1.0))
     table = ops.lowrank_table(rows, device=dev, n_elems=off)
     pflat = torch.zeros(off, dtype=torch.float32, device=dev)

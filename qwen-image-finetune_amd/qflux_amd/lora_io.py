@@ -72,9 +72,26 @@ def get_peft_model_state_dict(model, state_dict: dict | None = None, adapter_nam
     return {k.replace(f".{adapter_name}", ""): v for k, v in keep.items()}
 
 
-def save_lora_weights(model, save_folder: str, style: str = "diffusers") -> str:
+def save_lora_weights(model, save_folder: str, style: str = "diffusers", convert_pissa: bool = False, rank: int | None = None) -> str:
+    """convert_pissa: peft's PiSSA -> LoRA conversion (pissa.pissa_to_lora): B' = [B | B0], A' = [A ; -A0] with lora_alpha doubled,
+    a file that applies to the ORIGINAL base weights; rank=k resizes the converted pairs.  The default writes A, B as they are."""
     os.makedirs(save_folder, exist_ok=True)
     path = os.path.join(save_folder, WEIGHT_NAME)
+    if convert_pissa:
+        from .pissa import pissa_to_lora
+        tensors, alphas = pissa_to_lora(model, rank)
+        out = {}
+        for name, (a, b) in tensors.items():
+            if style == "diffusers":
+                renamed = name.endswith(_DIFFUSERS_RENAMED)
+                out[f"transformer.{name}" + (".lora.down.weight" if renamed else ".lora_A.weight")] = a
+                out[f"transformer.{name}" + (".lora.up.weight" if renamed else ".lora_B.weight")] = b
+            else:
+                out[f"{name}.lora_A.weight"], out[f"{name}.lora_B.weight"] = a, b
+        save_file(out, path, metadata={"format": "pt", "lora_alpha": repr({n: str(v) for n, v in alphas.items()})})
+        return path
+    if rank is not None:
+        raise ValueError("save_lora_weights: rank= goes with convert_pissa=True (resize.resize_lora_file resizes any other file)")
     alphas = {n: str(m.lora_alpha[m.active_adapter]) for n, m in model.named_modules() if isinstance(m, QfxLoraLinear)}
     save_file(get_lora_state_dict(model, style), path, metadata={"format": "pt", "lora_alpha": repr(alphas)})
     return path

@@ -162,6 +162,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._mod_keys = None      # timestep keys of the modulation table (None: the flow-match training timesteps / 1000)
         self._mod_table = None     # None: not decided; False: decided against; dict(keys, mods, out): see ensure_modulation_table
         self._dropout = None       # dropout.LoraDropoutState while network_dropout / rank_dropout are on (set_lora_dropout)
+        self._pissa = None         # dict(A0, B0, niter, oversample, seed) once the base weights are PiSSA residuals (pissa_init_)
 
     # ------------------------------------------------------------------ reference-surface methods
     @classmethod
@@ -255,8 +256,20 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         return r
 
     def add_adapter(self, adapter_config, adapter_name: str = "default", generator: torch.Generator | None = None):
-        """peft add_adapter look-alike (base_trainer.py:939): wrap matching Linears, freeze all but 'lora' params."""
+        """peft add_adapter look-alike (base_trainer.py:939): wrap matching Linears, freeze all but 'lora' params.
+        init_lora_weights="pissa" / "pissa_niter_N" (N <= 4) then runs pissa_init_ with 2 resp. N power iterations: the model
+        must be on the GPU (for a model moved later: any other init here, then model.pissa_init_(...) on the device)."""
         cfg = adapter_config
+        from ..pissa import check_config, parse_init
+        pissa_niter = parse_init(cfg.init_lora_weights)      # a ValueError for a bad spelling, before anything is wrapped
+        if pissa_niter is not None:
+            check_config(cfg.r, cfg.lora_alpha, "add_adapter")
+            if self._pissa is not None:
+                raise ValueError("add_adapter: the base weights are PiSSA residuals already")
+            if not self.device.type == "cuda":
+                raise RuntimeError(f"add_adapter: init_lora_weights={cfg.init_lora_weights!r} factorises the weights on the GPU and the "
+                                   f"model is on {self.device}: move it first, or add the adapter with another init and call "
+                                   "model.pissa_init_(...) on the device")
         names = [n for n, m in self.named_modules() if isinstance(m, QfxLinear) and ".base_layer" not in n
                  and not n.endswith("base_layer") and match_target(n, cfg.target_modules)]
         for n in names:
@@ -275,6 +288,7 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
                 parent[int(child)] = wrapped
             else:
                 setattr(parent, child, wrapped)
+        prev_name, prev_cfg = self._adapter_name, (getattr(self, "peft_config", None) or {}).get(adapter_name)
         self._adapter_name = adapter_name
         for pn, p in self.named_parameters():
             p.requires_grad_("lora" in pn)
@@ -290,6 +304,25 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._invalidate()
         self._adapter_gen += 1
         self._lora.tag()
+        if pissa_niter is not None:
+            try:
+                self.pissa_init_(niter=pissa_niter)
+            except Exception:      # (a non-finite weight, ...): no plain LoRA is left behind -- the linears wrapped above are unwrapped again
+                for n in names:
+                    parent_name, _, child = n.rpartition(".")
+                    parent = self.get_submodule(parent_name)
+                    if child.isdigit():
+                        parent[int(child)] = parent[int(child)].base_layer
+                    else:
+                        setattr(parent, child, getattr(parent, child).base_layer)
+                self._adapter_name = prev_name
+                if prev_cfg is None:
+                    del self.peft_config[adapter_name]
+                else:
+                    self.peft_config[adapter_name] = prev_cfg
+                self._invalidate()
+                self._lora.tag()
+                raise
         # The reference wraps its LoRA container in DDP right after this call (base_trainer.py:384-393); the kernels write dA / dB
         # straight into the flat gradient buffer, so the model exchanges them itself.  Under an initialised multi-rank process
         # group that happens without an extra line in the trainer (no-op otherwise; call enable_data_parallel(...) again to
@@ -362,10 +395,17 @@ class QwenImageTransformer2DModel(DataParallelMixin, nn.Module):
         self._merged = False
         self._invalidate()
 
-    def save_lora_weights(self, save_folder, style="diffusers"):
-        """pytorch_lora_weights.safetensors as BaseTrainer.save_lora writes it (base_trainer.py:858-875)."""
+    def save_lora_weights(self, save_folder, style="diffusers", convert_pissa=False, rank=None):
+        """pytorch_lora_weights.safetensors as BaseTrainer.save_lora writes it (base_trainer.py:858-875).  convert_pissa: after a
+        PiSSA initialisation, the rank-2r pair that applies to the ORIGINAL base weights (pissa.pissa_to_lora; rank=k resizes it)
+        where the default writes the residual-basis A, B a resumed run loads."""
         from ..lora_io import save_lora_weights
-        return save_lora_weights(self, save_folder, style)
+        return save_lora_weights(self, save_folder, style, convert_pissa=convert_pissa, rank=rank)
+
+    def pissa_init_(self, niter=2, oversample=8, seed=0, group_bytes=2 << 30):
+        """PiSSA initialisation of the adapters in place (qflux_amd.pissa.pissa_init_): the model is on the GPU."""
+        from ..pissa import pissa_init_
+        return pissa_init_(self, niter=niter, oversample=oversample, seed=seed, group_bytes=group_bytes)
 
     def load_lora_adapter(self, path, adapter_name="default", lora_alpha=None):
         """DIFFUSERS- or PEFT-style LoRA file/folder (base_trainer.py:977-999)."""

@@ -1092,6 +1092,56 @@ def lowrank_sketch(table, pflat, normsq, info, skipped, ws, power_iters=2, seed=
     L.check(lib.qfx_lowrank_sketch(a, stream_ptr()), "qfx_lowrank_sketch")
 
 
+LORA_FOLD_MAX_RANK = 64
+
+
+class LoraFoldLayout:
+    """Descriptor table of qfx_lora_fold, built once per set of matrices.  rows[i] = (off_a, off_b, r, in_features, out_features,
+    c); extent: elements the flat buffer of A / B needs; host: the ctypes array (read again at every launch); tile_start: the
+    device words the launch writes; keep: the tensors the table points at."""
+
+    def __init__(self, table, rows, extent, host, tile_start, keep):
+        self.table, self.rows, self.extent, self.host, self.tile_start, self.keep = table, rows, extent, host, tile_start, keep
+        self.n_mats = len(rows)
+
+
+_LORA_FOLD_TABLE = _TableSpec("lora_fold", L.LoraFoldMat, LORA_FOLD_MAX_RANK,
+                              refused="a dimension, a leading dimension, an offset, or two matrices that overlap",
+                              over="matrix {i} has rank {r}: ranks above {cap} are not implemented", none="matrices")
+
+
+def lora_fold_table(mats, device=None, n_elems=None):
+    """mats: (W, off_a, off_b, r, c) per matrix -- W a 2-D device tensor [out, in] with unit column stride, bfloat16 or float32,
+    folded in place; A [r, in] at off_a and B [out, r] at off_b of the flat fp32 buffer; c the coefficient of B A.  Checked by
+    qfx_lora_fold_check_table against n_elems (default: the extent of the rows themselves) before it goes to the device."""
+    keep = []
+
+    def described():
+        for i, (W, off_a, off_b, r, c) in enumerate(mats):
+            if W is None or W.dim() != 2 or W.dtype not in _LOWRANK_DTYPES or W.stride(1) != 1:
+                raise ValueError(f"lora_fold table: matrix {i}: W must be a 2-D bfloat16 or float32 tensor with unit column stride")
+            nout, nin = W.shape
+            row = (int(off_a), int(off_b), int(r), int(nin), int(nout), float(c))
+            keep.append(W)
+            yield row, (_p(W), W.stride(0) if nout > 1 else max(W.stride(0), nin), row[0], row[1], row[2], row[3], row[4],
+                        _LOWRANK_DTYPES[W.dtype], row[5])
+    b = _pair_table(_LORA_FOLD_TABLE, described(), device, n_elems)
+    tile_start = torch.zeros(len(b.rows) + 1, dtype=torch.int64, device=device)
+    return LoraFoldLayout(b.table, b.rows, b.extent, b.host, tile_start, keep)
+
+
+def lora_fold(table, pflat):
+    """W <- W + c B A for every matrix of `table` (a lora_fold_table), in place, with A and B read from pflat: fp64 dots in
+    index order, one rounding to fp32 and for a bfloat16 W one more to bfloat16 -- the same bits at any address and in any table
+    order.  One launch over (64 x 64 tile, matrix) behind a one-workgroup prefix launch; nothing synchronises.  See qfx.h."""
+    dev = pflat.device
+    _svd_buf("lora_fold", "pflat", pflat, torch.float32, table.extent, dev)
+    if table.table.device != dev or table.tile_start.device != dev or any(w.device != dev for w in table.keep):
+        raise ValueError("lora_fold: the descriptor table or a matrix lives on another device")
+    a = L.LoraFoldArgs(_p(table.table), C.cast(table.host, C.c_void_p), table.n_mats, 0, _p(pflat), pflat.numel(), _p(table.tile_start))
+    L.check(lib.qfx_lora_fold(a, stream_ptr()), "qfx_lora_fold")
+
+
 SCALED_ADAMW_MAX_RANK = 64
 
 

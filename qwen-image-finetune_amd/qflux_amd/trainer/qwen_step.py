@@ -673,9 +673,14 @@ class QwenLoraTrainStep:
         swapped-back y, and so does a run resumed from the folder.
         With ema_decay the weights file holds the trained weights (resume is exact), pytorch_lora_weights_ema.safetensors holds
         shadow 0 and _ema1 ... the others, each written by the same writer with the shadow swapped in (any LoRA loader reads them),
-        and ema.bin is torch.save of EmaState.state_dict(); the step ends in the form it was in."""
+        and ema.bin is torch.save of EmaState.state_dict(); the step ends in the form it was in.
+        After a PiSSA initialisation state.json also carries "pissa": its (niter, oversample, seed) -- the residual trunk itself
+        is not stored, load_checkpoint rebuilds it bit for bit from the original weights."""
         import json
         os.makedirs(save_dir, exist_ok=True)
+        pissa = getattr(self.dit, "_pissa", None)
+        if pissa is not None:
+            extra_state = dict(extra_state or {}, pissa={k: pissa[k] for k in ("niter", "oversample", "seed")})
         if self.ema_decays is not None:
             self._save_ema(save_dir)
         else:
@@ -715,8 +720,22 @@ class QwenLoraTrainStep:
         Schedule-free: the step ends in train mode.  Weights read from the folder are the averaged x whatever optimizer.bin says
         (save_checkpoint writes them in eval mode); weights already in place are x when the file says train_mode=False.  Either
         way y is reconstructed from x and the file's z with train()'s lerp -- the same launch on the same bits as the swap back in
-        save_checkpoint, so the resumed run continues like the run that wrote the folder."""
+        save_checkpoint, so the resumed run continues like the run that wrote the folder.
+        A folder written after a PiSSA initialisation names its (niter, oversample, seed): a model that still holds the ORIGINAL
+        weights is initialised with them first (the same residual trunk, bit for bit), then the trained A, B are loaded over
+        A0, B0 -- so such a folder needs adapter_name, and a model whose adapters exist with the run's rank and lora_alpha."""
         import json
+        with open(os.path.join(save_dir, "state.json")) as f:
+            pissa = json.load(f).get("pissa")
+        if pissa is not None:
+            have = getattr(self.dit, "_pissa", None)
+            if have is None:
+                if adapter_name is None:
+                    raise ValueError(f"{save_dir} was trained from a PiSSA initialisation {pissa}: pass adapter_name, so that the trained "
+                                     "weights are loaded after the residual trunk has been rebuilt")
+                self.dit.pissa_init_(**pissa)
+            elif any(have[k] != pissa[k] for k in pissa):
+                raise ValueError(f"{save_dir} was trained from the PiSSA initialisation {pissa}, the model holds another one")
         if adapter_name is not None:
             self.dit.load_lora_adapter(save_dir, adapter_name=adapter_name)
         self.load_state_dict(torch.load(os.path.join(save_dir, "optimizer.bin"), map_location="cpu", weights_only=False))
